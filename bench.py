@@ -12,13 +12,20 @@ matrix -- BASELINE.json configs[2]: 1M cells x 20k genes -- with rank r holding 
 ``--scaling weak``: every rank holds a full-size gene shard (N x 20k genes in total).  value = gene-tests of all ranks /
 max-over-ranks time.
 
-Extra objects on the JSON line:
+A plain run sets up, warms up, times the steps and prints the JSON line (metric, value, unit, higher_is_better, dtype,
+ms_per_step, ...).  ``--dump-outputs DIR`` also writes what the last timed step computed -- the arrays a caller of
+compute_1d_moments + ht_1d_moments receives -- as DIR/<name>.npy (float64, rank 0), so two builds can be compared output for
+output on identical inputs.
+
+``--full`` adds everything else the bench measures, each with launches or processes of its own (``--extra`` implies it).
+Extra objects on the JSON line with ``--full``:
   "roofline"      the K1 kernel on the bytes it really moves (the packed 4 B/entry count blocks): bytes / HIP-event time vs 8 TB/s
   "roofline_csr"  SURVEY.md section 8(d)'s unit of work -- the CSR's 8 B/nnz + per-cell and output vectors -- over the time of
                   CSR -> moments for one grouping: ingest (K0: count + layout + scatter, paid once per grouping) + K1
   "bootstrap"     binomial draws/s of the replay kernel, refilled-chain fraction
   "cpu_baseline"  the CPU oracle on a bounded sample (rank 0, N=1 only); "reference_cpu": the REAL reference timed in the build
                   container (baselines/ref_cpu_*.json, other hardware, stated as such)
+  "e2e"           the step plus the CSR upload and the ingest (N=1 only), also as "value_e2e"
 """
 
 import argparse
@@ -47,6 +54,7 @@ CONFIGS = {
 }
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: 8 TB/s spec (6.3 TB/s achievable)
 TRAFFIC_FILE = "r03_k1_traffic_C3.json"   # this round's PMC record of K1's HBM traffic (tools/k1_traffic.py)
+DUMP_BUDGET_BYTES = 64 << 20              # --dump-outputs: at most this much in all
 
 
 def calibrated_profile(cfg, seed):
@@ -130,6 +138,35 @@ def sample_columns(csr, genes, torch):
     return out
 
 
+def step_outputs(adata, state):
+    """What one step hands its caller, as float64 copies: the flat 1d_ht vectors (gene-major, one entry per test), the 1D moments
+    [group][kept gene], the gene filter, the kept genes' column indices, the pooled mean-variance fit and the binned size factors."""
+    m = adata.uns["memento"]
+    groups = m["groups"]
+    out = {k: m["1d_ht"][k] for k in ("mean_coef", "mean_se", "mean_asl", "var_coef", "var_se", "var_asl")}
+    for i, k in enumerate(("mean", "var", "res_var")):
+        out["moments_" + k] = np.stack([m["1d_moments"][g][i] for g in groups])
+    out["overall_gene_filter"] = m["overall_gene_filter"]
+    out["kept_gene_index"] = state.gene_idx
+    out["mv_fit"] = m["mv_regressor"]["all"]
+    out["approx_size_factor"] = m["all_approx_size_factor"]
+    return {k: np.array(v, dtype=np.float64) for k, v in out.items()}
+
+
+def write_outputs(directory, arrays):
+    """DIR/<name>.npy for every array.  Above DUMP_BUDGET_BYTES in all, every array is cut to the same fixed, seeded sample share
+    and DIR/<name>_sample_index.npy records the flat positions kept."""
+    os.makedirs(directory, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > DUMP_BUDGET_BYTES and a.size:
+            keep = max(1, int(a.size * DUMP_BUDGET_BYTES / (2 * total)))      # values + indices, 8 B each
+            idx = np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))
+            np.save(os.path.join(directory, name + "_sample_index.npy"), idx.astype(np.float64))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(directory, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -144,13 +181,21 @@ def main():
                     help="single process, no collectives: time the step of each of the N cost-balanced gene shards of the config on this "
                          "GPU, one after the other, and print the per-shard times and the predicted N-GPU makespan (a PREDICTION, "
                          "not a multi-GPU measurement)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: K1 roofline, CSR roofline, bootstrap draw rate and fast mode, CPU baseline, recorded "
+                         "reference CPU timing, end-to-end value (each with launches or processes of its own)")
     ap.add_argument("--extra", action="store_true",
-                    help="also time BASELINE.json configs[3] (one GPU's share: 250 x 2000 gene pairs, 500k cells, 1k bootstraps) and "
-                         "configs[4] (Perturb-seq: 200k x 15k, 500 guides vs control, 5k bootstraps) and add pair_tests_per_s / "
-                         "vs_control_tests_per_s to the JSON line (N = 1 only; about two more minutes)")
+                    help="--full, and also time BASELINE.json configs[3] (one GPU's share: 250 x 2000 gene pairs, 500k cells, 1k "
+                         "bootstraps) and configs[4] (Perturb-seq: 200k x 15k, 500 guides vs control, 5k bootstraps) and add "
+                         "pair_tests_per_s / vs_control_tests_per_s to the JSON line (N = 1 only; about two more minutes)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float64, rank 0)")
     ap.add_argument("--scaling", choices=["strong", "weak"], default="strong",
                     help="strong: the same 20k-gene matrix split over the ranks (configs[2]); weak: a full-size gene shard per rank")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    args.full = args.full or args.extra
     cfg = CONFIGS[args.config]
 
     import torch
@@ -251,10 +296,12 @@ def main():
         nt = torch.tensor([float(n_tests)], dtype=torch.float64, device=cdev)
         torch.distributed.all_reduce(nt, op=torch.distributed.ReduceOp.SUM)
         elapsed, n_tests = float(tt.item()), float(nt.item())
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, step_outputs(adata, state))
 
-    # ---- roofline of the dominant HBM kernel (K1 moments) and bootstrap draw rate, rank 0 --------
+    # ---- --full: roofline of the dominant HBM kernel (K1 moments) and bootstrap draw rate, rank 0 --------
     roof = roof_csr = boot = cpu = None
-    if rank == 0:
+    if rank == 0 and args.full:
         blocks = state.blocks
         stream = engine._stream()
         d_inv = engine.dev((1.0 / adata.obs["memento_size_factor"].values)[blocks.cell_order])
@@ -344,7 +391,7 @@ def main():
             cpu = cpu_baseline(args, cfg, adata, csr, state, cov, trt, torch, last_seed=1000 + args.steps - 1)
 
     e2e = None
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and args.full:
         # SURVEY 8(d)'s metric to the letter: the step PLUS the upload of the CSR from pinned host memory and create_groups (K0
         # ingest) once per step -- value stays "inputs resident in HBM", value_e2e is printed beside it
         import ctypes
@@ -381,9 +428,10 @@ def main():
                                    f"{B} bootstraps, 1D moments + ht (resampling=bootstrap, approx=False)",
                        "rng": "numpy PCG64 multinomial replay; device refill of invalid replicates", "parallelism": f"genes x{world} (cost-balanced shards)" if world > 1 else "1 GPU",
                        "host_tail_fit_procs": args.num_cpus, "prep_s": round(prep_s, 2)},
-            "roofline": roof, "roofline_csr": roof_csr, "bootstrap": boot, "cpu_baseline": cpu, "reference_cpu": reference_cpu(args.config),
-            "e2e": e2e,
         }
+        if args.full:
+            line.update({"roofline": roof, "roofline_csr": roof_csr, "bootstrap": boot, "cpu_baseline": cpu,
+                         "reference_cpu": reference_cpu(args.config), "e2e": e2e})
         if e2e:
             line["value_e2e"] = e2e["value_e2e"]
         if args.extra and world == 1:
