@@ -344,6 +344,21 @@ int mm_contrast_stats(const double *d_ym, const double *d_yv, int64_t ld, int32_
 int mm_contrast_rows(const double *d_ym, const double *d_yv, int64_t ld, int32_t num_boot, int32_t n_groups, int32_t ctrl,
                      const int32_t *d_test_gene, const int32_t *d_test_grp, int64_t n_tests, int32_t which, double *d_out,
                      void *stream);
+/* ---- guide-vs-control contrasts with covariates (replicate / well / dose strata) ------------------------------
+ * test t: coef_c = sum_p design_w[p] * y[test_gene[t], design_grp[p]][c] over p in [design_ptr[d], design_ptr[d + 1]),
+ * d = test_design[t] -- the per-guide weighted regression of _regress_1d (hypothesis_test.py:242-300) on the guide's and
+ * the control's stratum groups, folded into one sparse weight row per design (memento/design.py).  Column c counts only
+ * if the mean and the variability rows of every listed group are finite there.  An empty design gives a NaN test.
+ * stats layout as mm_contrast_stats, mean and variability response in one launch. */
+int mm_contrast_design_stats(const double *d_ym, const double *d_yv, int64_t ld, int32_t num_boot, int32_t n_groups,
+                             const int32_t *d_test_gene, const int32_t *d_test_design, const int32_t *d_design_ptr,
+                             const int32_t *d_design_grp, const double *d_design_w, int64_t n_tests, double *d_stats_mean,
+                             double *d_stats_var, void *stream);
+/* coefficient rows [n_tests][ld] of selected design contrasts (NaN where a replicate column is not valid) */
+int mm_contrast_design_rows(const double *d_ym, const double *d_yv, int64_t ld, int32_t num_boot, int32_t n_groups,
+                            const int32_t *d_test_gene, const int32_t *d_test_design, const int32_t *d_design_ptr,
+                            const int32_t *d_design_grp, const double *d_design_w, int64_t n_tests, int32_t which, double *d_out,
+                            void *stream);
 
 /* ==== 2D (gene pairs) ===========================================================================
  * K11 step 1: copy the columns of the n_cols genes with d_col_id[gene] = m >= 0 out of the SELL blocks into a

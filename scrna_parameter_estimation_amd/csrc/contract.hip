@@ -450,6 +450,119 @@ __global__ __launch_bounds__(256) void k_contrast_rows(const double *__restrict_
   }
 }
 
+// ------------------------------------------------------------------------------------------------
+// Guide-vs-control contrasts with covariates (replicate / well / dose strata): test t applies the sparse weight row of
+// design test_design[t] -- the per-guide weighted regression of _regress_1d (hypothesis_test.py:242-300) on the guide's and
+// the control's stratum groups, folded into weights by memento/design.py -- to the resident replicate rows of gene
+// test_gene[t]:  coef_c = sum_p design_w[p] * y[gene, design_grp[p]][c]  for p in [design_ptr[d], design_ptr[d + 1]).
+// Column c is valid only if the mean AND the variability rows of every listed group are finite there (:249-251; groups with
+// a ~0 weight included).  An empty design (no good guide or control group, or no stratum holding both arms) gives the NaN
+// record of k_contrast_stats.  One workgroup per test; the coefficient is recomputed in the second pass instead of being
+// stored (a test reads 2 x |groups| rows; the control rows are shared by the gene's consecutive tests through L2 / MALL).
+__device__ __forceinline__ void design_coef(const double *__restrict__ ym, const double *__restrict__ yv, int64_t ld, int64_t row_base,
+                                            const int32_t *__restrict__ grp, const double *__restrict__ w, int p0, int p1, int c,
+                                            double &cm, double &cv, bool &ok) {
+  double am = 0.0, av = 0.0;
+  bool good = true;
+  for (int p = p0; p < p1; p++) {
+    int64_t o = (row_base + grp[p]) * ld + c;
+    double a = ym[o], v = yv[o], wp = w[p];
+    good = good && isfinite(a) && isfinite(v);
+    am += wp * a;
+    av += wp * v;
+  }
+  cm = am; cv = av; ok = good;
+}
+
+__global__ __launch_bounds__(K9_THREADS) void k_contrast_design_stats(const double *__restrict__ ym, const double *__restrict__ yv,
+                                                                      int64_t ld, int32_t num_boot, int32_t n_groups,
+                                                                      const int32_t *__restrict__ test_gene,
+                                                                      const int32_t *__restrict__ test_design,
+                                                                      const int32_t *__restrict__ design_ptr,
+                                                                      const int32_t *__restrict__ design_grp,
+                                                                      const double *__restrict__ design_w, double *__restrict__ stats_m,
+                                                                      double *__restrict__ stats_v) {
+  __shared__ double red[K9_THREADS / 64];
+  int64_t t = blockIdx.x;
+  int gene = test_gene[t], d = test_design[t];
+  int p0 = design_ptr[d], p1 = design_ptr[d + 1];
+  double *sm_ = stats_m + t * 8, *sv_ = stats_v + t * 8;
+  if (p1 <= p0) {
+    if (threadIdx.x == 0) {
+      for (int i = 0; i < 8; i++) {
+        sm_[i] = (i == 2 || i == 3 || i == 5) ? 0.0 : NAN;
+        sv_[i] = (i == 2 || i == 3 || i == 5) ? 0.0 : NAN;
+      }
+    }
+    return;
+  }
+  int64_t row_base = (int64_t)gene * n_groups;
+  int n_cols = num_boot + 1;
+  double sum_m = 0, sum_v = 0, cnt = 0, mn_m = INFINITY, mx_m = -INFINITY, mn_v = INFINITY, mx_v = -INFINITY;
+  for (int c = threadIdx.x; c < n_cols; c += K9_THREADS) {
+    double dm, dv;
+    bool ok;
+    design_coef(ym, yv, ld, row_base, design_grp, design_w, p0, p1, c, dm, dv, ok);
+    if (ok) {
+      mn_m = fmin(mn_m, dm); mx_m = fmax(mx_m, dm);
+      mn_v = fmin(mn_v, dv); mx_v = fmax(mx_v, dv);
+      if (c > 0) { sum_m += dm; sum_v += dv; cnt += 1.0; }
+    }
+  }
+  double n = wg_sum(cnt, red);
+  double tm = wg_sum(sum_m, red), tv = wg_sum(sum_v, red);
+  double lo_m = wg_min(mn_m, red), hi_m = wg_max(mx_m, red), lo_v = wg_min(mn_v, red), hi_v = wg_max(mx_v, red);
+  double c0m, c0v;
+  bool ok0;
+  design_coef(ym, yv, ld, row_base, design_grp, design_w, p0, p1, 0, c0m, c0v, ok0);   // the observed coefficient (column 0)
+  if (!ok0) { c0m = NAN; c0v = NAN; }
+  double mean_m = n > 0 ? tm / n : NAN, mean_v = n > 0 ? tv / n : NAN;
+  double am = fabs(c0m), av = fabs(c0v);
+  double sq_m = 0, sq_v = 0, ex_m = 0, ex_v = 0, rw_m = 0, rw_v = 0;
+  for (int c = 1 + threadIdx.x; c < n_cols; c += K9_THREADS) {
+    double dm, dv;
+    bool ok;
+    design_coef(ym, yv, ld, row_base, design_grp, design_w, p0, p1, c, dm, dv, ok);
+    if (ok) {
+      sq_m += (dm - mean_m) * (dm - mean_m);
+      sq_v += (dv - mean_v) * (dv - mean_v);
+      double nm = dm - c0m, nv = dv - c0v;
+      if (nm > am || nm < -am) ex_m += 1.0;
+      if (nv > av || nv < -av) ex_v += 1.0;
+      if (dm > am || dm < -am) rw_m += 1.0;
+      if (dv > av || dv < -av) rw_v += 1.0;
+    }
+  }
+  double qm = wg_sum(sq_m, red), qv = wg_sum(sq_v, red), em = wg_sum(ex_m, red), ev = wg_sum(ex_v, red);
+  double rm = wg_sum(rw_m, red), rv = wg_sum(rw_v, red);
+  if (threadIdx.x == 0) {
+    sm_[0] = c0m; sm_[1] = n > 0 ? sqrt(qm / n) : NAN; sm_[2] = n; sm_[3] = em; sm_[4] = mean_m - c0m;
+    sm_[5] = (lo_m == hi_m) ? 1.0 : 0.0; sm_[6] = rm; sm_[7] = hi_m - lo_m;
+    sv_[0] = c0v; sv_[1] = n > 0 ? sqrt(qv / n) : NAN; sv_[2] = n; sv_[3] = ev; sv_[4] = mean_v - c0v;
+    sv_[5] = (lo_v == hi_v) ? 1.0 : 0.0; sv_[6] = rv; sv_[7] = hi_v - lo_v;
+  }
+}
+
+// coefficient rows of selected design contrasts (for the host-side tail fits); NaN in the columns that are not valid
+__global__ __launch_bounds__(256) void k_contrast_design_rows(const double *__restrict__ ym, const double *__restrict__ yv, int64_t ld,
+                                                              int32_t num_boot, int32_t n_groups, const int32_t *__restrict__ test_gene,
+                                                              const int32_t *__restrict__ test_design,
+                                                              const int32_t *__restrict__ design_ptr,
+                                                              const int32_t *__restrict__ design_grp,
+                                                              const double *__restrict__ design_w, int32_t which,
+                                                              double *__restrict__ out) {
+  int64_t t = blockIdx.x;
+  int gene = test_gene[t], d = test_design[t];
+  int p0 = design_ptr[d], p1 = design_ptr[d + 1];
+  int64_t row_base = (int64_t)gene * n_groups;
+  for (int c = threadIdx.x; c <= num_boot; c += 256) {
+    double dm, dv;
+    bool ok;
+    design_coef(ym, yv, ld, row_base, design_grp, design_w, p0, p1, c, dm, dv, ok);
+    out[t * ld + c] = (ok && p1 > p0) ? (which ? dv : dm) : NAN;
+  }
+}
+
 extern "C" {
 
 int mm_contract_stats(const double *d_ym, const double *d_yv, int64_t ld, int32_t num_boot, int32_t n_groups,
@@ -525,6 +638,32 @@ int mm_contrast_rows(const double *d_ym, const double *d_yv, int64_t ld, int32_t
   if (n_tests == 0) return MM_OK;
   hipLaunchKernelGGL(k_contrast_rows, dim3((unsigned)n_tests), dim3(256), 0, (hipStream_t)stream, d_ym, d_yv, ld, num_boot, n_groups, ctrl,
                      d_test_gene, d_test_grp, which, d_out);
+  MM_LAUNCH_CHECK();
+  return MM_OK;
+}
+
+int mm_contrast_design_stats(const double *d_ym, const double *d_yv, int64_t ld, int32_t num_boot, int32_t n_groups,
+                             const int32_t *d_test_gene, const int32_t *d_test_design, const int32_t *d_design_ptr,
+                             const int32_t *d_design_grp, const double *d_design_w, int64_t n_tests, double *d_stats_mean,
+                             double *d_stats_var, void *stream) {
+  MM_ARG(d_ym && d_yv && d_test_gene && d_test_design && d_design_ptr && d_design_grp && d_design_w && d_stats_mean && d_stats_var);
+  MM_ARG(n_tests >= 0 && n_tests < 2147483647LL && n_groups > 0 && num_boot > 0 && ld >= (int64_t)num_boot + 1);
+  if (n_tests == 0) return MM_OK;
+  hipLaunchKernelGGL(k_contrast_design_stats, dim3((unsigned)n_tests), dim3(K9_THREADS), 0, (hipStream_t)stream, d_ym, d_yv, ld, num_boot,
+                     n_groups, d_test_gene, d_test_design, d_design_ptr, d_design_grp, d_design_w, d_stats_mean, d_stats_var);
+  MM_LAUNCH_CHECK();
+  return MM_OK;
+}
+
+int mm_contrast_design_rows(const double *d_ym, const double *d_yv, int64_t ld, int32_t num_boot, int32_t n_groups,
+                            const int32_t *d_test_gene, const int32_t *d_test_design, const int32_t *d_design_ptr,
+                            const int32_t *d_design_grp, const double *d_design_w, int64_t n_tests, int32_t which, double *d_out,
+                            void *stream) {
+  MM_ARG(d_ym && d_yv && d_test_gene && d_test_design && d_design_ptr && d_design_grp && d_design_w && d_out);
+  MM_ARG(n_tests >= 0 && n_tests < 2147483647LL && n_groups > 0 && num_boot > 0 && ld >= (int64_t)num_boot + 1 && (which == 0 || which == 1));
+  if (n_tests == 0) return MM_OK;
+  hipLaunchKernelGGL(k_contrast_design_rows, dim3((unsigned)n_tests), dim3(256), 0, (hipStream_t)stream, d_ym, d_yv, ld, num_boot, n_groups,
+                     d_test_gene, d_test_design, d_design_ptr, d_design_grp, d_design_w, which, d_out);
   MM_LAUNCH_CHECK();
   return MM_OK;
 }

@@ -896,6 +896,44 @@ class Bootstrap1D:
 
         return host(st_m)[:n_tests], host(st_v)[:n_tests], rows
 
+    def contrast_design(self, test_gene, test_design, design_ptr, design_grp, design_w):
+        """Guide-vs-control contrasts with covariates (mm_contrast_design_stats): test t applies the sparse weight row
+        ``design_grp/design_w[design_ptr[d]:design_ptr[d + 1]]``, d = ``test_design[t]``, to the replicate rows of gene
+        ``test_gene[t]``.  Returns (stats_mean, stats_var) host arrays [n_tests][8] and ``rows(which, idx)``, as ``contrast``."""
+        torch = _torch()
+        test_gene = np.asarray(test_gene, dtype=np.int32)
+        test_design = np.asarray(test_design, dtype=np.int32)
+        design_ptr = np.asarray(design_ptr, dtype=np.int32)
+        design_grp = np.asarray(design_grp, dtype=np.int32)
+        design_w = np.asarray(design_w, dtype=np.float64)
+        n_tests, n_designs = len(test_gene), len(design_ptr) - 1
+        # the kernel trusts these indices: check them here
+        if len(test_design) != n_tests or n_designs < 0 or len(design_w) != len(design_grp):
+            raise ValueError("contrast_design: inconsistent table sizes")
+        if n_designs >= 0 and len(design_ptr) and (design_ptr[0] != 0 or design_ptr[-1] != len(design_grp) or (np.diff(design_ptr) < 0).any()):
+            raise ValueError("contrast_design: design_ptr is not a CSR pointer over design_grp")
+        if len(design_grp) and (design_grp.min() < 0 or design_grp.max() >= self.ng):
+            raise ValueError("contrast_design: group index out of range")
+        if n_tests and (test_gene.min() < 0 or test_gene.max() >= self.n_tested or test_design.min() < 0 or test_design.max() >= n_designs):
+            raise ValueError("contrast_design: test index out of range")
+        st_m = empty((max(1, n_tests), 8), torch.float64)
+        st_v = empty((max(1, n_tests), 8), torch.float64)
+        d_ptr, d_grp = dev(design_ptr), dev(design_grp if len(design_grp) else np.zeros(1, np.int32))
+        d_w = dev(design_w if len(design_w) else np.zeros(1))
+        d_tg, d_td = dev(test_gene), dev(test_design)
+        _lib.call("mm_contrast_design_stats", P(self.ym), P(self.yv), self.ld, self.B, self.ng, P(d_tg), P(d_td), P(d_ptr), P(d_grp), P(d_w),
+                  n_tests, P(st_m), P(st_v), _stream())
+
+        def rows(which, idx):
+            idx = np.asarray(idx, dtype=np.int64)
+            out = empty((max(1, len(idx)), self.ld), torch.float64)
+            a, b = dev(test_gene[idx]), dev(test_design[idx])
+            _lib.call("mm_contrast_design_rows", P(self.ym), P(self.yv), self.ld, self.B, self.ng, P(a), P(b), P(d_ptr), P(d_grp), P(d_w),
+                      len(idx), int(which), P(out), _stream())
+            return host(out)[: len(idx)]
+
+        return host(st_m)[:n_tests], host(st_v)[:n_tests], rows
+
     def valid_cols(self, good):
         """hypothesis_test.py:249-251 on the device: (col_map device tensor [n_tested][B+1], n_valid host [n_tested]) --
         the replicate columns in which every good group is finite in both the mean and the variability rows."""

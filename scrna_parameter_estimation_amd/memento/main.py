@@ -723,7 +723,7 @@ def ht_1d_moments(adata, covariate, treatment, treatment_for_gene=None, inplace=
 
 
 def ht_1d_vs_control(adata, control, num_boot=10000, num_cpus=1, rng='replay', fill_seed=0, max_rows=None, approx=False,
-                     resampling='bootstrap'):
+                     resampling='bootstrap', *, treatment_col=None):
     """Perturb-seq style batch test: every group against one shared ``control`` group (a label of
     ``adata.uns['memento']['groups']`` or its index), for all kept genes, in one call.
 
@@ -735,14 +735,35 @@ def ht_1d_vs_control(adata, control, num_boot=10000, num_cpus=1, rng='replay', f
     gene filters and the mean-variance fit are those of ``compute_1d_moments`` over ALL groups (the per-guide loop refits
     them on each two-group subset), so numbers differ from that loop by the fit, not by the test.
 
+    With ``treatment_col`` (one of the label columns, e.g. ``'guide'``) the groups are guide x stratum and every other label
+    column is a covariate (replicate, well, dose): ``control`` is then a VALUE of that column (compared as the string it has
+    in the group labels), and the test of guide value ``g`` is the per-guide regression the reference's loop runs on the
+    subset ``{g, control}`` with ``create_groups([is_g, *other_columns])`` -- intercept, the is_g indicator and main-effect
+    dummies of the other columns, weighted by cells per group -- over that gene's good guide and control groups of any
+    stratum.  A test with no good guide or control group, or with no stratum holding both arms, is NaN.  The ``group``
+    column of the result is then the guide value.
+
     Returns a DataFrame (gene, group, de_coef, de_se, de_pval, dv_coef, dv_se, dv_pval) and stores the arrays in
     ``uns['memento']['1d_ht_vs_control']``."""
     m = adata.uns['memento']
     st = m['_hip']
     groups = m['groups']
     ng = len(groups)
-    ctrl = groups.index(control) if not isinstance(control, (int, np.integer)) else int(control)
-    others = [j for j in range(ng) if j != ctrl]
+    designs = None
+    if treatment_col is not None:
+        label_columns = list(m['label_columns'])
+        if treatment_col not in label_columns:
+            raise ValueError(f"treatment_col {treatment_col!r} is not one of the label columns {label_columns}")
+        k_trt = label_columns.index(treatment_col)
+        labels = [g.split(m['label_delimiter'])[1:] for g in groups]
+        Nc = np.array([m['group_cells'][g].shape[0] for g in groups], dtype=np.float64)
+        designs = _design.VsControlDesigns(labels, k_trt, str(control), Nc)     # raises ValueError for an absent control value
+        covariates = [c for c in label_columns if c != treatment_col]
+        tested = designs.guides
+    else:
+        ctrl = groups.index(control) if not isinstance(control, (int, np.integer)) else int(control)
+        others = [j for j in range(ng) if j != ctrl]
+        tested = [groups[j] for j in others]
     mean_only = m['estimator_type'] == 'mean_only'
     names = _var_names(adata)
     gq = np.array([m['group_q'][g] for g in groups])
@@ -756,7 +777,7 @@ def ht_1d_vs_control(adata, control, num_boot=10000, num_cpus=1, rng='replay', f
     chunk = max(1, int(max_rows) // max(1, ng))
     cols = {k: [] for k in ('mean_coef', 'mean_se', 'mean_asl', 'var_coef', 'var_se', 'var_asl')}
     bs = rows = None
-    st.last_bootstrap = None                   # (see ht_1d_moments: free the previous call's replicate rows first)
+    st.last_bootstrap = st.last_good = None    # (see ht_1d_moments: free the previous call's replicate rows first)
     for g0 in range(0, G_all, chunk):
         g1 = min(G_all, g0 + chunk)
         G = g1 - g0
@@ -773,9 +794,14 @@ def ht_1d_vs_control(adata, control, num_boot=10000, num_cpus=1, rng='replay', f
         r1[live], r0[live] = u[0::2], u[1::2]
         n_inv = bs.run(skip, r1, r0, fit, fill_mode=0, fill_seed=fill_seed, fast=(rng == 'fast'), mean_only=mean_only)
         good = ((~skip) & (bs.K >= 2) & ~(n_inv < 0).any(axis=1)).reshape(G, ng)
-        test_gene = np.repeat(np.arange(G), len(others))
-        test_grp = np.tile(np.asarray(others), G)
-        st_m, st_v, rows = bs.contrast(test_gene, test_grp, ctrl, good)
+        st.last_good = good                    # (diagnostics / tests: the good groups of the last gene chunk)
+        test_gene = np.repeat(np.arange(G), len(tested))
+        if designs is None:
+            test_grp = np.tile(np.asarray(others), G)
+            st_m, st_v, rows = bs.contrast(test_gene, test_grp, ctrl, good)
+        else:
+            test_design = designs.tests(good)
+            st_m, st_v, rows = bs.contrast_design(test_gene, test_design, *designs.tables())
         for tag, stt, which in (('mean', st_m, 0), ('var', st_v, 1)):
             p = _asl.asl_from_stats(stt, approx, lambda idx, w=which: rows(w, idx), num_cpus, resampling)
             cols[tag + '_coef'].append(stt[:, 0])
@@ -783,8 +809,11 @@ def ht_1d_vs_control(adata, control, num_boot=10000, num_cpus=1, rng='replay', f
             cols[tag + '_asl'].append(p)
     out = {k: (np.concatenate(v) if v else np.zeros(0)) for k, v in cols.items()}
     st.last_bootstrap, st.last_chunk = bs, ((g0, g1) if G_all else (0, 0))       # diagnostics / tests: the last gene chunk's replicate rows
-    m['1d_ht_vs_control'] = dict(out, control=groups[ctrl], groups=[groups[j] for j in others])
-    df = pd.DataFrame({'gene': np.repeat(names, len(others)), 'group': np.tile([groups[j] for j in others], G_all)})
+    if designs is None:
+        m['1d_ht_vs_control'] = dict(out, control=groups[ctrl], groups=tested)
+    else:
+        m['1d_ht_vs_control'] = dict(out, control=str(control), groups=tested, treatment_col=treatment_col, covariates=covariates)
+    df = pd.DataFrame({'gene': np.repeat(names, len(tested)), 'group': np.tile(tested, G_all)})
     df['de_coef'], df['de_se'], df['de_pval'] = out['mean_coef'], out['mean_se'], out['mean_asl']
     df['dv_coef'], df['dv_se'], df['dv_pval'] = out['var_coef'], out['var_se'], out['var_asl']
     return df
