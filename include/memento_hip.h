@@ -360,6 +360,20 @@ int mm_contrast_design_rows(const double *d_ym, const double *d_yv, int64_t ld, 
                             const int32_t *d_design_grp, const double *d_design_w, int64_t n_tests, int32_t which, double *d_out,
                             void *stream);
 
+/* Guide-vs-control contrasts on ONE response plane d_y (the replicate correlations of the 2D bootstrap, rows
+ * [pair * n_groups + group][ld]): test t applies the sparse weight row of design d_test_design[t] to the rows of pair
+ * d_test_row[t], coef_c = sum_p d_design_w[p] * y[d_test_row[t] * n_groups + d_design_grp[p]][c].  A plain two-group
+ * test is the design {(guide, +1), (control, -1)}; an empty design gives a NaN test.  Column c counts only if every
+ * listed group is finite there.  The index tables are trusted: validate them on the host.  d_stats [n_tests][8], layout
+ * as mm_contrast_stats. */
+int mm_contrast_design1_stats(const double *d_y, int64_t ld, int32_t num_boot, int32_t n_groups, const int32_t *d_test_row,
+                              const int32_t *d_test_design, const int32_t *d_design_ptr, const int32_t *d_design_grp,
+                              const double *d_design_w, int64_t n_tests, double *d_stats, void *stream);
+/* coefficient rows [n_tests][ld] of selected single-plane design contrasts (NaN where a replicate column is not valid) */
+int mm_contrast_design1_rows(const double *d_y, int64_t ld, int32_t num_boot, int32_t n_groups, const int32_t *d_test_row,
+                             const int32_t *d_test_design, const int32_t *d_design_ptr, const int32_t *d_design_grp,
+                             const double *d_design_w, int64_t n_tests, double *d_out, void *stream);
+
 /* ==== 2D (gene pairs) ===========================================================================
  * K11 step 1: copy the columns of the n_cols genes with d_col_id[gene] = m >= 0 out of the SELL blocks into a
  * gene-contiguous store: entries of (block b, column m) at d_out[col_ptr[b*(n_cols+1)+m] .. col_ptr[b*(n_cols+1)+m+1])

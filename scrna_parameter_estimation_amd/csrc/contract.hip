@@ -563,6 +563,98 @@ __global__ __launch_bounds__(256) void k_contrast_design_rows(const double *__re
   }
 }
 
+// ------------------------------------------------------------------------------------------------
+// Guide-vs-control contrasts on ONE response plane (the replicate correlations of Bootstrap2D, ht_2d_vs_control): test t
+// applies the sparse weight row of design test_design[t] to the rows of pair test_row[t]:
+//   coef_c = sum_p design_w[p] * y[test_row[t] * n_groups + design_grp[p]][c],  p in [design_ptr[d], design_ptr[d + 1]).
+// The plain two-group test is the design {(guide, +1), (control, -1)}; an empty design gives the NaN record.  Column c is
+// valid only if every listed group is finite there (_regress_2d, hypothesis_test.py:372-373).  Against running the plane
+// through k_contrast_design_stats as both ym and yv this reads every byte once, tests it once and writes one record.
+// Two passes that recompute the coefficient (nothing per-replicate is stored): a test reads 2 x |design| rows, and the
+// control rows of a pair are shared by its consecutive tests through L2 / MALL (tests are issued pair-major).
+__device__ __forceinline__ double design1_coef(const double *__restrict__ y, int64_t ld, int64_t row_base, const int32_t *__restrict__ grp,
+                                               const double *__restrict__ w, int p0, int p1, int c, bool &ok) {
+  double acc = 0.0;
+  bool good = true;
+  for (int p = p0; p < p1; p++) {
+    double a = y[(row_base + grp[p]) * ld + c];
+    good = good && isfinite(a);
+    acc += w[p] * a;
+  }
+  ok = good;
+  return acc;
+}
+
+__global__ __launch_bounds__(K9_THREADS) void k_contrast_design1_stats(const double *__restrict__ y, int64_t ld, int32_t num_boot,
+                                                                       int32_t n_groups, const int32_t *__restrict__ test_row,
+                                                                       const int32_t *__restrict__ test_design,
+                                                                       const int32_t *__restrict__ design_ptr,
+                                                                       const int32_t *__restrict__ design_grp,
+                                                                       const double *__restrict__ design_w, double *__restrict__ stats) {
+  __shared__ double red[K9_THREADS / 64];
+  int64_t t = blockIdx.x;
+  int d = test_design[t];
+  int p0 = design_ptr[d], p1 = design_ptr[d + 1];
+  double *st = stats + t * 8;
+  if (p1 <= p0) {
+    if (threadIdx.x == 0)
+      for (int i = 0; i < 8; i++) st[i] = (i == 2 || i == 3 || i == 5) ? 0.0 : NAN;
+    return;
+  }
+  int64_t row_base = (int64_t)test_row[t] * n_groups;
+  int n_cols = num_boot + 1;
+  double sum = 0, cnt = 0, mn = INFINITY, mx = -INFINITY;
+  for (int c = threadIdx.x; c < n_cols; c += K9_THREADS) {
+    bool ok;
+    double v = design1_coef(y, ld, row_base, design_grp, design_w, p0, p1, c, ok);
+    if (ok) {
+      mn = fmin(mn, v); mx = fmax(mx, v);
+      if (c > 0) { sum += v; cnt += 1.0; }
+    }
+  }
+  double n = wg_sum(cnt, red), tot = wg_sum(sum, red);
+  double lo = wg_min(mn, red), hi = wg_max(mx, red);
+  bool ok0;
+  double c0 = design1_coef(y, ld, row_base, design_grp, design_w, p0, p1, 0, ok0);   // the observed coefficient (column 0)
+  if (!ok0) c0 = NAN;
+  double mean1 = n > 0 ? tot / n : NAN;
+  double a0 = fabs(c0);
+  double sq = 0, ex = 0, rw = 0;
+  for (int c = 1 + threadIdx.x; c < n_cols; c += K9_THREADS) {
+    bool ok;
+    double v = design1_coef(y, ld, row_base, design_grp, design_w, p0, p1, c, ok);
+    if (ok) {
+      sq += (v - mean1) * (v - mean1);
+      double nul = v - c0;
+      if (nul > a0 || nul < -a0) ex += 1.0;
+      if (v > a0 || v < -a0) rw += 1.0;       // null NOT centred on the observed value (resampling != 'bootstrap')
+    }
+  }
+  double q = wg_sum(sq, red), e = wg_sum(ex, red), r = wg_sum(rw, red);
+  if (threadIdx.x == 0) {
+    st[0] = c0; st[1] = n > 0 ? sqrt(q / n) : NAN; st[2] = n; st[3] = e; st[4] = mean1 - c0;
+    st[5] = (lo == hi) ? 1.0 : 0.0; st[6] = r; st[7] = hi - lo;
+  }
+}
+
+// coefficient rows of selected single-plane design contrasts (for the host-side tail fits); NaN in the columns that are not valid
+__global__ __launch_bounds__(256) void k_contrast_design1_rows(const double *__restrict__ y, int64_t ld, int32_t num_boot, int32_t n_groups,
+                                                               const int32_t *__restrict__ test_row,
+                                                               const int32_t *__restrict__ test_design,
+                                                               const int32_t *__restrict__ design_ptr,
+                                                               const int32_t *__restrict__ design_grp,
+                                                               const double *__restrict__ design_w, double *__restrict__ out) {
+  int64_t t = blockIdx.x;
+  int d = test_design[t];
+  int p0 = design_ptr[d], p1 = design_ptr[d + 1];
+  int64_t row_base = (int64_t)test_row[t] * n_groups;
+  for (int c = threadIdx.x; c <= num_boot; c += 256) {
+    bool ok;
+    double v = design1_coef(y, ld, row_base, design_grp, design_w, p0, p1, c, ok);
+    out[t * ld + c] = (ok && p1 > p0) ? v : NAN;
+  }
+}
+
 extern "C" {
 
 int mm_contract_stats(const double *d_ym, const double *d_yv, int64_t ld, int32_t num_boot, int32_t n_groups,
@@ -664,6 +756,30 @@ int mm_contrast_design_rows(const double *d_ym, const double *d_yv, int64_t ld, 
   if (n_tests == 0) return MM_OK;
   hipLaunchKernelGGL(k_contrast_design_rows, dim3((unsigned)n_tests), dim3(256), 0, (hipStream_t)stream, d_ym, d_yv, ld, num_boot, n_groups,
                      d_test_gene, d_test_design, d_design_ptr, d_design_grp, d_design_w, which, d_out);
+  MM_LAUNCH_CHECK();
+  return MM_OK;
+}
+
+int mm_contrast_design1_stats(const double *d_y, int64_t ld, int32_t num_boot, int32_t n_groups, const int32_t *d_test_row,
+                              const int32_t *d_test_design, const int32_t *d_design_ptr, const int32_t *d_design_grp,
+                              const double *d_design_w, int64_t n_tests, double *d_stats, void *stream) {
+  MM_ARG(d_y && d_test_row && d_test_design && d_design_ptr && d_design_grp && d_design_w && d_stats);
+  MM_ARG(n_tests >= 0 && n_tests < 2147483647LL && n_groups > 0 && num_boot > 0 && ld >= (int64_t)num_boot + 1);
+  if (n_tests == 0) return MM_OK;
+  hipLaunchKernelGGL(k_contrast_design1_stats, dim3((unsigned)n_tests), dim3(K9_THREADS), 0, (hipStream_t)stream, d_y, ld, num_boot, n_groups,
+                     d_test_row, d_test_design, d_design_ptr, d_design_grp, d_design_w, d_stats);
+  MM_LAUNCH_CHECK();
+  return MM_OK;
+}
+
+int mm_contrast_design1_rows(const double *d_y, int64_t ld, int32_t num_boot, int32_t n_groups, const int32_t *d_test_row,
+                             const int32_t *d_test_design, const int32_t *d_design_ptr, const int32_t *d_design_grp,
+                             const double *d_design_w, int64_t n_tests, double *d_out, void *stream) {
+  MM_ARG(d_y && d_test_row && d_test_design && d_design_ptr && d_design_grp && d_design_w && d_out);
+  MM_ARG(n_tests >= 0 && n_tests < 2147483647LL && n_groups > 0 && num_boot > 0 && ld >= (int64_t)num_boot + 1);
+  if (n_tests == 0) return MM_OK;
+  hipLaunchKernelGGL(k_contrast_design1_rows, dim3((unsigned)n_tests), dim3(256), 0, (hipStream_t)stream, d_y, ld, num_boot, n_groups,
+                     d_test_row, d_test_design, d_design_ptr, d_design_grp, d_design_w, d_out);
   MM_LAUNCH_CHECK();
   return MM_OK;
 }

@@ -1216,3 +1216,41 @@ class Bootstrap2D:
         _lib.call("mm_contract_stats", P(self.yc), P(self.yc), self.ld, self.B, self.ng, P(d_tp), P(d_W), P(d_good), n_tests, 0, P(coef),
                   P(stats), _stream())
         return coef, host(stats)[:n_tests]
+
+    def contrast_design(self, test_pair, test_design, design_ptr, design_grp, design_w):
+        """Guide-vs-control contrasts on the correlation rows (mm_contrast_design1_stats): test t applies the sparse weight row
+        ``design_grp/design_w[design_ptr[d]:design_ptr[d + 1]]``, d = ``test_design[t]``, to the replicate rows of pair
+        ``test_pair[t]`` (device pair order, ``self.order``).  Returns (stats host [n_tests][8], ``rows(idx)`` giving the
+        coefficient rows of selected tests on demand)."""
+        torch = _torch()
+        test_pair = np.asarray(test_pair, dtype=np.int32)
+        test_design = np.asarray(test_design, dtype=np.int32)
+        design_ptr = np.asarray(design_ptr, dtype=np.int32)
+        design_grp = np.asarray(design_grp, dtype=np.int32)
+        design_w = np.asarray(design_w, dtype=np.float64)
+        n_tests, n_designs = len(test_pair), len(design_ptr) - 1
+        # the kernel trusts these indices: check them here
+        if len(test_design) != n_tests or n_designs < 0 or len(design_w) != len(design_grp):
+            raise ValueError("contrast_design: inconsistent table sizes")
+        if design_ptr[0] != 0 or design_ptr[-1] != len(design_grp) or (np.diff(design_ptr) < 0).any():
+            raise ValueError("contrast_design: design_ptr is not a CSR pointer over design_grp")
+        if len(design_grp) and (design_grp.min() < 0 or design_grp.max() >= self.ng):
+            raise ValueError("contrast_design: group index out of range")
+        if n_tests and (test_pair.min() < 0 or test_pair.max() >= self.n_pairs or test_design.min() < 0 or test_design.max() >= n_designs):
+            raise ValueError("contrast_design: test index out of range")
+        stats = empty((max(1, n_tests), 8), torch.float64)
+        d_ptr, d_grp = dev(design_ptr), dev(design_grp if len(design_grp) else np.zeros(1, np.int32))
+        d_w = dev(design_w if len(design_w) else np.zeros(1))
+        d_tp, d_td = dev(test_pair if n_tests else np.zeros(1, np.int32)), dev(test_design if n_tests else np.zeros(1, np.int32))
+        _lib.call("mm_contrast_design1_stats", P(self.yc), self.ld, self.B, self.ng, P(d_tp), P(d_td), P(d_ptr), P(d_grp), P(d_w), n_tests,
+                  P(stats), _stream())
+
+        def rows(idx):
+            idx = np.asarray(idx, dtype=np.int64)
+            out = empty((max(1, len(idx)), self.ld), torch.float64)
+            a, b = dev(test_pair[idx]), dev(test_design[idx])
+            _lib.call("mm_contrast_design1_rows", P(self.yc), self.ld, self.B, self.ng, P(a), P(b), P(d_ptr), P(d_grp), P(d_w), len(idx),
+                      P(out), _stream())
+            return host(out)[: len(idx)]
+
+        return host(stats)[:n_tests], rows

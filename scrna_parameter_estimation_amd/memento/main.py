@@ -1080,6 +1080,138 @@ def ht_2d_moments(adata, covariate, treatment, treatment_for_gene=None, inplace=
         return adata
 
 
+def ht_2d_vs_control(adata, control, num_boot=10000, num_cpus=1, fill_seed=0, max_rows=None, approx=False, resampling='bootstrap',
+                     *, treatment_col=None):
+    """Perturb-seq style batch test of differential COEXPRESSION: the correlation of every pair of ``compute_2d_moments`` in
+    every group against one shared ``control``, in one call.  ``control`` / ``treatment_col`` mean what they mean in
+    ``ht_1d_vs_control``: without ``treatment_col`` a group label (or index) every other group is tested against; with it the
+    groups are guide x stratum, ``control`` is a value of that column and every other label column is a covariate (the
+    per-guide regression of the reference's loop -- subset to {guide, control}, create_groups([is_guide, *others]),
+    compute_2d_moments, ht_2d_moments with intercept + main-effect dummies -- folded into weights by ``design.VsControlDesigns``).
+
+    Every (pair, group) is bootstrapped once (``Bootstrap2D``: the control's pair histograms and chains, the largest ones, are
+    not redone per guide) and the test statistic is taken per guide from the resident replicate correlations
+    (mm_contrast_design1_stats): ``coef[c] = corr[pair, guide][c] - corr[pair, control][c]``, or the design's weighted sum over
+    the guide's and the control's stratum groups.  The per-group correlation uses the global size factors and no mean-variance
+    fit, so ``corr_coef`` equals the per-guide loop's wherever both use the same groups.  Pairs are handled as in
+    ``ht_2d_moments`` (unordered duplicates share the first one's result, self pairs stay NaN, a (pair, group) with a NaN or
+    +-1 correlation is skipped) and the global ``np.random`` stream is consumed as there (three uniforms per live
+    (pair, group), pair-major, up front).  A test with no good guide or control group, or with no stratum holding both arms,
+    is NaN.
+
+    Returns a DataFrame (gene_1, gene_2, group, corr_coef, corr_se, corr_pval), pair-major, one row per (requested pair,
+    tested guide), and stores the arrays in ``uns['memento']['2d_ht_vs_control']``."""
+    m = adata.uns['memento']
+    st = m['_hip']
+    st.last_bootstrap2d = None                 # (free the previous call's replicate rows before this call allocates its own)
+    groups = m['groups']
+    ng = len(groups)
+    designs = None
+    if treatment_col is not None:
+        label_columns = list(m['label_columns'])
+        if treatment_col not in label_columns:
+            raise ValueError(f"treatment_col {treatment_col!r} is not one of the label columns {label_columns}")
+        k_trt = label_columns.index(treatment_col)
+        labels = [g.split(m['label_delimiter'])[1:] for g in groups]
+        Nc = np.array([m['group_cells'][g].shape[0] for g in groups], dtype=np.float64)
+        designs = _design.VsControlDesigns(labels, k_trt, str(control), Nc)     # raises ValueError for an absent control value
+        covariates = [c for c in label_columns if c != treatment_col]
+        tested = designs.guides
+    else:
+        ctrl = groups.index(control) if not isinstance(control, (int, np.integer)) else int(control)
+        if not 0 <= ctrl < ng:
+            raise ValueError(f"control index {control!r} is not one of the {ng} groups")
+        others = np.array([j for j in range(ng) if j != ctrl], dtype=np.int64)
+        tested = [groups[j] for j in others]
+        # design k = {(guide k, +1), (control, -1)}; the last design is empty (a guide or the control is not good -> NaN test)
+        plain_ptr = np.concatenate([2 * np.arange(len(others) + 1), [2 * len(others)]]).astype(np.int32)
+        plain_grp = np.column_stack([others, np.full(len(others), ctrl)]).reshape(-1).astype(np.int32)
+        plain_w = np.tile([1.0, -1.0], len(others))
+    n_t = len(tested)
+    gq = np.array([m['group_q'][g] for g in groups])
+    idx1, idx2 = m['2d_moments']['gene_idx_1'], m['2d_moments']['gene_idx_2']
+    n_conv = idx1.shape[0]
+    # unordered pairs, first appearance wins; self pairs skipped (as ht_2d_moments)
+    first, members = [], {}
+    for c in range(n_conv):
+        a, b = int(idx1[c]), int(idx2[c])
+        if a == b:
+            continue
+        key = frozenset((a, b))
+        if key in members:
+            members[key].append(c)
+            continue
+        members[key] = [c]
+        first.append(c)
+    first = np.asarray(first, dtype=np.int64)
+    P_ = len(first)
+    slot = {int(g): i for i, g in enumerate(st.cols_local)}
+    c1 = np.array([slot[int(idx1[c])] for c in first], dtype=np.int64)
+    c2 = np.array([slot[int(idx2[c])] for c in first], dtype=np.int64)
+    true_corr = np.stack([m['2d_moments'][g]['corr'][first] for g in groups], axis=1) if P_ else np.zeros((0, ng))   # [pair][group]
+    with np.errstate(invalid="ignore"):
+        skip = np.isnan(true_corr) | (np.abs(true_corr) == 1)                                  # hypothesis_test.py:325
+    live = ~skip.reshape(-1)
+    r1a, r1b, r0 = (np.zeros(P_ * ng) for _ in range(3))
+    u = np.random.random(3 * int(live.sum()))            # r = random(2) then r0 = random() per live (pair, group), in order
+    r1a[live], r1b[live], r0[live] = u[0::3], u[1::3], u[2::3]
+    out = {k: np.full((n_conv, n_t), np.nan) for k in ('corr_coef', 'corr_se', 'corr_asl')}
+    bs = None
+    # pairs are independent: chunks bound the replicate rows ([pair x group][B+1] fp64) and the histogram tables (as ht_2d_moments)
+    if max_rows is None:
+        max_rows = min(1 << 19, engine.auto_max_rows(num_boot + 1, arrays=1))
+    chunk = max(1, int(max_rows) // max(1, ng))
+    tab_bytes = engine.pair_table_bytes(st.maxx, st.cols.genes, c1, c2, ng, len(st.sf_table)) if P_ else np.zeros(0, dtype=np.int64)
+    budget = max(1 << 28, engine._torch().cuda.mem_get_info()[0] // 3)
+    bounds, acc = [0], 0
+    for k in range(P_):
+        if k - bounds[-1] >= chunk or (acc + int(tab_bytes[k]) > budget and k > bounds[-1]):
+            bounds.append(k)
+            acc = 0
+        acc += int(tab_bytes[k])
+    bounds.append(P_)
+    for lo, hi in zip(bounds[:-1], bounds[1:]):
+        if hi <= lo:
+            continue
+        n_ch = hi - lo
+        del bs                   # release the previous chunk's tables and replicate rows first: the caching allocator hands them back
+        bs = engine.Bootstrap2D(st.cols, c1[lo:hi], c2[lo:hi], st.maxx, st.sf_bin, st.sf_table, gq, num_boot)
+        so = bs.order                                     # device pair order (sorted by left column)
+        sl = slice(lo * ng, hi * ng)
+
+        def to_dev_order(a):
+            return a[sl].reshape(n_ch, ng)[so].reshape(-1)
+
+        bs.run(to_dev_order(skip.reshape(-1)), to_dev_order(r1a), to_dev_order(r1b), to_dev_order(r0),
+               to_dev_order(np.where(skip, np.nan, true_corr).reshape(-1)))
+        good = bs.active.reshape(n_ch, ng)                # device order
+        test_pair = np.repeat(np.arange(n_ch), n_t)       # pair-major: a pair's control rows stay in L2 for its consecutive guides
+        if designs is None:
+            both = good[:, others] & good[:, [ctrl]]
+            test_design = np.where(both, np.arange(n_t)[None, :], n_t).reshape(-1)
+            stt, rows = bs.contrast_design(test_pair, test_design, plain_ptr, plain_grp, plain_w)
+        else:
+            stt, rows = bs.contrast_design(test_pair, designs.tests(good), *designs.tables())
+        pvals = _asl.asl_from_stats(stt, approx, rows, num_cpus, resampling)
+        for k in range(n_ch):
+            c = int(first[lo + so[k]])
+            cc = members[frozenset((int(idx1[c]), int(idx2[c])))]
+            tt = slice(k * n_t, (k + 1) * n_t)
+            out['corr_coef'][cc], out['corr_se'][cc], out['corr_asl'][cc] = stt[tt, 0], stt[tt, 1], pvals[tt]
+    out = {k: v.reshape(-1) for k, v in out.items()}
+    st.last_bootstrap2d = bs
+    st.last_chunk2d = (bounds[-2], bounds[-1]) if P_ else (0, 0)                   # diagnostics / tests: pair range of the last chunk
+    if designs is None:
+        m['2d_ht_vs_control'] = dict(out, control=groups[ctrl], groups=tested)
+    else:
+        m['2d_ht_vs_control'] = dict(out, control=str(control), groups=tested, treatment_col=treatment_col, covariates=covariates)
+    pairs = list(m['2d_moments']['gene_pairs'])
+    df = pd.DataFrame({'gene_1': np.repeat([a for a, _ in pairs], n_t), 'gene_2': np.repeat([b for _, b in pairs], n_t),
+                       'group': np.tile(tested, n_conv)})
+    df['corr_coef'], df['corr_se'], df['corr_pval'] = out['corr_coef'], out['corr_se'], out['corr_asl']
+    return df
+
+
 # ----------------------------------------------------------------------------------------------
 # getters
 # ----------------------------------------------------------------------------------------------
