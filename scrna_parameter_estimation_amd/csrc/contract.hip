@@ -12,32 +12,110 @@
 
 #define K9_THREADS 256
 
-__device__ __forceinline__ double wg_sum(double x, double *red) {
-  for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off, 64);
+// workgroup reduction: xor butterfly inside each wave, then the wave results in ascending order starting from ``init``
+template <class Op>
+__device__ __forceinline__ double wg_reduce(double x, double *red, double init, Op op) {
+  for (int off = 32; off > 0; off >>= 1) x = op(x, __shfl_xor(x, off, 64));
   __syncthreads();
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = x;
   __syncthreads();
-  double t = 0.0;
-  for (int i = 0; i < K9_THREADS / 64; i++) t += red[i];
+  double t = init;
+  for (int i = 0; i < K9_THREADS / 64; i++) t = op(t, red[i]);
   return t;
+}
+__device__ __forceinline__ double wg_sum(double x, double *red) {
+  return wg_reduce(x, red, 0.0, [](double a, double b) { return a + b; });
 }
 __device__ __forceinline__ double wg_min(double x, double *red) {
-  for (int off = 32; off > 0; off >>= 1) x = fmin(x, __shfl_xor(x, off, 64));
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = x;
-  __syncthreads();
-  double t = red[0];
-  for (int i = 1; i < K9_THREADS / 64; i++) t = fmin(t, red[i]);
-  return t;
+  return wg_reduce(x, red, INFINITY, [](double a, double b) { return fmin(a, b); });
 }
 __device__ __forceinline__ double wg_max(double x, double *red) {
-  for (int off = 32; off > 0; off >>= 1) x = fmax(x, __shfl_xor(x, off, 64));
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = x;
-  __syncthreads();
-  double t = red[0];
-  for (int i = 1; i < K9_THREADS / 64; i++) t = fmax(t, red[i]);
-  return t;
+  return wg_reduce(x, red, -INFINITY, [](double a, double b) { return fmax(a, b); });
+}
+
+// ------------------------------------------------------------------------------------------------
+// THE TEST RECORD.  Every statistics kernel of this file writes, per test and response plane, the same 8 doubles
+//   [0] coef0      the observed coefficient (replicate column 0)
+//   [1] se         sqrt(mean squared deviation of coef[1:] about its mean) over the valid columns   (hypothesis_test.py:297-298)
+//   [2] n_valid    number of valid columns among 1..B
+//   [3] n_extreme  #{ |coef[c] - coef0| > |coef0| }   (_compute_asl, hypothesis_test.py:62-92)
+//   [4] mean(coef[1:]) - coef0
+//   [5] all_equal  1 when every valid coefficient, column 0 included, is the same number
+//   [6] n_raw_extreme  #{ |coef[c]| > |coef0| }: the null NOT centred on the observed value (resampling != 'bootstrap')
+//   [7] range      max - min over the valid columns, column 0 included
+// and the kernels differ only in how the coefficient of a column is obtained.
+__device__ __forceinline__ void write_nan_record(double *st) {   // a test with nothing to test
+  if (threadIdx.x == 0)
+    for (int i = 0; i < 8; i++) st[i] = (i == 2 || i == 3 || i == 5) ? 0.0 : NAN;
+}
+
+// Fill the records st[0..NP) of one test from ``coef_at(c, v)``: it puts the NP coefficients of replicate column c into v and
+// returns whether the column is valid (one verdict for all planes; v of column 0 is reported as coef0 either way).  Called
+// by all K9_THREADS threads of the workgroup.  Pass A: count / sum / min / max; pass B: squared deviations and the extreme
+// counts.  STORED = false: pass B calls coef_at again (nothing per-replicate is stored; row is unused).  STORED = true
+// (NP == 1): pass A stores the coefficient row in ``row``, which is also an output, and pass B reads it back; invalid
+// columns are NaN in it.
+template <int NP, bool STORED, class F>
+__device__ __forceinline__ void fill_records(F coef_at, int n_cols, double *row, double *const (&st)[NP], double *red) {
+  double v[NP], sum[NP], lo[NP], hi[NP], cnt = 0.0;
+  for (int k = 0; k < NP; k++) { sum[k] = 0.0; lo[k] = INFINITY; hi[k] = -INFINITY; }
+  for (int c = threadIdx.x; c < n_cols; c += K9_THREADS) {
+    bool ok = coef_at(c, v);
+    if (STORED) row[c] = v[0];
+    if (ok) {
+      for (int k = 0; k < NP; k++) { lo[k] = fmin(lo[k], v[k]); hi[k] = fmax(hi[k], v[k]); }
+      if (c > 0) {
+        for (int k = 0; k < NP; k++) sum[k] += v[k];
+        cnt += 1.0;
+      }
+    }
+  }
+  double n = wg_sum(cnt, red);
+  for (int k = 0; k < NP; k++) sum[k] = wg_sum(sum[k], red);
+  for (int k = 0; k < NP; k++) { lo[k] = wg_min(lo[k], red); hi[k] = wg_max(hi[k], red); }
+  double c0[NP], mean[NP], a0[NP], sq[NP], ext[NP], raw[NP];
+  if (STORED) {
+    __threadfence_block();
+    __syncthreads();
+    c0[0] = row[0];
+  } else {
+    coef_at(0, c0);
+  }
+  for (int k = 0; k < NP; k++) {
+    mean[k] = n > 0 ? sum[k] / n : NAN;
+    a0[k] = fabs(c0[k]);
+    sq[k] = ext[k] = raw[k] = 0.0;
+  }
+  for (int c = 1 + threadIdx.x; c < n_cols; c += K9_THREADS) {
+    bool ok;
+    if (STORED) { v[0] = row[c]; ok = v[0] == v[0]; }
+    else ok = coef_at(c, v);
+    if (ok) {
+      for (int k = 0; k < NP; k++) {
+        double d = v[k] - mean[k];
+        sq[k] += d * d;
+        double nul = v[k] - c0[k];
+        if (nul > a0[k] || nul < -a0[k]) ext[k] += 1.0;
+        if (v[k] > a0[k] || v[k] < -a0[k]) raw[k] += 1.0;
+      }
+    }
+  }
+  for (int k = 0; k < NP; k++) sq[k] = wg_sum(sq[k], red);
+  for (int k = 0; k < NP; k++) ext[k] = wg_sum(ext[k], red);
+  for (int k = 0; k < NP; k++) raw[k] = wg_sum(raw[k], red);
+  if (threadIdx.x == 0) {
+    for (int k = 0; k < NP; k++) {
+      double *s = st[k];
+      s[0] = c0[k];
+      s[1] = n > 0 ? sqrt(sq[k] / n) : NAN;
+      s[2] = n;
+      s[3] = ext[k];
+      s[4] = mean[k] - c0[k];
+      s[5] = (lo[k] == hi[k]) ? 1.0 : 0.0;
+      s[6] = raw[k];
+      s[7] = hi[k] - lo[k];
+    }
+  }
 }
 
 __global__ __launch_bounds__(K9_THREADS) void k_contract_stats(const double *__restrict__ ym, const double *__restrict__ yv, int64_t ld,
@@ -62,19 +140,15 @@ __global__ __launch_bounds__(K9_THREADS) void k_contract_stats(const double *__r
   __syncthreads();
   int n_good = n_good_s;
   double *crow = coef + t * ld;
-  double *st = stats + t * 8;
+  double *const st[1] = {stats + t * 8};
   int64_t row_base = (int64_t)gene * n_groups;
   int n_cols = num_boot + 1;
   if (n_good == 0) {
     for (int c = threadIdx.x; c < n_cols; c += K9_THREADS) crow[c] = NAN;
-    if (threadIdx.x == 0) {
-      st[0] = NAN; st[1] = NAN; st[2] = 0; st[3] = 0; st[4] = NAN; st[5] = 0; st[6] = NAN; st[7] = NAN;
-    }
+    write_nan_record(st[0]);
     return;
   }
-  // pass A: coefficients
-  double s_sum = 0.0, s_cnt = 0.0, s_min = INFINITY, s_max = -INFINITY;
-  for (int c = threadIdx.x; c < n_cols; c += K9_THREADS) {
+  auto coef_at = [&](int c, double(&v)[1]) {
     double acc = 0.0;
     bool ok = true;
     for (int q = 0; q < n_good; q++) {
@@ -84,51 +158,10 @@ __global__ __launch_bounds__(K9_THREADS) void k_contract_stats(const double *__r
       ok = ok && isfinite(a) && isfinite(b);
       acc += wrow[j] * (which ? b : a);
     }
-    double val = ok ? acc : NAN;
-    crow[c] = val;
-    if (ok) {
-      s_min = fmin(s_min, val);
-      s_max = fmax(s_max, val);
-      if (c > 0) {
-        s_sum += val;
-        s_cnt += 1.0;
-      }
-    }
-  }
-  double tot = wg_sum(s_sum, red);
-  double cnt = wg_sum(s_cnt, red);
-  double mn = wg_min(s_min, red);
-  double mx = wg_max(s_max, red);
-  __threadfence_block();
-  __syncthreads();
-  double c0 = crow[0];
-  double mean1 = cnt > 0 ? tot / cnt : NAN;
-  double a0 = fabs(c0);
-  // pass B: variance about the mean of coef[1:], extreme count of null = coef[1:] - coef[0]
-  double s_sq = 0.0, s_ext = 0.0, s_raw = 0.0;
-  for (int c = 1 + threadIdx.x; c < n_cols; c += K9_THREADS) {
-    double val = crow[c];
-    if (val == val) {  // dropped replicates are stored as NaN
-      double d = val - mean1;
-      s_sq += d * d;
-      double nul = val - c0;
-      if (nul > a0 || nul < -a0) s_ext += 1.0;
-      if (val > a0 || val < -a0) s_raw += 1.0;   // null NOT centred on the observed value (resampling != 'bootstrap')
-    }
-  }
-  double sq = wg_sum(s_sq, red);
-  double ext = wg_sum(s_ext, red);
-  double raw = wg_sum(s_raw, red);
-  if (threadIdx.x == 0) {
-    st[0] = c0;
-    st[1] = cnt > 0 ? sqrt(sq / cnt) : NAN;
-    st[2] = cnt;
-    st[3] = ext;
-    st[4] = mean1 - c0;
-    st[5] = (mn == mx) ? 1.0 : 0.0;
-    st[6] = raw;
-    st[7] = mx - mn;
-  }
+    v[0] = ok ? acc : NAN;   // dropped replicates are stored as NaN
+    return ok;
+  };
+  fill_records<1, true>(coef_at, n_cols, crow, st, red);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -223,8 +256,8 @@ __device__ __forceinline__ uint64_t rr_mix(uint64_t x) {
 // Step 2: per test and resampled column c < nb (nb = surviving columns - 1, hypothesis_test.py:249-254): rows i = 0..n-1 take
 // group rep[i][c] and the bcol[i][c]-th SURVIVING replicate column of the residualised response; coefficient = weighted slope
 // on the residualised treatment of the drawn groups (_cross_coef_resampled).  rep/bcol NULL -> drawn on the fly from a
-// counter-based RNG (column 0 is always the identity / observed column).  rep/bcol rows have stride num_boot.  Then the same
-// null statistics as k_contract_stats.
+// counter-based RNG (column 0 is always the identity / observed column).  rep/bcol rows have stride num_boot.  Then the
+// test record, read back from the stored row as in k_contract_stats.
 __global__ __launch_bounds__(K9_THREADS) void k_cross_resampled(const double *__restrict__ yt, int64_t ld, int32_t num_boot,
                                                                 int32_t n_groups, const int32_t *__restrict__ test_gene,
                                                                 const double *__restrict__ tt /* [n_tests][ng] residualised treatment */,
@@ -254,13 +287,11 @@ __global__ __launch_bounds__(K9_THREADS) void k_cross_resampled(const double *__
   __syncthreads();
   int n = n_good_s;
   double *crow = coef + t * ld;
-  double *st = stats + t * 8;
+  double *const st[1] = {stats + t * 8};
   int64_t row_base = (int64_t)gene * n_groups;
   if (n == 0) {
     for (int c = threadIdx.x; c <= num_boot; c += K9_THREADS) crow[c] = NAN;
-    if (threadIdx.x == 0) {
-      st[0] = NAN; st[1] = NAN; st[2] = 0; st[3] = 0; st[4] = NAN; st[5] = 0; st[6] = NAN; st[7] = NAN;
-    }
+    write_nan_record(st[0]);
     return;
   }
   const int16_t *rg = rep ? rep + (int64_t)gene * n_groups * num_boot : nullptr;
@@ -270,13 +301,11 @@ __global__ __launch_bounds__(K9_THREADS) void k_cross_resampled(const double *__
   const int nb = n_valid ? n_valid[gene] - 1 : num_boot;
   if (nb < 1) {    // nothing (or only one column) survives: the reference returns NaNs ("skipped") or has no null at all
     for (int c = threadIdx.x; c <= num_boot; c += K9_THREADS) crow[c] = NAN;
-    if (threadIdx.x == 0) {
-      st[0] = NAN; st[1] = NAN; st[2] = 0; st[3] = 0; st[4] = NAN; st[5] = 0; st[6] = NAN; st[7] = NAN;
-    }
+    write_nan_record(st[0]);
     return;
   }
-  double s_sum = 0.0, s_cnt = 0.0, s_min = INFINITY, s_max = -INFINITY;
-  for (int c = threadIdx.x; c < nb; c += K9_THREADS) {
+  for (int c = nb + threadIdx.x; c <= num_boot; c += K9_THREADS) crow[c] = NAN;  // the resampled row uses nb <= num_boot slots
+  auto coef_at = [&](int c, double(&v)[1]) {
     double sw = 0.0, swy = 0.0, swa = 0.0, amax = 0.0;
     // first pass: weighted means
     for (int i = 0; i < n; i++) {
@@ -320,50 +349,10 @@ __global__ __launch_bounds__(K9_THREADS) void k_cross_resampled(const double *__
     // and the isfinite filter of _compute_asl ignore.  With >= 12 groups such columns do not occur (P < 1e-3 per column).
     double val = num / sw / (ss / sw);
     if (ss / sw <= 1e-24 * amax * amax) val = NAN;
-    crow[c] = val;
-    if (val == val) {
-      s_min = fmin(s_min, val);
-      s_max = fmax(s_max, val);
-      if (c > 0) {
-        s_sum += val;
-        s_cnt += 1.0;
-      }
-    }
-  }
-  for (int c = nb + threadIdx.x; c <= num_boot; c += K9_THREADS) crow[c] = NAN;  // the resampled row uses nb <= num_boot slots
-  double tot = wg_sum(s_sum, red);
-  double cnt = wg_sum(s_cnt, red);
-  double mn = wg_min(s_min, red);
-  double mx = wg_max(s_max, red);
-  __threadfence_block();
-  __syncthreads();
-  double c0 = crow[0];
-  double mean1 = cnt > 0 ? tot / cnt : NAN;
-  double a0 = fabs(c0);
-  double s_sq = 0.0, s_ext = 0.0, s_raw = 0.0;
-  for (int c = 1 + threadIdx.x; c < nb; c += K9_THREADS) {
-    double val = crow[c];
-    if (val == val) {
-      double d = val - mean1;
-      s_sq += d * d;
-      double nul = val - c0;
-      if (nul > a0 || nul < -a0) s_ext += 1.0;
-      if (val > a0 || val < -a0) s_raw += 1.0;   // null NOT centred on the observed value (resampling != 'bootstrap')
-    }
-  }
-  double sq = wg_sum(s_sq, red);
-  double ext = wg_sum(s_ext, red);
-  double raw = wg_sum(s_raw, red);
-  if (threadIdx.x == 0) {
-    st[0] = c0;
-    st[1] = cnt > 0 ? sqrt(sq / cnt) : NAN;
-    st[2] = cnt;
-    st[3] = ext;
-    st[4] = mean1 - c0;
-    st[5] = (mn == mx) ? 1.0 : 0.0;
-    st[6] = raw;
-    st[7] = mx - mn;
-  }
+    v[0] = val;
+    return val == val;
+  };
+  fill_records<1, true>(coef_at, nb, crow, st, red);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -380,58 +369,22 @@ __global__ __launch_bounds__(K9_THREADS) void k_contrast_stats(const double *__r
   __shared__ double red[K9_THREADS / 64];
   int64_t t = blockIdx.x;
   int gene = test_gene[t], grp = test_grp[t];
-  double *sm_ = stats_m + t * 8, *sv_ = stats_v + t * 8;
+  double *const st[2] = {stats_m + t * 8, stats_v + t * 8};
   const uint8_t *gd = good + (int64_t)gene * n_groups;
   if (!gd[grp] || !gd[ctrl]) {
-    if (threadIdx.x == 0) {
-      for (int i = 0; i < 8; i++) {
-        sm_[i] = (i == 2 || i == 3 || i == 5) ? 0.0 : NAN;
-        sv_[i] = (i == 2 || i == 3 || i == 5) ? 0.0 : NAN;
-      }
-    }
+    write_nan_record(st[0]);
+    write_nan_record(st[1]);
     return;
   }
   const double *ma = ym + ((int64_t)gene * n_groups + grp) * ld, *mc = ym + ((int64_t)gene * n_groups + ctrl) * ld;
   const double *va = yv + ((int64_t)gene * n_groups + grp) * ld, *vc = yv + ((int64_t)gene * n_groups + ctrl) * ld;
-  int n_cols = num_boot + 1;
-  double sum_m = 0, sum_v = 0, cnt = 0, mn_m = INFINITY, mx_m = -INFINITY, mn_v = INFINITY, mx_v = -INFINITY;
-  for (int c = threadIdx.x; c < n_cols; c += K9_THREADS) {
+  auto coef_at = [&](int c, double(&v)[2]) {
     double a = ma[c], b = mc[c], p = va[c], q = vc[c];
-    if (isfinite(a) && isfinite(b) && isfinite(p) && isfinite(q)) {
-      double dm = a - b, dv = p - q;
-      mn_m = fmin(mn_m, dm); mx_m = fmax(mx_m, dm);
-      mn_v = fmin(mn_v, dv); mx_v = fmax(mx_v, dv);
-      if (c > 0) { sum_m += dm; sum_v += dv; cnt += 1.0; }
-    }
-  }
-  double n = wg_sum(cnt, red);
-  double tm = wg_sum(sum_m, red), tv = wg_sum(sum_v, red);
-  double lo_m = wg_min(mn_m, red), hi_m = wg_max(mx_m, red), lo_v = wg_min(mn_v, red), hi_v = wg_max(mx_v, red);
-  double c0m = ma[0] - mc[0], c0v = va[0] - vc[0];
-  double mean_m = n > 0 ? tm / n : NAN, mean_v = n > 0 ? tv / n : NAN;
-  double am = fabs(c0m), av = fabs(c0v);
-  double sq_m = 0, sq_v = 0, ex_m = 0, ex_v = 0, rw_m = 0, rw_v = 0;
-  for (int c = 1 + threadIdx.x; c < n_cols; c += K9_THREADS) {
-    double a = ma[c], b = mc[c], p = va[c], q = vc[c];
-    if (isfinite(a) && isfinite(b) && isfinite(p) && isfinite(q)) {
-      double dm = a - b, dv = p - q;
-      sq_m += (dm - mean_m) * (dm - mean_m);
-      sq_v += (dv - mean_v) * (dv - mean_v);
-      double nm = dm - c0m, nv = dv - c0v;
-      if (nm > am || nm < -am) ex_m += 1.0;
-      if (nv > av || nv < -av) ex_v += 1.0;
-      if (dm > am || dm < -am) rw_m += 1.0;
-      if (dv > av || dv < -av) rw_v += 1.0;
-    }
-  }
-  double qm = wg_sum(sq_m, red), qv = wg_sum(sq_v, red), em = wg_sum(ex_m, red), ev = wg_sum(ex_v, red);
-  double rm = wg_sum(rw_m, red), rv = wg_sum(rw_v, red);
-  if (threadIdx.x == 0) {
-    sm_[0] = c0m; sm_[1] = n > 0 ? sqrt(qm / n) : NAN; sm_[2] = n; sm_[3] = em; sm_[4] = mean_m - c0m;
-    sm_[5] = (lo_m == hi_m) ? 1.0 : 0.0; sm_[6] = rm; sm_[7] = hi_m - lo_m;
-    sv_[0] = c0v; sv_[1] = n > 0 ? sqrt(qv / n) : NAN; sv_[2] = n; sv_[3] = ev; sv_[4] = mean_v - c0v;
-    sv_[5] = (lo_v == hi_v) ? 1.0 : 0.0; sv_[6] = rv; sv_[7] = hi_v - lo_v;
-  }
+    v[0] = a - b;
+    v[1] = p - q;
+    return isfinite(a) && isfinite(b) && isfinite(p) && isfinite(q);
+  };
+  fill_records<2, false>(coef_at, num_boot + 1, nullptr, st, red);
 }
 
 // coefficient rows of selected contrasts (for the host-side tail fits of the few tests that need them)
@@ -457,21 +410,27 @@ __global__ __launch_bounds__(256) void k_contrast_rows(const double *__restrict_
 // test_gene[t]:  coef_c = sum_p design_w[p] * y[gene, design_grp[p]][c]  for p in [design_ptr[d], design_ptr[d + 1]).
 // Column c is valid only if the mean AND the variability rows of every listed group are finite there (:249-251; groups with
 // a ~0 weight included).  An empty design (no good guide or control group, or no stratum holding both arms) gives the NaN
-// record of k_contrast_stats.  One workgroup per test; the coefficient is recomputed in the second pass instead of being
+// record.  One workgroup per test; the coefficient is recomputed in the second pass instead of being
 // stored (a test reads 2 x |groups| rows; the control rows are shared by the gene's consecutive tests through L2 / MALL).
-__device__ __forceinline__ void design_coef(const double *__restrict__ ym, const double *__restrict__ yv, int64_t ld, int64_t row_base,
-                                            const int32_t *__restrict__ grp, const double *__restrict__ w, int p0, int p1, int c,
-                                            double &cm, double &cv, bool &ok) {
-  double am = 0.0, av = 0.0;
+// design_coef<NP>: the coefficient of column c on NP response planes at once (each operand offset and weight read once);
+// returns whether the column is valid and leaves NaN in v where it is not.
+template <int NP>
+__device__ __forceinline__ bool design_coef(const double *const (&y)[NP], int64_t ld, int64_t row_base, const int32_t *__restrict__ grp,
+                                            const double *__restrict__ w, int p0, int p1, int c, double (&v)[NP]) {
   bool good = true;
+  for (int k = 0; k < NP; k++) v[k] = 0.0;
   for (int p = p0; p < p1; p++) {
     int64_t o = (row_base + grp[p]) * ld + c;
-    double a = ym[o], v = yv[o], wp = w[p];
-    good = good && isfinite(a) && isfinite(v);
-    am += wp * a;
-    av += wp * v;
+    double wp = w[p];
+    for (int k = 0; k < NP; k++) {
+      double a = y[k][o];
+      good = good && isfinite(a);
+      v[k] += wp * a;
+    }
   }
-  cm = am; cv = av; ok = good;
+  if (!good)
+    for (int k = 0; k < NP; k++) v[k] = NAN;
+  return good;
 }
 
 __global__ __launch_bounds__(K9_THREADS) void k_contrast_design_stats(const double *__restrict__ ym, const double *__restrict__ yv,
@@ -486,61 +445,16 @@ __global__ __launch_bounds__(K9_THREADS) void k_contrast_design_stats(const doub
   int64_t t = blockIdx.x;
   int gene = test_gene[t], d = test_design[t];
   int p0 = design_ptr[d], p1 = design_ptr[d + 1];
-  double *sm_ = stats_m + t * 8, *sv_ = stats_v + t * 8;
+  double *const st[2] = {stats_m + t * 8, stats_v + t * 8};
   if (p1 <= p0) {
-    if (threadIdx.x == 0) {
-      for (int i = 0; i < 8; i++) {
-        sm_[i] = (i == 2 || i == 3 || i == 5) ? 0.0 : NAN;
-        sv_[i] = (i == 2 || i == 3 || i == 5) ? 0.0 : NAN;
-      }
-    }
+    write_nan_record(st[0]);
+    write_nan_record(st[1]);
     return;
   }
+  const double *const y[2] = {ym, yv};
   int64_t row_base = (int64_t)gene * n_groups;
-  int n_cols = num_boot + 1;
-  double sum_m = 0, sum_v = 0, cnt = 0, mn_m = INFINITY, mx_m = -INFINITY, mn_v = INFINITY, mx_v = -INFINITY;
-  for (int c = threadIdx.x; c < n_cols; c += K9_THREADS) {
-    double dm, dv;
-    bool ok;
-    design_coef(ym, yv, ld, row_base, design_grp, design_w, p0, p1, c, dm, dv, ok);
-    if (ok) {
-      mn_m = fmin(mn_m, dm); mx_m = fmax(mx_m, dm);
-      mn_v = fmin(mn_v, dv); mx_v = fmax(mx_v, dv);
-      if (c > 0) { sum_m += dm; sum_v += dv; cnt += 1.0; }
-    }
-  }
-  double n = wg_sum(cnt, red);
-  double tm = wg_sum(sum_m, red), tv = wg_sum(sum_v, red);
-  double lo_m = wg_min(mn_m, red), hi_m = wg_max(mx_m, red), lo_v = wg_min(mn_v, red), hi_v = wg_max(mx_v, red);
-  double c0m, c0v;
-  bool ok0;
-  design_coef(ym, yv, ld, row_base, design_grp, design_w, p0, p1, 0, c0m, c0v, ok0);   // the observed coefficient (column 0)
-  if (!ok0) { c0m = NAN; c0v = NAN; }
-  double mean_m = n > 0 ? tm / n : NAN, mean_v = n > 0 ? tv / n : NAN;
-  double am = fabs(c0m), av = fabs(c0v);
-  double sq_m = 0, sq_v = 0, ex_m = 0, ex_v = 0, rw_m = 0, rw_v = 0;
-  for (int c = 1 + threadIdx.x; c < n_cols; c += K9_THREADS) {
-    double dm, dv;
-    bool ok;
-    design_coef(ym, yv, ld, row_base, design_grp, design_w, p0, p1, c, dm, dv, ok);
-    if (ok) {
-      sq_m += (dm - mean_m) * (dm - mean_m);
-      sq_v += (dv - mean_v) * (dv - mean_v);
-      double nm = dm - c0m, nv = dv - c0v;
-      if (nm > am || nm < -am) ex_m += 1.0;
-      if (nv > av || nv < -av) ex_v += 1.0;
-      if (dm > am || dm < -am) rw_m += 1.0;
-      if (dv > av || dv < -av) rw_v += 1.0;
-    }
-  }
-  double qm = wg_sum(sq_m, red), qv = wg_sum(sq_v, red), em = wg_sum(ex_m, red), ev = wg_sum(ex_v, red);
-  double rm = wg_sum(rw_m, red), rv = wg_sum(rw_v, red);
-  if (threadIdx.x == 0) {
-    sm_[0] = c0m; sm_[1] = n > 0 ? sqrt(qm / n) : NAN; sm_[2] = n; sm_[3] = em; sm_[4] = mean_m - c0m;
-    sm_[5] = (lo_m == hi_m) ? 1.0 : 0.0; sm_[6] = rm; sm_[7] = hi_m - lo_m;
-    sv_[0] = c0v; sv_[1] = n > 0 ? sqrt(qv / n) : NAN; sv_[2] = n; sv_[3] = ev; sv_[4] = mean_v - c0v;
-    sv_[5] = (lo_v == hi_v) ? 1.0 : 0.0; sv_[6] = rv; sv_[7] = hi_v - lo_v;
-  }
+  auto coef_at = [&](int c, double(&v)[2]) { return design_coef<2>(y, ld, row_base, design_grp, design_w, p0, p1, c, v); };
+  fill_records<2, false>(coef_at, num_boot + 1, nullptr, st, red);
 }
 
 // coefficient rows of selected design contrasts (for the host-side tail fits); NaN in the columns that are not valid
@@ -555,11 +469,11 @@ __global__ __launch_bounds__(256) void k_contrast_design_rows(const double *__re
   int gene = test_gene[t], d = test_design[t];
   int p0 = design_ptr[d], p1 = design_ptr[d + 1];
   int64_t row_base = (int64_t)gene * n_groups;
+  const double *const y[2] = {ym, yv};
   for (int c = threadIdx.x; c <= num_boot; c += 256) {
-    double dm, dv;
-    bool ok;
-    design_coef(ym, yv, ld, row_base, design_grp, design_w, p0, p1, c, dm, dv, ok);
-    out[t * ld + c] = (ok && p1 > p0) ? (which ? dv : dm) : NAN;
+    double v[2];
+    bool ok = design_coef<2>(y, ld, row_base, design_grp, design_w, p0, p1, c, v);
+    out[t * ld + c] = (ok && p1 > p0) ? (which ? v[1] : v[0]) : NAN;
   }
 }
 
@@ -572,19 +486,6 @@ __global__ __launch_bounds__(256) void k_contrast_design_rows(const double *__re
 // through k_contrast_design_stats as both ym and yv this reads every byte once, tests it once and writes one record.
 // Two passes that recompute the coefficient (nothing per-replicate is stored): a test reads 2 x |design| rows, and the
 // control rows of a pair are shared by its consecutive tests through L2 / MALL (tests are issued pair-major).
-__device__ __forceinline__ double design1_coef(const double *__restrict__ y, int64_t ld, int64_t row_base, const int32_t *__restrict__ grp,
-                                               const double *__restrict__ w, int p0, int p1, int c, bool &ok) {
-  double acc = 0.0;
-  bool good = true;
-  for (int p = p0; p < p1; p++) {
-    double a = y[(row_base + grp[p]) * ld + c];
-    good = good && isfinite(a);
-    acc += w[p] * a;
-  }
-  ok = good;
-  return acc;
-}
-
 __global__ __launch_bounds__(K9_THREADS) void k_contrast_design1_stats(const double *__restrict__ y, int64_t ld, int32_t num_boot,
                                                                        int32_t n_groups, const int32_t *__restrict__ test_row,
                                                                        const int32_t *__restrict__ test_design,
@@ -595,46 +496,15 @@ __global__ __launch_bounds__(K9_THREADS) void k_contrast_design1_stats(const dou
   int64_t t = blockIdx.x;
   int d = test_design[t];
   int p0 = design_ptr[d], p1 = design_ptr[d + 1];
-  double *st = stats + t * 8;
+  double *const st[1] = {stats + t * 8};
   if (p1 <= p0) {
-    if (threadIdx.x == 0)
-      for (int i = 0; i < 8; i++) st[i] = (i == 2 || i == 3 || i == 5) ? 0.0 : NAN;
+    write_nan_record(st[0]);
     return;
   }
+  const double *const yp[1] = {y};
   int64_t row_base = (int64_t)test_row[t] * n_groups;
-  int n_cols = num_boot + 1;
-  double sum = 0, cnt = 0, mn = INFINITY, mx = -INFINITY;
-  for (int c = threadIdx.x; c < n_cols; c += K9_THREADS) {
-    bool ok;
-    double v = design1_coef(y, ld, row_base, design_grp, design_w, p0, p1, c, ok);
-    if (ok) {
-      mn = fmin(mn, v); mx = fmax(mx, v);
-      if (c > 0) { sum += v; cnt += 1.0; }
-    }
-  }
-  double n = wg_sum(cnt, red), tot = wg_sum(sum, red);
-  double lo = wg_min(mn, red), hi = wg_max(mx, red);
-  bool ok0;
-  double c0 = design1_coef(y, ld, row_base, design_grp, design_w, p0, p1, 0, ok0);   // the observed coefficient (column 0)
-  if (!ok0) c0 = NAN;
-  double mean1 = n > 0 ? tot / n : NAN;
-  double a0 = fabs(c0);
-  double sq = 0, ex = 0, rw = 0;
-  for (int c = 1 + threadIdx.x; c < n_cols; c += K9_THREADS) {
-    bool ok;
-    double v = design1_coef(y, ld, row_base, design_grp, design_w, p0, p1, c, ok);
-    if (ok) {
-      sq += (v - mean1) * (v - mean1);
-      double nul = v - c0;
-      if (nul > a0 || nul < -a0) ex += 1.0;
-      if (v > a0 || v < -a0) rw += 1.0;       // null NOT centred on the observed value (resampling != 'bootstrap')
-    }
-  }
-  double q = wg_sum(sq, red), e = wg_sum(ex, red), r = wg_sum(rw, red);
-  if (threadIdx.x == 0) {
-    st[0] = c0; st[1] = n > 0 ? sqrt(q / n) : NAN; st[2] = n; st[3] = e; st[4] = mean1 - c0;
-    st[5] = (lo == hi) ? 1.0 : 0.0; st[6] = r; st[7] = hi - lo;
-  }
+  auto coef_at = [&](int c, double(&v)[1]) { return design_coef<1>(yp, ld, row_base, design_grp, design_w, p0, p1, c, v); };
+  fill_records<1, false>(coef_at, num_boot + 1, nullptr, st, red);
 }
 
 // coefficient rows of selected single-plane design contrasts (for the host-side tail fits); NaN in the columns that are not valid
@@ -648,10 +518,11 @@ __global__ __launch_bounds__(256) void k_contrast_design1_rows(const double *__r
   int d = test_design[t];
   int p0 = design_ptr[d], p1 = design_ptr[d + 1];
   int64_t row_base = (int64_t)test_row[t] * n_groups;
+  const double *const yp[1] = {y};
   for (int c = threadIdx.x; c <= num_boot; c += 256) {
-    bool ok;
-    double v = design1_coef(y, ld, row_base, design_grp, design_w, p0, p1, c, ok);
-    out[t * ld + c] = (ok && p1 > p0) ? v : NAN;
+    double v[1];
+    bool ok = design_coef<1>(yp, ld, row_base, design_grp, design_w, p0, p1, c, v);
+    out[t * ld + c] = (ok && p1 > p0) ? v[0] : NAN;
   }
 }
 

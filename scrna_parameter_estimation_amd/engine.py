@@ -873,7 +873,6 @@ class Bootstrap1D:
                   int(which), P(coef), P(stats), _stream())
         return coef, host(stats)[:n_tests]
 
-
     def contrast(self, test_gene, test_grp, ctrl, good):
         """Two-group contrasts against the control group ``ctrl`` (mm_contrast_stats): returns (stats_mean, stats_var)
         host arrays [n_tests][8]; ``rows(which, idx)`` gives the coefficient rows of selected tests on demand."""
@@ -901,35 +900,19 @@ class Bootstrap1D:
         ``design_grp/design_w[design_ptr[d]:design_ptr[d + 1]]``, d = ``test_design[t]``, to the replicate rows of gene
         ``test_gene[t]``.  Returns (stats_mean, stats_var) host arrays [n_tests][8] and ``rows(which, idx)``, as ``contrast``."""
         torch = _torch()
-        test_gene = np.asarray(test_gene, dtype=np.int32)
-        test_design = np.asarray(test_design, dtype=np.int32)
-        design_ptr = np.asarray(design_ptr, dtype=np.int32)
-        design_grp = np.asarray(design_grp, dtype=np.int32)
-        design_w = np.asarray(design_w, dtype=np.float64)
-        n_tests, n_designs = len(test_gene), len(design_ptr) - 1
-        # the kernel trusts these indices: check them here
-        if len(test_design) != n_tests or n_designs < 0 or len(design_w) != len(design_grp):
-            raise ValueError("contrast_design: inconsistent table sizes")
-        if n_designs >= 0 and len(design_ptr) and (design_ptr[0] != 0 or design_ptr[-1] != len(design_grp) or (np.diff(design_ptr) < 0).any()):
-            raise ValueError("contrast_design: design_ptr is not a CSR pointer over design_grp")
-        if len(design_grp) and (design_grp.min() < 0 or design_grp.max() >= self.ng):
-            raise ValueError("contrast_design: group index out of range")
-        if n_tests and (test_gene.min() < 0 or test_gene.max() >= self.n_tested or test_design.min() < 0 or test_design.max() >= n_designs):
-            raise ValueError("contrast_design: test index out of range")
+        test_gene, test_design, d_tab = _design_tables(test_gene, test_design, design_ptr, design_grp, design_w, self.n_tested, self.ng)
+        n_tests = len(test_gene)
         st_m = empty((max(1, n_tests), 8), torch.float64)
         st_v = empty((max(1, n_tests), 8), torch.float64)
-        d_ptr, d_grp = dev(design_ptr), dev(design_grp if len(design_grp) else np.zeros(1, np.int32))
-        d_w = dev(design_w if len(design_w) else np.zeros(1))
-        d_tg, d_td = dev(test_gene), dev(test_design)
-        _lib.call("mm_contrast_design_stats", P(self.ym), P(self.yv), self.ld, self.B, self.ng, P(d_tg), P(d_td), P(d_ptr), P(d_grp), P(d_w),
-                  n_tests, P(st_m), P(st_v), _stream())
+        _lib.call("mm_contrast_design_stats", P(self.ym), P(self.yv), self.ld, self.B, self.ng, *map(P, d_tab), n_tests, P(st_m), P(st_v),
+                  _stream())
 
         def rows(which, idx):
             idx = np.asarray(idx, dtype=np.int64)
             out = empty((max(1, len(idx)), self.ld), torch.float64)
             a, b = dev(test_gene[idx]), dev(test_design[idx])
-            _lib.call("mm_contrast_design_rows", P(self.ym), P(self.yv), self.ld, self.B, self.ng, P(a), P(b), P(d_ptr), P(d_grp), P(d_w),
-                      len(idx), int(which), P(out), _stream())
+            _lib.call("mm_contrast_design_rows", P(self.ym), P(self.yv), self.ld, self.B, self.ng, P(a), P(b), *map(P, d_tab[2:]), len(idx),
+                      int(which), P(out), _stream())
             return host(out)[: len(idx)]
 
         return host(st_m)[:n_tests], host(st_v)[:n_tests], rows
@@ -945,6 +928,33 @@ class Bootstrap1D:
         device.  ``col_map``/``n_valid`` (from ``valid_cols``): surviving replicate columns, None = all of them."""
         return _contract_resampled(self.yv if which else self.ym, self.ld, self.B, self.ng, self.n_tested, test_gene, tt, good, gene_mask,
                                    M, Nc, rep, bcol, seed, col_map, n_valid)
+
+
+def _design_tables(test_row, test_design, design_ptr, design_grp, design_w, n_rows, ng):
+    """The tables of the design-contrast kernels (``contrast_design`` of Bootstrap1D / Bootstrap2D): test t applies design
+    ``test_design[t]`` -- the CSR row ``design_grp/design_w[design_ptr[d]:design_ptr[d + 1]]`` over the ``ng`` groups -- to
+    row block ``test_row[t]`` < ``n_rows`` (a gene slot or a pair).  Coerces and checks them (the kernels trust these indices)
+    and uploads them, empty arrays padded to one element.  Returns test_row and test_design as int32 host arrays and the
+    device tensors (test_row, test_design, design_ptr, design_grp, design_w), the order in which the kernels take them."""
+    test_row = np.asarray(test_row, dtype=np.int32)
+    test_design = np.asarray(test_design, dtype=np.int32)
+    design_ptr = np.asarray(design_ptr, dtype=np.int32)
+    design_grp = np.asarray(design_grp, dtype=np.int32)
+    design_w = np.asarray(design_w, dtype=np.float64)
+    n_tests, n_designs = len(test_row), len(design_ptr) - 1
+    if len(test_design) != n_tests or n_designs < 0 or len(design_w) != len(design_grp):
+        raise ValueError("contrast_design: inconsistent table sizes")
+    if design_ptr[0] != 0 or design_ptr[-1] != len(design_grp) or (np.diff(design_ptr) < 0).any():
+        raise ValueError("contrast_design: design_ptr is not a CSR pointer over design_grp")
+    if len(design_grp) and (design_grp.min() < 0 or design_grp.max() >= ng):
+        raise ValueError("contrast_design: group index out of range")
+    if n_tests and (test_row.min() < 0 or test_row.max() >= n_rows or test_design.min() < 0 or test_design.max() >= n_designs):
+        raise ValueError("contrast_design: test index out of range")
+
+    def up(a):
+        return dev(a if len(a) else np.zeros(1, a.dtype))
+
+    return test_row, test_design, (up(test_row), up(test_design), dev(design_ptr), up(design_grp), up(design_w))
 
 
 def _valid_cols(ym, yv, ld, B, ng, good, n_genes):
@@ -1223,34 +1233,16 @@ class Bootstrap2D:
         ``test_pair[t]`` (device pair order, ``self.order``).  Returns (stats host [n_tests][8], ``rows(idx)`` giving the
         coefficient rows of selected tests on demand)."""
         torch = _torch()
-        test_pair = np.asarray(test_pair, dtype=np.int32)
-        test_design = np.asarray(test_design, dtype=np.int32)
-        design_ptr = np.asarray(design_ptr, dtype=np.int32)
-        design_grp = np.asarray(design_grp, dtype=np.int32)
-        design_w = np.asarray(design_w, dtype=np.float64)
-        n_tests, n_designs = len(test_pair), len(design_ptr) - 1
-        # the kernel trusts these indices: check them here
-        if len(test_design) != n_tests or n_designs < 0 or len(design_w) != len(design_grp):
-            raise ValueError("contrast_design: inconsistent table sizes")
-        if design_ptr[0] != 0 or design_ptr[-1] != len(design_grp) or (np.diff(design_ptr) < 0).any():
-            raise ValueError("contrast_design: design_ptr is not a CSR pointer over design_grp")
-        if len(design_grp) and (design_grp.min() < 0 or design_grp.max() >= self.ng):
-            raise ValueError("contrast_design: group index out of range")
-        if n_tests and (test_pair.min() < 0 or test_pair.max() >= self.n_pairs or test_design.min() < 0 or test_design.max() >= n_designs):
-            raise ValueError("contrast_design: test index out of range")
+        test_pair, test_design, d_tab = _design_tables(test_pair, test_design, design_ptr, design_grp, design_w, self.n_pairs, self.ng)
+        n_tests = len(test_pair)
         stats = empty((max(1, n_tests), 8), torch.float64)
-        d_ptr, d_grp = dev(design_ptr), dev(design_grp if len(design_grp) else np.zeros(1, np.int32))
-        d_w = dev(design_w if len(design_w) else np.zeros(1))
-        d_tp, d_td = dev(test_pair if n_tests else np.zeros(1, np.int32)), dev(test_design if n_tests else np.zeros(1, np.int32))
-        _lib.call("mm_contrast_design1_stats", P(self.yc), self.ld, self.B, self.ng, P(d_tp), P(d_td), P(d_ptr), P(d_grp), P(d_w), n_tests,
-                  P(stats), _stream())
+        _lib.call("mm_contrast_design1_stats", P(self.yc), self.ld, self.B, self.ng, *map(P, d_tab), n_tests, P(stats), _stream())
 
         def rows(idx):
             idx = np.asarray(idx, dtype=np.int64)
             out = empty((max(1, len(idx)), self.ld), torch.float64)
             a, b = dev(test_pair[idx]), dev(test_design[idx])
-            _lib.call("mm_contrast_design1_rows", P(self.yc), self.ld, self.B, self.ng, P(a), P(b), P(d_ptr), P(d_grp), P(d_w), len(idx),
-                      P(out), _stream())
+            _lib.call("mm_contrast_design1_rows", P(self.yc), self.ld, self.B, self.ng, P(a), P(b), *map(P, d_tab[2:]), len(idx), P(out), _stream())
             return host(out)[: len(idx)]
 
         return host(stats)[:n_tests], rows

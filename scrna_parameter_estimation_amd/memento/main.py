@@ -722,6 +722,31 @@ def ht_1d_moments(adata, covariate, treatment, treatment_for_gene=None, inplace=
         return adata
 
 
+def _vs_control_plan(m, control, treatment_col):
+    """What ``ht_1d_vs_control`` / ``ht_2d_vs_control`` test: (names of the tested groups or guides, the
+    ``VsControlDesigns`` or None, (control group index, the other groups' indices) or (None, None), the metadata that goes
+    into ``uns`` next to the result arrays).  Without ``treatment_col``, ``control`` is a group label or index and every other
+    group is tested against it; with it, ``control`` is a value of that label column and the designs carry the rest."""
+    groups = m['groups']
+    ng = len(groups)
+    if treatment_col is None:
+        ctrl = groups.index(control) if not isinstance(control, (int, np.integer)) else int(control)
+        if not 0 <= ctrl < ng:
+            raise ValueError(f"control index {control!r} is not one of the {ng} groups")
+        others = np.array([j for j in range(ng) if j != ctrl], dtype=np.int64)
+        tested = [groups[j] for j in others]
+        return tested, None, (ctrl, others), dict(control=groups[ctrl], groups=tested)
+    label_columns = list(m['label_columns'])
+    if treatment_col not in label_columns:
+        raise ValueError(f"treatment_col {treatment_col!r} is not one of the label columns {label_columns}")
+    labels = [g.split(m['label_delimiter'])[1:] for g in groups]
+    Nc = np.array([m['group_cells'][g].shape[0] for g in groups], dtype=np.float64)
+    designs = _design.VsControlDesigns(labels, label_columns.index(treatment_col), str(control), Nc)   # ValueError for an absent control value
+    covariates = [c for c in label_columns if c != treatment_col]
+    return designs.guides, designs, (None, None), dict(control=str(control), groups=designs.guides, treatment_col=treatment_col,
+                                                       covariates=covariates)
+
+
 def ht_1d_vs_control(adata, control, num_boot=10000, num_cpus=1, rng='replay', fill_seed=0, max_rows=None, approx=False,
                      resampling='bootstrap', *, treatment_col=None):
     """Perturb-seq style batch test: every group against one shared ``control`` group (a label of
@@ -749,21 +774,7 @@ def ht_1d_vs_control(adata, control, num_boot=10000, num_cpus=1, rng='replay', f
     st = m['_hip']
     groups = m['groups']
     ng = len(groups)
-    designs = None
-    if treatment_col is not None:
-        label_columns = list(m['label_columns'])
-        if treatment_col not in label_columns:
-            raise ValueError(f"treatment_col {treatment_col!r} is not one of the label columns {label_columns}")
-        k_trt = label_columns.index(treatment_col)
-        labels = [g.split(m['label_delimiter'])[1:] for g in groups]
-        Nc = np.array([m['group_cells'][g].shape[0] for g in groups], dtype=np.float64)
-        designs = _design.VsControlDesigns(labels, k_trt, str(control), Nc)     # raises ValueError for an absent control value
-        covariates = [c for c in label_columns if c != treatment_col]
-        tested = designs.guides
-    else:
-        ctrl = groups.index(control) if not isinstance(control, (int, np.integer)) else int(control)
-        others = [j for j in range(ng) if j != ctrl]
-        tested = [groups[j] for j in others]
+    tested, designs, (ctrl, others), meta = _vs_control_plan(m, control, treatment_col)
     mean_only = m['estimator_type'] == 'mean_only'
     names = _var_names(adata)
     gq = np.array([m['group_q'][g] for g in groups])
@@ -797,7 +808,7 @@ def ht_1d_vs_control(adata, control, num_boot=10000, num_cpus=1, rng='replay', f
         st.last_good = good                    # (diagnostics / tests: the good groups of the last gene chunk)
         test_gene = np.repeat(np.arange(G), len(tested))
         if designs is None:
-            test_grp = np.tile(np.asarray(others), G)
+            test_grp = np.tile(others, G)
             st_m, st_v, rows = bs.contrast(test_gene, test_grp, ctrl, good)
         else:
             test_design = designs.tests(good)
@@ -809,10 +820,7 @@ def ht_1d_vs_control(adata, control, num_boot=10000, num_cpus=1, rng='replay', f
             cols[tag + '_asl'].append(p)
     out = {k: (np.concatenate(v) if v else np.zeros(0)) for k, v in cols.items()}
     st.last_bootstrap, st.last_chunk = bs, ((g0, g1) if G_all else (0, 0))       # diagnostics / tests: the last gene chunk's replicate rows
-    if designs is None:
-        m['1d_ht_vs_control'] = dict(out, control=groups[ctrl], groups=tested)
-    else:
-        m['1d_ht_vs_control'] = dict(out, control=str(control), groups=tested, treatment_col=treatment_col, covariates=covariates)
+    m['1d_ht_vs_control'] = dict(out, **meta)
     df = pd.DataFrame({'gene': np.repeat(names, len(tested)), 'group': np.tile(tested, G_all)})
     df['de_coef'], df['de_se'], df['de_pval'] = out['mean_coef'], out['mean_se'], out['mean_asl']
     df['dv_coef'], df['dv_se'], df['dv_pval'] = out['var_coef'], out['var_se'], out['var_asl']
@@ -912,6 +920,48 @@ def get_corr_matrix(adata, group):
     return corr
 
 
+def _pair_plan(m, st, num_boot, max_rows):
+    """The pairs of ``compute_2d_moments`` as the 2D tests run them: ``first`` = convolution index of every distinct unordered
+    pair (first appearance wins, self pairs skipped; main.py:467-482), ``members[k]`` = all convolution indices that share
+    pair k's result, ``c1`` / ``c2`` = its column slots, ``true_corr`` [pair][group], ``skip`` (hypothesis_test.py:325) and the
+    chunk ``bounds``: pairs are independent, so they run in chunks of at most ``max_rows`` replicate rows
+    ([pair x group][B+1] fp64) AND at most a third of the free HBM in histogram tables."""
+    groups = m['groups']
+    ng = len(groups)
+    idx1, idx2 = m['2d_moments']['gene_idx_1'], m['2d_moments']['gene_idx_2']
+    first, members, seen = [], [], {}
+    for c in range(idx1.shape[0]):
+        a, b = int(idx1[c]), int(idx2[c])
+        if a == b:
+            continue
+        k = seen.setdefault(frozenset((a, b)), len(first))
+        if k == len(first):
+            first.append(c)
+            members.append([])
+        members[k].append(c)
+    first = np.asarray(first, dtype=np.int64)
+    P_ = len(first)
+    slot = {int(g): i for i, g in enumerate(st.cols_local)}
+    c1 = np.array([slot[int(idx1[c])] for c in first], dtype=np.int64)
+    c2 = np.array([slot[int(idx2[c])] for c in first], dtype=np.int64)
+    true_corr = np.stack([m['2d_moments'][g]['corr'][first] for g in groups], axis=1) if P_ else np.zeros((0, ng))   # [pair][group]
+    with np.errstate(invalid="ignore"):
+        skip = np.isnan(true_corr) | (np.abs(true_corr) == 1)
+    if max_rows is None:
+        max_rows = min(1 << 19, engine.auto_max_rows(num_boot + 1, arrays=1))   # also bounds the per-pair 2D tables
+    chunk = max(1, int(max_rows) // max(1, ng))
+    tab_bytes = engine.pair_table_bytes(st.maxx, st.cols.genes, c1, c2, ng, len(st.sf_table)) if P_ else np.zeros(0, dtype=np.int64)
+    budget = max(1 << 28, engine._torch().cuda.mem_get_info()[0] // 3)
+    bounds, acc = [0], 0
+    for k in range(P_):
+        if k - bounds[-1] >= chunk or (acc + int(tab_bytes[k]) > budget and k > bounds[-1]):
+            bounds.append(k)
+            acc = 0
+        acc += int(tab_bytes[k])
+    bounds.append(P_)
+    return first, members, c1, c2, true_corr, skip, bounds
+
+
 def ht_2d_moments(adata, covariate, treatment, treatment_for_gene=None, inplace=True, num_boot=10000, verbose=3, num_cpus=1,
                   max_rows=None, fill_seed=0, strict=False, **kwargs):
     """Bootstrap hypothesis test of correlation differences (reference: memento/main.py:418-520,
@@ -941,19 +991,7 @@ def ht_2d_moments(adata, covariate, treatment, treatment_for_gene=None, inplace=
     gq = np.array([m['group_q'][g] for g in groups])
     idx1, idx2 = m['2d_moments']['gene_idx_1'], m['2d_moments']['gene_idx_2']
     n_conv = idx1.shape[0]
-    # unordered pairs, first appearance wins; self pairs skipped (main.py:467-482)
-    first, members = [], {}
-    for c in range(n_conv):
-        a, b = int(idx1[c]), int(idx2[c])
-        if a == b:
-            continue
-        key = frozenset((a, b))
-        if key in members:
-            members[key].append(c)
-            continue
-        members[key] = [c]
-        first.append(c)
-    first = np.asarray(first, dtype=np.int64)
+    first, members, c1, c2, true_corr, skip, bounds = _pair_plan(m, st, num_boot, max_rows)
     P_ = len(first)
     tcol = np.zeros(P_, dtype=np.int64)                   # treatment column of every tested pair (column 0 without treatment_for_gene)
     if treatment_for_gene is not None:
@@ -963,12 +1001,6 @@ def ht_2d_moments(adata, covariate, treatment, treatment_for_gene=None, inplace=
             if len(cols) != 1:
                 raise ValueError("setting an array element with a sequence.")          # what main.py:507 does with more columns
             tcol[k] = trt_cols.index(cols[0])
-    slot = {int(g): i for i, g in enumerate(st.cols_local)}
-    c1 = np.array([slot[int(idx1[c])] for c in first], dtype=np.int64)
-    c2 = np.array([slot[int(idx2[c])] for c in first], dtype=np.int64)
-    true_corr = np.stack([m['2d_moments'][g]['corr'][first] for g in groups], axis=1) if P_ else np.zeros((0, ng))   # [pair][group]
-    with np.errstate(invalid="ignore"):
-        skip = np.isnan(true_corr) | (np.abs(true_corr) == 1)                                  # hypothesis_test.py:325
     live = ~skip.reshape(-1)
     r1a, r1b, r0 = (np.zeros(P_ * ng) for _ in range(3))
     replay_rr = resample_rep and strict                   # the choice draws interleave with the hash uniforms, pair by pair
@@ -977,20 +1009,6 @@ def ht_2d_moments(adata, covariate, treatment, treatment_for_gene=None, inplace=
         r1a[live], r1b[live], r0[live] = u[0::3], u[1::3], u[2::3]
     corr_coef, corr_se, corr_asl = (np.full(n_conv, np.nan) for _ in range(3))
     bs = None
-    # pairs are independent: process them in chunks so the replicate rows ([pair x group][B+1] fp64) stay bounded
-    if max_rows is None:
-        max_rows = min(1 << 19, engine.auto_max_rows(num_boot + 1, arrays=1))   # also bounds the per-pair 2D tables
-    chunk = max(1, int(max_rows) // max(1, ng))
-    # chunk boundaries: at most ``chunk`` pairs (replicate rows) AND at most a third of the free HBM in histogram tables
-    tab_bytes = engine.pair_table_bytes(st.maxx, st.cols.genes, c1, c2, ng, len(st.sf_table)) if P_ else np.zeros(0, dtype=np.int64)
-    budget = max(1 << 28, engine._torch().cuda.mem_get_info()[0] // 3)
-    bounds, acc = [0], 0
-    for k in range(P_):
-        if k - bounds[-1] >= chunk or (acc + int(tab_bytes[k]) > budget and k > bounds[-1]):
-            bounds.append(k)
-            acc = 0
-        acc += int(tab_bytes[k])
-    bounds.append(P_)
     for lo, hi in zip(bounds[:-1], bounds[1:]):
         if hi <= lo:
             continue
@@ -1066,10 +1084,8 @@ def ht_2d_moments(adata, covariate, treatment, treatment_for_gene=None, inplace=
                 coef[rr_idx] = coef_r[rr_idx]
         pvals = _asl.asl_from_stats(stt, approx, lambda idx: engine.host(coef[engine.dev(np.asarray(idx, dtype=np.int64))]), num_cpus, resampling)
         for k in range(n_ch):
-            c = int(first[lo + so[k]])
-            if not good[k].any():
-                continue
-            for cc in members[frozenset((int(idx1[c]), int(idx2[c])))]:
+            if good[k].any():
+                cc = members[lo + so[k]]
                 corr_coef[cc], corr_se[cc], corr_asl[cc] = stt[k, 0], stt[k, 1], pvals[k]
     m['2d_ht'] = {'treatment': treatment, 'covariate': covariate, 'corr_coef': corr_coef, 'corr_se': corr_se, 'corr_asl': corr_asl}
     if treatment_for_gene is not None:
@@ -1106,23 +1122,8 @@ def ht_2d_vs_control(adata, control, num_boot=10000, num_cpus=1, fill_seed=0, ma
     st.last_bootstrap2d = None                 # (free the previous call's replicate rows before this call allocates its own)
     groups = m['groups']
     ng = len(groups)
-    designs = None
-    if treatment_col is not None:
-        label_columns = list(m['label_columns'])
-        if treatment_col not in label_columns:
-            raise ValueError(f"treatment_col {treatment_col!r} is not one of the label columns {label_columns}")
-        k_trt = label_columns.index(treatment_col)
-        labels = [g.split(m['label_delimiter'])[1:] for g in groups]
-        Nc = np.array([m['group_cells'][g].shape[0] for g in groups], dtype=np.float64)
-        designs = _design.VsControlDesigns(labels, k_trt, str(control), Nc)     # raises ValueError for an absent control value
-        covariates = [c for c in label_columns if c != treatment_col]
-        tested = designs.guides
-    else:
-        ctrl = groups.index(control) if not isinstance(control, (int, np.integer)) else int(control)
-        if not 0 <= ctrl < ng:
-            raise ValueError(f"control index {control!r} is not one of the {ng} groups")
-        others = np.array([j for j in range(ng) if j != ctrl], dtype=np.int64)
-        tested = [groups[j] for j in others]
+    tested, designs, (ctrl, others), meta = _vs_control_plan(m, control, treatment_col)
+    if designs is None:
         # design k = {(guide k, +1), (control, -1)}; the last design is empty (a guide or the control is not good -> NaN test)
         plain_ptr = np.concatenate([2 * np.arange(len(others) + 1), [2 * len(others)]]).astype(np.int32)
         plain_grp = np.column_stack([others, np.full(len(others), ctrl)]).reshape(-1).astype(np.int32)
@@ -1131,45 +1132,14 @@ def ht_2d_vs_control(adata, control, num_boot=10000, num_cpus=1, fill_seed=0, ma
     gq = np.array([m['group_q'][g] for g in groups])
     idx1, idx2 = m['2d_moments']['gene_idx_1'], m['2d_moments']['gene_idx_2']
     n_conv = idx1.shape[0]
-    # unordered pairs, first appearance wins; self pairs skipped (as ht_2d_moments)
-    first, members = [], {}
-    for c in range(n_conv):
-        a, b = int(idx1[c]), int(idx2[c])
-        if a == b:
-            continue
-        key = frozenset((a, b))
-        if key in members:
-            members[key].append(c)
-            continue
-        members[key] = [c]
-        first.append(c)
-    first = np.asarray(first, dtype=np.int64)
+    first, members, c1, c2, true_corr, skip, bounds = _pair_plan(m, st, num_boot, max_rows)
     P_ = len(first)
-    slot = {int(g): i for i, g in enumerate(st.cols_local)}
-    c1 = np.array([slot[int(idx1[c])] for c in first], dtype=np.int64)
-    c2 = np.array([slot[int(idx2[c])] for c in first], dtype=np.int64)
-    true_corr = np.stack([m['2d_moments'][g]['corr'][first] for g in groups], axis=1) if P_ else np.zeros((0, ng))   # [pair][group]
-    with np.errstate(invalid="ignore"):
-        skip = np.isnan(true_corr) | (np.abs(true_corr) == 1)                                  # hypothesis_test.py:325
     live = ~skip.reshape(-1)
     r1a, r1b, r0 = (np.zeros(P_ * ng) for _ in range(3))
     u = np.random.random(3 * int(live.sum()))            # r = random(2) then r0 = random() per live (pair, group), in order
     r1a[live], r1b[live], r0[live] = u[0::3], u[1::3], u[2::3]
     out = {k: np.full((n_conv, n_t), np.nan) for k in ('corr_coef', 'corr_se', 'corr_asl')}
     bs = None
-    # pairs are independent: chunks bound the replicate rows ([pair x group][B+1] fp64) and the histogram tables (as ht_2d_moments)
-    if max_rows is None:
-        max_rows = min(1 << 19, engine.auto_max_rows(num_boot + 1, arrays=1))
-    chunk = max(1, int(max_rows) // max(1, ng))
-    tab_bytes = engine.pair_table_bytes(st.maxx, st.cols.genes, c1, c2, ng, len(st.sf_table)) if P_ else np.zeros(0, dtype=np.int64)
-    budget = max(1 << 28, engine._torch().cuda.mem_get_info()[0] // 3)
-    bounds, acc = [0], 0
-    for k in range(P_):
-        if k - bounds[-1] >= chunk or (acc + int(tab_bytes[k]) > budget and k > bounds[-1]):
-            bounds.append(k)
-            acc = 0
-        acc += int(tab_bytes[k])
-    bounds.append(P_)
     for lo, hi in zip(bounds[:-1], bounds[1:]):
         if hi <= lo:
             continue
@@ -1194,17 +1164,13 @@ def ht_2d_vs_control(adata, control, num_boot=10000, num_cpus=1, fill_seed=0, ma
             stt, rows = bs.contrast_design(test_pair, designs.tests(good), *designs.tables())
         pvals = _asl.asl_from_stats(stt, approx, rows, num_cpus, resampling)
         for k in range(n_ch):
-            c = int(first[lo + so[k]])
-            cc = members[frozenset((int(idx1[c]), int(idx2[c])))]
+            cc = members[lo + so[k]]
             tt = slice(k * n_t, (k + 1) * n_t)
             out['corr_coef'][cc], out['corr_se'][cc], out['corr_asl'][cc] = stt[tt, 0], stt[tt, 1], pvals[tt]
     out = {k: v.reshape(-1) for k, v in out.items()}
     st.last_bootstrap2d = bs
     st.last_chunk2d = (bounds[-2], bounds[-1]) if P_ else (0, 0)                   # diagnostics / tests: pair range of the last chunk
-    if designs is None:
-        m['2d_ht_vs_control'] = dict(out, control=groups[ctrl], groups=tested)
-    else:
-        m['2d_ht_vs_control'] = dict(out, control=str(control), groups=tested, treatment_col=treatment_col, covariates=covariates)
+    m['2d_ht_vs_control'] = dict(out, **meta)
     pairs = list(m['2d_moments']['gene_pairs'])
     df = pd.DataFrame({'gene_1': np.repeat([a for a, _ in pairs], n_t), 'gene_2': np.repeat([b for _, b in pairs], n_t),
                        'group': np.tile(tested, n_conv)})
