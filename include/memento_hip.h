@@ -191,13 +191,6 @@ int mm_debug_wave_clock(int64_t *d_buf);
  * arithmetic; 0 (default) uses the guarded fp32 evaluation of those loops (csrc/npy_rng.h: same integer draws, the guard sends
  * the ~0.1-0.5 % of draws that land near a decision threshold to the fp64 arithmetic).  Process-wide switch. */
 int mm_debug_replay_arith(int32_t exact);
-/* Measurement / test aid: on != 0 (default) lets every lane of mm_boot1d_replay produce its PCG64 uniforms AHEAD of their use, all
- * lanes together a fixed number of times per bin step, into a 16-slot ring in LDS (the draws read them back); 0 = every sampler
- * call site steps the generator for the lanes that draw there (rounds 1-2).  Same stream, same draws.  Process-wide switch. */
-int mm_debug_replay_ring(int32_t on);
-/* Timing experiments only -- WRONG results: rows > 0 makes every tile of mm_boot1d_replay read its operand rows modulo ``rows``
- * (a cache-resident region), which separates the kernel's arithmetic from its operand traffic.  0 (default) = off. */
-int mm_debug_replay_rows_mod(int64_t rows);
 
 /* ---- K6+K7: replay bootstrap -- numpy Generator(PCG64).multinomial draw-for-draw + replicate moments
  * replaces bootstrap._bootstrap_1d  memento/bootstrap.py:97-110 and the tuple branch of
@@ -229,11 +222,7 @@ int mm_boot1d_replay(const double *d_pk, const double *d_lq, const double *d_v, 
                      int64_t ld, double *d_out_mean, double *d_out_var, int32_t *d_w_dump, int32_t kmax_dump,
                      int64_t co_resident_waves /* waves of mm_boot1d_chain launched beside this call (0 = none): with n_tiles they
                                                   decide between the two- and the three-waves-per-SIMD build of the kernel */,
-                     const mm_chain_tiles *chains /* NULL = every tile is a tile */,
-                     const double *d_stream /* optional: the stream's uniforms from mm_pcg64_stream; every lane then reads its
-                                               uniforms from this table at its own position instead of stepping PCG64 */,
-                     int64_t stream_len, int32_t *d_stream_overflow /* set to 1 if a chain ran past the table: redo without it */,
-                     void *stream);
+                     const mm_chain_tiles *chains /* NULL = every tile is a tile */, void *stream);
 /* K6+K7, FREE-RUNNING tiles (memento/bootstrap.py:97-110, estimator.py:171-174; the launch the timed path uses): slot s = 64 * tile + lane
  * runs the chain whose 8-double operand records (mm_bins_order, MM_CHAIN_SLOT pairs) are [d_slot_rec[s], d_slot_rec[s] + d_slot_K[s]) of
  * d_recs; d_slot_rec[s] < 0 or d_slot_K[s] <= 0 = unused lane.  The lanes of a tile share the instruction stream only: a BTPE draw makes

@@ -13,6 +13,7 @@
 // fp64, contraction OFF (-ffp-contract=off): replicate means/variances are bit-identical to numpy's.
 #include "mm_common.h"
 #include "npy_rng.h"
+#include <type_traits>
 
 // Chains that run one per WAVE (below: chain_body, k_boot1d_chain).  The tile kernel takes them as well: a tile flagged in
 // ``tile_chain`` is such a chain, so that the host can put chain waves at chosen places of ONE launch's dispatch order.
@@ -27,86 +28,14 @@ struct ChainArgs {
   const int32_t *tile_chain;   // [tile] chain index or -1 (tile kernel only; may be NULL)
   int32_t *w_dump;             // optional weights [chain][k][b]
   int32_t kmax_dump;
-  int64_t debug_rows_mod;      // timing experiments only (mm_debug_replay_rows_mod): > 0 = tiles read operand rows modulo this (WRONG results)
 };
 template <bool FAST>
 __device__ __forceinline__ void chain_body(const ChainArgs &ca, int64_t ch, int lane, uint64_t st0, uint64_t st1, int32_t num_boot,
                                            int32_t mean_only, int64_t ld, double *__restrict__ out_mean, double *__restrict__ out_var,
                                            int64_t *__restrict__ wave_clock);
 
-// Every chain of a launch replays the SAME stream: the reference seeds PCG64(5) anew for every (gene, group) pair
-// (memento/bootstrap.py:102).  So the stream's uniforms can be produced ONCE (k_pcg64_stream: lane-parallel jump-ahead, a few
-// milliseconds for millions of outputs) and a chain's generator shrinks to its position in that table: one gather load per
-// uniform instead of a 128-bit multiply-add, an xor-shift-rotate and an integer -> double conversion per lane (~45 VALU
-// instructions, ten of them quarter-rate multiplies: about a quarter of the tile kernel's VALU time).  Same uniforms, same draws.
-namespace npyrng {
-struct TableRng {
-  const double *__restrict__ tab;
-  int64_t len, pos;
-  int32_t *overflow;                 // set when a chain runs past the table (the host then redoes the launch with the arithmetic generator)
-  typedef int64_t Mark;
-  __device__ __forceinline__ Mark mark() const { return pos; }
-  __device__ __forceinline__ void rewind(Mark m) { pos = m; }
-  __device__ __forceinline__ void reserve(int) {}
-  __device__ __forceinline__ int max_attempts() const { return 16; }
-};
-__device__ __forceinline__ double pcg64_next_double(TableRng &g) {
-  int64_t p = g.pos++;
-  if (p >= g.len) {
-    *g.overflow = 1;
-    p = g.len - 1;
-  }
-  return g.tab[p];
-}
-// RING generator: the lane's own PCG64 stream, produced AHEAD of its use into a 16-slot ring in LDS.  In the lock-step tile
-// kernel every sampler call site costs the whole wave a PCG64 step (~45 VALU instructions, a third of them quarter-rate
-// multiplies) however few lanes draw there: seven sites per bin step (one for the inversion sampler, two per BTPE attempt of the
-// unluckiest lane) for ~1.5 uniforms a lane actually uses.  With the ring ALL lanes step their generators together, a fixed
-// number of times per bin step (top_up), and a draw just reads its uniforms back (ds_read); a lane that runs dry mid-draw steps
-// its generator on the spot.  Same stream, same uniforms in the same order.  Rewinding (the exact redo of a guarded draw) moves
-// the read position back: the ring keeps the last 16 uniforms, so the fast BTPE may use 14 (7 attempts) before it must hand over.
-struct RingRng {
-  uint64_t s_hi, s_lo, i_hi, i_lo;   // generator state at stream position ``tail``
-  int32_t head, tail;                // uniforms consumed / produced so far (slot = position & 15)
-  double *ring;                      // this lane's column of the [16][256] LDS ring (stride 256 doubles)
-  typedef int32_t Mark;
-  __device__ __forceinline__ Mark mark() const { return head; }
-  __device__ __forceinline__ void rewind(Mark m) { head = m; }
-  __device__ __forceinline__ void reserve(int) {}
-  __device__ __forceinline__ int max_attempts() const { return 7; }
-  __device__ __forceinline__ double step() {
-    Pcg64 g{s_hi, s_lo, i_hi, i_lo};
-    double u = pcg64_next_double(g);
-    s_hi = g.s_hi;
-    s_lo = g.s_lo;
-    return u;
-  }
-  __device__ __forceinline__ void top_up(int rounds) {      // every lane with room produces ``rounds`` more uniforms (wave-uniform trip count)
-    for (int j = 0; j < rounds; j++) {
-      if (tail - head < 16) {
-        ring[(tail & 15) * 256] = step();
-        tail++;
-      }
-    }
-  }
-};
-__device__ __forceinline__ double pcg64_next_double(RingRng &g) {
-  double u;
-  if (g.head == g.tail) {            // ring empty: produce on the spot (and keep it, a rewind may come back to it)
-    u = g.step();
-    g.ring[(g.tail & 15) * 256] = u;
-    g.tail++;
-  } else {
-    u = g.ring[(g.head & 15) * 256];
-  }
-  g.head++;
-  return u;
-}
-template <int MODE> struct GenOf { typedef Pcg64 type; };     // MODE 0: arithmetic, 1: stream table, 2: ring
-template <> struct GenOf<1> { typedef TableRng type; };
-template <> struct GenOf<2> { typedef RingRng type; };
-}  // namespace npyrng
-
+// The uniforms of a stream as a table (engine.pcg64_stream_table; the tile kernel once read its uniforms from such a table:
+// measured slower, a wave's lanes sit at 64 different places of it).
 // out[i] = the (i + 1)-th uniform of the stream that starts at ``state`` (numpy: Generator(PCG64).random()): every thread jumps
 // to the start of its run of 64 outputs (PCG's O(log n) advance) and steps through it.
 __global__ __launch_bounds__(256) void k_pcg64_stream(double *__restrict__ out, int64_t n, uint64_t st0, uint64_t st1, uint64_t st2,
@@ -139,16 +68,49 @@ __global__ __launch_bounds__(256) void k_pcg64_stream(double *__restrict__ out, 
 #endif
 // MINW = waves per SIMD the register budget is set for: 2 when every tile is resident (<= 2048 tiles, the pairing order below
 // assumes two per SIMD), 3 in the many-tile regime where a third resident wave adds a little issue throughput.
-#ifndef BOOT_RING_ROUNDS
-#define BOOT_RING_ROUNDS 2       // uniforms every lane produces ahead per bin step in ring mode (a lane uses ~1.5 on average)
-#endif
 #ifndef BOOT_BTPE_CAP
 #define BOOT_BTPE_CAP 1          // BTPE attempts a lane makes per bin step of its tile (0: as many as the draw takes, every lane waiting)
 #endif
 #ifndef BOOT_TAIL_LANES
 #define BOOT_TAIL_LANES 4        // with at most this many lanes still inside the replicate, draws run to completion
 #endif
-template <int MINW, bool FAST, int TAB>
+// One bin's share of a replicate's two sums (estimator.py:171-174, :182-183) and the replicate's mean / variance from them.  Every 1D
+// kernel below adds its bins in chain order through these two: the association of every product is numpy's, which is what makes
+// the replicate moments of all of them the same bit for bit.
+__device__ __forceinline__ void accumulate_1d(double &M1, double &M2, int32_t w, double v, double a, double b, double omq) {
+  double wd = (double)w;
+  M1 += (v * wd) * a;
+  M2 += ((v * v) * wd) * b - ((omq * v) * wd) * b;
+}
+__device__ __forceinline__ void close_replicate(double M1, double M2, double nobs, int32_t mean_only, double *mean_out, double *var_out) {
+  double mean = M1 / nobs;
+  double var = M2 / nobs - mean * mean;
+  if (mean_only) {  // estimator._mean_only_1p (estimator.py:188-204): [mean + 1, 10]
+    mean = mean + 1;
+    var = 10.0;
+  }
+  *mean_out = mean;
+  *var_out = var;
+}
+// A wave of a tile kernel whose "tile" is flagged in ca.tile_chain runs that chain in the one-wave-per-chain form, at the tile's
+// place (and priority) in the dispatch order.  True when it did: the wave is done.
+template <bool FAST>
+__device__ __forceinline__ bool run_tile_as_chain(const ChainArgs &ca, int64_t tile, int64_t n_tiles, int lane, uint64_t st0, uint64_t st1,
+                                                  int32_t num_boot, int32_t mean_only, int64_t ld, double *__restrict__ out_mean,
+                                                  double *__restrict__ out_var, int64_t *__restrict__ wave_clock) {
+  if (ca.tile_chain) {
+    int cidx = __builtin_amdgcn_readfirstlane(ca.tile_chain[tile]);
+    if (cidx >= 0) {
+      if (tile * 2 < n_tiles) __builtin_amdgcn_s_setprio(BOOT_SETPRIO);
+      chain_body<FAST>(ca, (int64_t)cidx, lane, st0, st1, num_boot, mean_only, ld, out_mean, out_var,
+                       wave_clock ? wave_clock + MM_CHAIN_CLOCK_OFF : nullptr);
+      return true;
+    }
+  }
+  return false;
+}
+
+template <int MINW, bool FAST>
 __global__ __launch_bounds__(256, MINW) void k_boot1d_replay(const double *__restrict__ pk_, const double *__restrict__ lq_,
                                                        const double *__restrict__ v, const double *__restrict__ a,
                                                        const double *__restrict__ b,
@@ -158,21 +120,11 @@ __global__ __launch_bounds__(256, MINW) void k_boot1d_replay(const double *__res
                                                        uint64_t st2, uint64_t st3, int32_t num_boot, int32_t mean_only,
                                                        int64_t ld, double *__restrict__ out_mean, double *__restrict__ out_var,
                                                        int32_t *__restrict__ w_dump, int32_t kmax_dump,
-                                                       int64_t *__restrict__ wave_clock, ChainArgs ca,
-                                                       const double *__restrict__ stream_tab, int64_t stream_len,
-                                                       int32_t *__restrict__ stream_overflow) {
+                                                       int64_t *__restrict__ wave_clock, ChainArgs ca) {
   int lane = mm_lane();
   int64_t tile = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   if (tile >= n_tiles) return;
-  if (ca.tile_chain) {                                  // this wave's "tile" may be a chain of the one-wave-per-chain form
-    int cidx = __builtin_amdgcn_readfirstlane(ca.tile_chain[tile]);
-    if (cidx >= 0) {
-      if (tile * 2 < n_tiles) __builtin_amdgcn_s_setprio(BOOT_SETPRIO);
-      chain_body<FAST>(ca, (int64_t)cidx, lane, st0, st1, num_boot, mean_only, ld, out_mean, out_var,
-                       wave_clock ? wave_clock + MM_CHAIN_CLOCK_OFF : nullptr);
-      return;
-    }
-  }
+  if (run_tile_as_chain<FAST>(ca, tile, n_tiles, lane, st0, st1, num_boot, mean_only, ld, out_mean, out_var, wave_clock)) return;
   int64_t t_start = wave_clock ? (int64_t)wall_clock64() : 0;
   // Two waves share a SIMD.  The host puts the long tiles in the first half of the grid (engine.pair_tiles) and pairs
   // each with a short one from the second half: the long tile is the critical path, so it is served first.
@@ -182,8 +134,6 @@ __global__ __launch_bounds__(256, MINW) void k_boot1d_replay(const double *__res
   int64_t row = slot_row[slot];
   if (K <= 0 || row < 0) K = 0;  // unused lane
   int64_t row0 = tile_ptr[tile];
-  int kmax = (int)(tile_ptr[tile + 1] - row0);
-  if (ca.debug_rows_mod > 0) row0 %= ca.debug_rows_mod;     // (timing experiment: operands out of a cache-resident region)
   double nobs = slot_nobs[slot];
   double omq = slot_omq[slot];  // 1 - q of the pair's group
   int32_t n = (int32_t)nobs;  // N_g < 2^31 (checked by the host)
@@ -195,36 +145,8 @@ __global__ __launch_bounds__(256, MINW) void k_boot1d_replay(const double *__res
       ov[r] = NAN;
     }
   }
-  typename npyrng::GenOf<TAB>::type g;
-  if constexpr (TAB == 2) {
-    __shared__ double ring_lds[16 * 256];
-    g.s_hi = st0;
-    g.s_lo = st1;
-    g.i_hi = st2;
-    g.i_lo = st3;
-    g.head = 0;
-    g.tail = 0;
-    g.ring = ring_lds + threadIdx.x;
-    g.top_up(10);
-  } else if constexpr (TAB == 1) {
-    g.tab = stream_tab;
-    g.len = stream_len;
-    g.pos = 0;
-    g.overflow = stream_overflow;
-  } else {
-    g.s_hi = st0;
-    g.s_lo = st1;
-    g.i_hi = st2;
-    g.i_lo = st3;
-  }
+  npyrng::Pcg64 g{st0, st1, st2, st3};
   const bool run = K >= 2;
-#ifdef BOOT_STAMPS
-  uint64_t stamp_inv = 0, stamp_btpe = 0, stamp_t0 = __builtin_amdgcn_s_memtime();
-  uint64_t stamp_fastcall = 0;                       // wave time inside the fast BTPE call (the rest of stamp_btpe is the exact redo)
-  uint64_t stamp_iters = 0, stamp_tail_iters = 0;    // bin steps the wave really made (retries included) / of them with only stragglers left
-  uint64_t cnt_bt = 0, cnt_fb = 0;                   // BTPE draws of this lane / of them redone in the exact arithmetic
-  uint64_t stamp_bt[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // inside the fast BTPE: set-up | uniforms | regions | floor + k | explicit product | squeeze | Stirling
-#endif
   // operands of the NEXT bin step are loaded while the current one computes (one lane = one latency-bound
   // sequential chain, so an exposed L2/HBM round trip per step would be a large part of the step)
   const int64_t obase = row0 * 64 + lane;
@@ -242,15 +164,10 @@ __global__ __launch_bounds__(256, MINW) void k_boot1d_replay(const double *__res
       const bool act = run && kl < K;
       const uint64_t act_mask = __ballot(act);
       if (act_mask == 0) break;
-#ifdef BOOT_STAMPS
-      stamp_iters++;
-      if (__popcll(act_mask) <= BOOT_TAIL_LANES) stamp_tail_iters++;
-#endif
       const int cap = (BOOT_BTPE_CAP > 0 && __popcll(act_mask) > BOOT_TAIL_LANES) ? BOOT_BTPE_CAP : 0;
       int kn = kl + 1 < K ? kl + 1 : 0;
       int64_t on = obase + (int64_t)kn * 64;
       double n_pk = pk_[on], n_lq = lq_[on], n_v = v[on], n_a = a[on], n_b = b[on];
-      if constexpr (TAB == 2) g.top_up(BOOT_RING_ROUNDS);
       bool adv = false;
       if (act) {
         int32_t w;
@@ -258,52 +175,8 @@ __global__ __launch_bounds__(256, MINW) void k_boot1d_replay(const double *__res
         if (kl < K - 1) {
           w = 0;
           if (live) {
-#ifdef BOOT_STAMPS  // diagnostic build only (tools/replay_stamps.sh): where a wave-step spends its cycles.  Same draws.
-            {
-              uint64_t s0, s1, s2;
-              NPY_CLOCK(s0);
-              bool flip = !(c_pk <= 0.5);
-              double p = flip ? 1.0 - c_pk : c_pk;
-              int32_t X = 0;
-              bool zero = (dn == 0 || c_pk == 0.0), inv = !zero && (p * (double)dn <= 30.0);
-              if (inv) {
-                double U = npyrng::pcg64_next_double(g);
-                int32_t xf = FAST ? npyrng::binomial_inversion_fast<int32_t>(U, dn, p, c_lq) : -1;
-                X = xf >= 0 ? xf : npyrng::binomial_inversion_pre<int32_t>(g, dn, p, c_lq, U);
-              }
-              NPY_CLOCK(s1);
-              auto saved = g.mark();
-              bool bt = !zero && !inv;
-              if (bt) {
-                NPY_CLOCK(stamp_bt[7]);
-                X = FAST ? npyrng::binomial_btpe_fast<int32_t>(g, dn, p, cap, stamp_bt) : -1;
-                cnt_bt++;
-              }
-              uint64_t s15;
-              NPY_CLOCK(s15);
-              stamp_fastcall += s15 - s1;
-              if (bt && X == -2) {
-                pending = true;
-                cnt_bt--;
-#ifdef STAMP_RETRY       // (the second counter then counts retried attempts instead of exact redos)
-                cnt_fb++;
-#endif
-              } else if (bt && X < 0) {
-#ifndef STAMP_RETRY
-                cnt_fb++;
-#endif
-                g.rewind(saved);
-                X = npyrng::binomial_btpe<int32_t>(g, dn, p);
-              }
-              NPY_CLOCK(s2);
-              stamp_inv += s1 - s0;
-              stamp_btpe += s2 - s1;
-              w = zero ? 0 : (flip ? dn - X : X);
-            }
-#else
             if constexpr (FAST) w = npyrng::binomial_pre_capped<int32_t>(g, c_pk, c_lq, dn, cap, pending);
             else w = npyrng::binomial_pre<int32_t, false>(g, c_pk, c_lq, dn);
-#endif
             if (!pending) {
               dn -= w;
               if (dn <= 0) live = false;
@@ -314,11 +187,7 @@ __global__ __launch_bounds__(256, MINW) void k_boot1d_replay(const double *__res
         }
         if (!pending) {
           if (w_dump) w_dump[((int64_t)slot * kmax_dump + kl) * num_boot + r] = (int32_t)w;
-          if (w != 0) {
-            double wd = (double)w;
-            M1 += (c_v * wd) * c_a;
-            M2 += ((c_v * c_v) * wd) * c_b - ((omq * c_v) * wd) * c_b;
-          }
+          if (w != 0) accumulate_1d(M1, M2, w, c_v, c_a, c_b, omq);
           adv = true;
         }
       }
@@ -328,39 +197,12 @@ __global__ __launch_bounds__(256, MINW) void k_boot1d_replay(const double *__res
       }
     }
     if (run) {
-      double mean = M1 / nobs;
-      double var = M2 / nobs - mean * mean;
-      if (mean_only) {  // estimator._mean_only_1p (estimator.py:188-204): [mean + 1, 10]
-        mean = mean + 1;
-        var = 10.0;
-      }
+      double mean, var;
+      close_replicate(M1, M2, nobs, mean_only, &mean, &var);
       om[r] = mean;
       ov[r] = var;
     }
   }
-#ifdef BOOT_STAMPS
-  // the inner stamps are accumulated by every lane while it is active in that code; the busiest lane's sum is the (lower bound of
-  // the) wave's time there
-  for (int i = 0; i < 7; i++)
-    for (int off = 32; off > 0; off >>= 1) {
-      uint64_t o = (uint64_t)__shfl_xor((long long)stamp_bt[i], off, 64);
-      stamp_bt[i] = o > stamp_bt[i] ? o : stamp_bt[i];
-    }
-  for (int off = 32; off > 0; off >>= 1) {
-    cnt_bt += (uint64_t)__shfl_xor((long long)cnt_bt, off, 64);
-    cnt_fb += (uint64_t)__shfl_xor((long long)cnt_fb, off, 64);
-  }
-  if (wave_clock && lane == 0) wave_clock[(n_tiles + tile) * 8 + 7] = (int64_t)((cnt_fb << 40) | cnt_bt);
-  if (wave_clock && lane == 0) {  // shader-clock cycles: total, inside the inversion sampler, inside BTPE (wave_clock slots 2, 3 reused)
-    wave_clock[tile * 4 + 0] = (int64_t)((stamp_tail_iters << 40) | stamp_iters);
-    wave_clock[tile * 4 + 1] = (int64_t)(__builtin_amdgcn_s_memtime() - stamp_t0);
-    wave_clock[tile * 4 + 2] = (int64_t)stamp_inv;
-    wave_clock[tile * 4 + 3] = (int64_t)stamp_btpe;
-    for (int i = 0; i < 6; i++) wave_clock[(n_tiles + tile) * 8 + i] = (int64_t)stamp_bt[i];   // second half of the debug buffer
-    wave_clock[(n_tiles + tile) * 8 + 6] = (int64_t)stamp_fastcall;
-    return;
-  }
-#endif
   if (wave_clock && lane == 0) {  // profiling hook (mm_debug_wave_clock): when and where this wave ran
     wave_clock[tile * 4 + 0] = t_start;
     wave_clock[tile * 4 + 1] = (int64_t)wall_clock64();
@@ -460,9 +302,6 @@ __device__ __forceinline__ void chain_body(const ChainArgs &ca, int64_t ch, int 
   g.c_lo = jump[lane * 4 + 3];
   g.fill(st0, st1);
   double keep_m = 0.0, keep_v = 0.0;     // lane (r & 63) keeps replicate r until 64 of them go out as one coalesced store
-#ifdef BOOT_STAMPS
-  uint64_t st_n_inv = 0, st_c_inv = 0, st_n_bt = 0, st_c_bt = 0, st_t0 = __builtin_amdgcn_s_memtime();
-#endif
   for (int r = 0; r < num_boot; r++) {
     double M1 = 0.0, M2 = 0.0;
     int32_t dn = n;
@@ -470,41 +309,19 @@ __device__ __forceinline__ void chain_body(const ChainArgs &ca, int64_t ch, int 
     for (int k = 0; k < K - 1; k++) {
       const double *nx = op + (int64_t)(k + 1) * 8;          // k + 1 <= K - 1: the last bin's v, a, b are read here
       double n_pk = nx[0], n_lq = nx[1], n_v = nx[2], n_a = nx[3], n_b = nx[4];
-#ifdef BOOT_STAMPS   // diagnostic build (tools/chain_micro.py): shader cycles inside the sampler call, by sampler
-      uint64_t s0_, s1_;
-      const double pe_ = c_pk <= 0.5 ? c_pk : 1.0 - c_pk;
-      const bool inv_ = pe_ * (double)dn <= 30.0;
-      NPY_CLOCK(s0_);
-#endif
       int32_t w = npyrng::binomial_pre<int32_t, FAST, true>(g, c_pk, c_lq, dn);
-#ifdef BOOT_STAMPS
-      NPY_CLOCK(s1_);
-      if (c_pk != 0.0) {
-        if (inv_) { st_n_inv++; st_c_inv += s1_ - s0_; } else { st_n_bt++; st_c_bt += s1_ - s0_; }
-      }
-#endif
       dn -= w;
       if (w_dump && lane == 0) w_dump[((int64_t)ch * kmax_dump + k) * num_boot + r] = w;
-      if (w != 0) {
-        double wd = (double)w;
-        M1 += (c_v * wd) * c_a;
-        M2 += ((c_v * c_v) * wd) * c_b - ((omq * c_v) * wd) * c_b;
-      }
+      if (w != 0) accumulate_1d(M1, M2, w, c_v, c_a, c_b, omq);
       c_pk = n_pk; c_lq = n_lq; c_v = n_v; c_a = n_a; c_b = n_b;
       if (dn <= 0) break;                                      // numpy stops the chain here; nothing is left for later bins
     }
     if (dn > 0) {                                              // the loop ran to its end: c_* hold the last bin, which takes the rest
       if (w_dump && lane == 0) w_dump[((int64_t)ch * kmax_dump + (K - 1)) * num_boot + r] = dn;
-      double wd = (double)dn;
-      M1 += (c_v * wd) * c_a;
-      M2 += ((c_v * c_v) * wd) * c_b - ((omq * c_v) * wd) * c_b;
+      accumulate_1d(M1, M2, dn, c_v, c_a, c_b, omq);
     }
-    double mean = M1 / nobs;
-    double var = M2 / nobs - mean * mean;
-    if (mean_only) {
-      mean = mean + 1;
-      var = 10.0;
-    }
+    double mean, var;
+    close_replicate(M1, M2, nobs, mean_only, &mean, &var);
     if (lane == (r & 63)) {
       keep_m = mean;
       keep_v = var;
@@ -517,16 +334,9 @@ __device__ __forceinline__ void chain_body(const ChainArgs &ca, int64_t ch, int 
       }
     }
   }
-  if (wave_clock && lane == 0) {   // 8 int64 per chain: start, end (100 MHz); the stamps build adds sampler calls / shader cycles
+  if (wave_clock && lane == 0) {   // 8 int64 per chain: start, end (100 MHz); the rest spare
     wave_clock[ch * 8 + 0] = t_start;
     wave_clock[ch * 8 + 1] = (int64_t)wall_clock64();
-#ifdef BOOT_STAMPS
-    wave_clock[ch * 8 + 2] = (int64_t)st_n_inv;
-    wave_clock[ch * 8 + 3] = (int64_t)st_c_inv;
-    wave_clock[ch * 8 + 4] = (int64_t)st_n_bt;
-    wave_clock[ch * 8 + 5] = (int64_t)st_c_bt;
-    wave_clock[ch * 8 + 6] = (int64_t)(__builtin_amdgcn_s_memtime() - st_t0);
-#endif
   }
 }
 
@@ -592,26 +402,13 @@ __global__ __launch_bounds__(256, ASYNC_MIN_WAVES) void k_boot1d_async(const dou
   double M1 = 0.0, M2 = 0.0;
   BinOps cur = load_bin(rec), nxt = load_bin(rec + (K ? 8 : 0));
   int64_t passes = 0;
-#ifdef BOOT_STAMPS   // diagnostic build (tools/chain_sweep.py): shader cycles of a wave per phase of the pass
-  uint64_t ph_c[8] = {0, 0, 0, 0, 0, 0, 0, 0}, ph_t;
-#define ASYNC_STAMP(i) do { uint64_t t_; NPY_CLOCK(t_); ph_c[i] += t_ - ph_t; ph_t = t_; } while (0)
-#else
-#define ASYNC_STAMP(i)
-#endif
   while (__ballot(state != LS_IDLE)) {
     passes++;
-#ifdef BOOT_STAMPS
-    NPY_CLOCK(ph_t);
-#endif
     // ---- retire the finished draw; finish the replicate or move on to the next bin ----------------------------------------
     if (state == LS_DONE) {
       const int32_t w = D.w;
       if (w_dump) w_dump[((int64_t)slot * kmax_dump + k) * num_boot + r] = w;
-      if (w != 0) {
-        double wd = (double)w;
-        M1 += (cur.v * wd) * cur.a;
-        M2 += ((cur.v * cur.v) * wd) * cur.b - ((omq * cur.v) * wd) * cur.b;
-      }
+      if (w != 0) accumulate_1d(M1, M2, w, cur.v, cur.a, cur.b, omq);
       dn -= w;
       k++;
       cur = nxt;                                                 // record k
@@ -634,16 +431,10 @@ __global__ __launch_bounds__(256, ASYNC_MIN_WAVES) void k_boot1d_async(const dou
     if ((passes & 3) == 0 && state == LS_FINISH) {
       if (dn > 0) {                                              // every bin but the last has drawn: the last one takes the rest
         if (w_dump) w_dump[((int64_t)slot * kmax_dump + k) * num_boot + r] = dn;
-        double wd = (double)dn;
-        M1 += (cur.v * wd) * cur.a;
-        M2 += ((cur.v * cur.v) * wd) * cur.b - ((omq * cur.v) * wd) * cur.b;
+        accumulate_1d(M1, M2, dn, cur.v, cur.a, cur.b, omq);
       }
-      double mean = M1 / nobs;
-      double var = M2 / nobs - mean * mean;
-      if (mean_only) {
-        mean = mean + 1;
-        var = 10.0;
-      }
+      double mean, var;
+      close_replicate(M1, M2, nobs, mean_only, &mean, &var);
       om[r] = mean;
       ov[r] = var;
       r++;
@@ -655,35 +446,28 @@ __global__ __launch_bounds__(256, ASYNC_MIN_WAVES) void k_boot1d_async(const dou
         state = LS_IDLE;
       }
     }
-    ASYNC_STAMP(0);
     // ---- the draw of bin k, phase by phase (csrc/npy_rng.h) ------------------------------------------------------------------
     if (FAST) {
       // start + inversion segment + BTPE attempt in one straight line for every lane (csrc/npy_rng.h: the branch-free forms):
       // the independent dependency chains interleave instead of queueing behind three branches
       int32_t s0 = lane_begin_bf(D, g, cur.pk, cur.lq, dn > 0 ? dn : 1, state == LS_START);
       state = state == LS_START ? s0 : state;
-      ASYNC_STAMP(1);
       state = lane_inv_att_bf(D, g, state);
-      ASYNC_STAMP(2);
       if (state == LS_ATT2) state = lane_att_rest(D);
     } else if (state == LS_START) {                              // mm_debug_replay_arith(1): numpy's arithmetic, draw by draw
       D.w = binomial_pre<int32_t, false>(g, cur.pk, cur.lq, dn);
       state = LS_DONE;
     }
-    ASYNC_STAMP(3);
     if (state == LS_EXPL) state = lane_expl(D);
-    ASYNC_STAMP(4);
     // the rarer phases do not run on every pass: a lane in one of them waits a pass or a few, every other lane saves the time
     // (squeeze / Stirling: ~3 % of the lanes, every second pass; the exact redo: ~0.3 % of the draws, every 32nd pass)
     if ((passes & 1) == 0) {
       if (state == LS_SQZ) state = lane_sqz(D);
     }
-    ASYNC_STAMP(5);
     if ((passes & 31) == 0) {
       if (state == LS_XINV) state = lane_xinv(D, g);
       if (state == LS_XBT) state = lane_xbt(D, g);
     }
-    ASYNC_STAMP(6);
   }
   if (wave_clock && mm_lane() == 0) {
     int64_t wave = slot >> 6;
@@ -691,9 +475,6 @@ __global__ __launch_bounds__(256, ASYNC_MIN_WAVES) void k_boot1d_async(const dou
     wave_clock[wave * 4 + 1] = (int64_t)wall_clock64();
     wave_clock[wave * 4 + 2] = passes;
     wave_clock[wave * 4 + 3] = 0;
-#ifdef BOOT_STAMPS
-    for (int i = 0; i < 7; i++) wave_clock[(1 << 19) + wave * 8 + i] = (int64_t)ph_c[i];
-#endif
   }
 }
 
@@ -788,13 +569,6 @@ __global__ __launch_bounds__(256) void k_boot_fill_log(double *__restrict__ mean
 // replicates give the chip millions of independent chains.  Each (pair, replicate) owns a PCG64 stream
 // derived from (seed, pair, replicate) -- NOT numpy's single stream: results are statistically equivalent
 // to the reference (same algorithm, different random numbers), not draw-for-draw identical.
-__device__ __forceinline__ uint64_t mix64b(uint64_t x) {
-  x += 0x9E3779B97F4A7C15ull;
-  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-  return x ^ (x >> 31);
-}
-
 __global__ __launch_bounds__(256) void k_boot1d_fast(const double *__restrict__ pk_, const double *__restrict__ lq_,
                                                      const double *__restrict__ v, const double *__restrict__ a,
                                                      const double *__restrict__ b, const int64_t *__restrict__ tile_ptr,
@@ -816,8 +590,8 @@ __global__ __launch_bounds__(256) void k_boot1d_fast(const double *__restrict__ 
   int64_t obase = tile_ptr[slot >> 6] * 64 + (slot & 63);
   double nobs = slot_nobs[slot], omq = slot_omq[slot];
   int32_t n = (int32_t)nobs;
-  uint64_t h = mix64b(seed ^ mix64b((uint64_t)row * 0x100000001B3ull + (uint64_t)r));
-  npyrng::Pcg64 g{mix64b(h), mix64b(h + 1), mix64b(h + 2), mix64b(h + 3) | 1ull};
+  uint64_t h = mix64(seed ^ mix64((uint64_t)row * 0x100000001B3ull + (uint64_t)r));
+  npyrng::Pcg64 g{mix64(h), mix64(h + 1), mix64(h + 2), mix64(h + 3) | 1ull};
   double M1 = 0.0, M2 = 0.0;
   int32_t dn = n;
   for (int k = 0; k < K; k++) {
@@ -829,17 +603,11 @@ __global__ __launch_bounds__(256) void k_boot1d_fast(const double *__restrict__ 
     } else {
       w = dn > 0 ? dn : 0;
     }
-    double wd = (double)w, vv = v[o], bb = b[o];
-    M1 += (vv * wd) * a[o];
-    M2 += ((vv * vv) * wd) * bb - ((omq * vv) * wd) * bb;
+    accumulate_1d(M1, M2, w, v[o], a[o], b[o], omq);
   }
   if (mine) {
-    double mean = M1 / nobs;
-    double var = M2 / nobs - mean * mean;
-    if (mean_only) {
-      mean = mean + 1;
-      var = 10.0;
-    }
+    double mean, var;
+    close_replicate(M1, M2, nobs, mean_only, &mean, &var);
     out_mean[row * ld + 1 + r] = mean;
     out_var[row * ld + 1 + r] = var;
   }
@@ -867,15 +635,7 @@ __global__ __launch_bounds__(256, MINW) void k_boot1d_free(const double *__restr
   int lane = mm_lane();
   int64_t tile = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   if (tile >= n_tiles) return;
-  if (ca.tile_chain) {
-    int cidx = __builtin_amdgcn_readfirstlane(ca.tile_chain[tile]);
-    if (cidx >= 0) {
-      if (tile * 2 < n_tiles) __builtin_amdgcn_s_setprio(BOOT_SETPRIO);
-      chain_body<FAST>(ca, (int64_t)cidx, lane, st0, st1, num_boot, mean_only, ld, out_mean, out_var,
-                       wave_clock ? wave_clock + MM_CHAIN_CLOCK_OFF : nullptr);
-      return;
-    }
-  }
+  if (run_tile_as_chain<FAST>(ca, tile, n_tiles, lane, st0, st1, num_boot, mean_only, ld, out_mean, out_var, wave_clock)) return;
   int64_t t_start = wave_clock ? (int64_t)wall_clock64() : 0;
   if (tile * 2 < n_tiles) __builtin_amdgcn_s_setprio(BOOT_SETPRIO);
   int64_t slot = tile * 64 + lane;
@@ -905,35 +665,9 @@ __global__ __launch_bounds__(256, MINW) void k_boot1d_free(const double *__restr
   double c_b = rec[4];
   int64_t steps = 0;
   for (;;) {
-#ifdef BOOT_FREE_SYNC    // experiment: the lanes meet at the end of every replicate, as in k_boot1d_replay (isolates the cost of the record layout)
-    const bool act = more && kl < K;
-    const uint64_t act_mask = __ballot(act);
-    if (act_mask == 0) {
-      if (more) {
-        double mean = M1 / nobs;
-        double var = M2 / nobs - mean * mean;
-        if (mean_only) {
-          mean = mean + 1;
-          var = 10.0;
-        }
-        om[rl] = mean;
-        ov[rl] = var;
-        rl++;
-        kl = 0;
-        M1 = 0.0;
-        M2 = 0.0;
-        dn = n;
-        live = true;
-        more = rl < num_boot;
-      }
-      if (__ballot(more) == 0) break;
-      continue;
-    }
-#else
     const bool act = more;
     const uint64_t act_mask = __ballot(more);
     if (act_mask == 0) break;
-#endif
     steps++;
     const int cap = (BOOT_BTPE_CAP > 0 && __popcll(act_mask) > BOOT_TAIL_LANES) ? BOOT_BTPE_CAP : 0;
     const int kn = kl + 1 < K ? kl + 1 : 0;
@@ -959,33 +693,14 @@ __global__ __launch_bounds__(256, MINW) void k_boot1d_free(const double *__restr
       }
       if (!pending) {
         if (w_dump) w_dump[((int64_t)slot * kmax_dump + kl) * num_boot + rl] = (int32_t)w;
-        if (w != 0) {
-          double wd = (double)w;
-          M1 += (c_v * wd) * c_a;
-          M2 += ((c_v * c_v) * wd) * c_b - ((omq * c_v) * wd) * c_b;
-        }
+        if (w != 0) accumulate_1d(M1, M2, w, c_v, c_a, c_b, omq);
         kl++;
         c01 = n01; c23 = n23; c_b = n_b;
-#ifndef BOOT_FREE_SYNC
         if (kl == K) {                       // the replicate is complete (the operands just taken over are bin 0's again)
-          double mean = M1 / nobs;
-          double var = M2 / nobs - mean * mean;
-          if (mean_only) {  // estimator._mean_only_1p (estimator.py:188-204): [mean + 1, 10]
-            mean = mean + 1;
-            var = 10.0;
-          }
-#ifdef BOOT_FREE_ABLATE_STORES   // timing experiment (WRONG results): one replicate in 16 is stored
-          if ((rl & 15) == 15) {
-            om[rl] = mean;
-            ov[rl] = var;
-          }
-#elif defined(BOOT_FREE_ABLATE_DIV)   // timing experiment (WRONG results): no division in the replicate's epilogue
-          om[rl] = M1;
-          ov[rl] = M2;
-#else
+          double mean, var;
+          close_replicate(M1, M2, nobs, mean_only, &mean, &var);
           om[rl] = mean;
           ov[rl] = var;
-#endif
           rl++;
           kl = 0;
           M1 = 0.0;
@@ -994,7 +709,6 @@ __global__ __launch_bounds__(256, MINW) void k_boot1d_free(const double *__restr
           live = true;
           more = rl < num_boot;
         }
-#endif
       }
     }
   }
@@ -1136,24 +850,34 @@ __global__ __launch_bounds__(256, MINW) void k_boot2d_replay(const double *__res
 }
 
 static int64_t *g_wave_clock = nullptr;  // set by mm_debug_wave_clock; nullptr = no profiling writes
-static int g_ring_rng = 0;               // set by mm_debug_replay_ring: 1 = the tile kernel's lanes produce their uniforms ahead into an LDS ring
-static int64_t g_debug_rows_mod = 0;    // MM_DEBUG_ROWS_MOD in the environment of the process (read once): timing experiments only
 static int g_exact_arith = 0;            // set by mm_debug_replay_arith: 1 = numpy's fp64 arithmetic in every search loop (A/B timing, tests)
+
+// The chains a tile launch takes along (``chains`` may be NULL: none) as the kernels' ChainArgs.
+static int chain_args_of(const mm_chain_tiles *chains, ChainArgs *ca) {
+  *ca = ChainArgs{};
+  if (!chains) return MM_OK;
+  MM_ARG(chains->d_tile_chain && chains->d_ops && chains->d_ch_base && chains->d_ch_K && chains->d_ch_nobs && chains->d_ch_omq &&
+         chains->d_ch_row && chains->d_jump);
+  *ca = ChainArgs{chains->d_ops, chains->d_ch_base, chains->d_ch_K, chains->d_ch_nobs, chains->d_ch_omq, chains->d_ch_row, chains->d_jump,
+                  chains->d_tile_chain, chains->d_w_dump, chains->kmax_dump};
+  return MM_OK;
+}
+
+// The instantiation of a tile kernel for one launch.  ``three``: the 168-VGPR build (three waves per SIMD) instead of the
+// BOOT_MIN_WAVES one; FAST is off under mm_debug_replay_arith(1).  ``pick(minw, fast)`` names the kernel: both arguments are
+// std::integral_constant values (``minw()`` is a constant expression), every instantiation of one kernel has the same type.
+template <typename Pick>
+static auto tile_kernel(bool three, Pick pick) {
+  std::integral_constant<int, 3> w3;
+  std::integral_constant<int, BOOT_MIN_WAVES> w2;
+  if (three) return g_exact_arith ? pick(w3, std::false_type()) : pick(w3, std::true_type());
+  return g_exact_arith ? pick(w2, std::false_type()) : pick(w2, std::true_type());
+}
 
 extern "C" {
 
 int mm_debug_wave_clock(int64_t *d_buf) {
   g_wave_clock = d_buf;
-  return MM_OK;
-}
-
-int mm_debug_replay_rows_mod(int64_t rows) {
-  g_debug_rows_mod = rows > 0 ? rows : 0;
-  return MM_OK;
-}
-
-int mm_debug_replay_ring(int32_t on) {
-  g_ring_rng = on ? 1 : 0;
   return MM_OK;
 }
 
@@ -1166,17 +890,10 @@ int mm_boot1d_replay(const double *d_pk, const double *d_lq, const double *d_v, 
                      const int64_t *d_tile_ptr, int64_t n_tiles, const int32_t *d_slot_K, const double *d_slot_nobs,
                      const double *d_slot_omq, const int64_t *d_slot_row, const uint64_t pcg_state[4], int32_t num_boot,
                      int32_t mean_only, int64_t ld, double *d_out_mean, double *d_out_var, int32_t *d_w_dump, int32_t kmax_dump,
-                     int64_t co_resident_waves, const mm_chain_tiles *chains, const double *d_stream, int64_t stream_len,
-                     int32_t *d_stream_overflow, void *stream) {
+                     int64_t co_resident_waves, const mm_chain_tiles *chains, void *stream) {
   MM_ARG(d_pk && d_lq && d_v && d_a && d_b && d_tile_ptr && d_slot_K && d_slot_nobs && d_slot_omq && d_slot_row && pcg_state);
-  ChainArgs ca{};
-  ca.debug_rows_mod = g_debug_rows_mod;
-  if (chains) {
-    MM_ARG(chains->d_tile_chain && chains->d_ops && chains->d_ch_base && chains->d_ch_K && chains->d_ch_nobs && chains->d_ch_omq &&
-           chains->d_ch_row && chains->d_jump);
-    ca = ChainArgs{chains->d_ops, chains->d_ch_base, chains->d_ch_K, chains->d_ch_nobs, chains->d_ch_omq, chains->d_ch_row, chains->d_jump,
-                   chains->d_tile_chain, chains->d_w_dump, chains->kmax_dump, g_debug_rows_mod};
-  }
+  ChainArgs ca;
+  if (int rc = chain_args_of(chains, &ca)) return rc;
   MM_ARG(d_out_mean && d_out_var && n_tiles >= 0 && num_boot > 0 && ld >= (int64_t)num_boot + 1);
   if (n_tiles == 0) return MM_OK;
   MM_ARG(n_tiles < 2147483647LL);
@@ -1184,19 +901,11 @@ int mm_boot1d_replay(const double *d_pk, const double *d_lq, const double *d_v, 
   // (one tile per workgroup was measured too: worse when everything is resident, a wash in the many-tile regime)
   // the 168-VGPR build (three waves per SIMD) when this launch and the chain-kernel waves running beside it need more than two
   // wave slots per SIMD; the two-wave build otherwise
-  MM_ARG(!d_stream || (stream_len > 0 && d_stream_overflow));
   const bool three = n_tiles + (co_resident_waves > 0 ? co_resident_waves : 0) > 2048;
-  const int mode = d_stream ? 1 : (g_ring_rng ? 2 : 0);
-  auto kern = mode == 1 ? (three ? (g_exact_arith ? k_boot1d_replay<3, false, 1> : k_boot1d_replay<3, true, 1>)
-                                 : (g_exact_arith ? k_boot1d_replay<BOOT_MIN_WAVES, false, 1> : k_boot1d_replay<BOOT_MIN_WAVES, true, 1>))
-            : mode == 2 ? (three ? (g_exact_arith ? k_boot1d_replay<3, false, 2> : k_boot1d_replay<3, true, 2>)
-                                 : (g_exact_arith ? k_boot1d_replay<BOOT_MIN_WAVES, false, 2> : k_boot1d_replay<BOOT_MIN_WAVES, true, 2>))
-                        : (three ? (g_exact_arith ? k_boot1d_replay<3, false, 0> : k_boot1d_replay<3, true, 0>)
-                                 : (g_exact_arith ? k_boot1d_replay<BOOT_MIN_WAVES, false, 0> : k_boot1d_replay<BOOT_MIN_WAVES, true, 0>));
+  auto kern = tile_kernel(three, [](auto minw, auto fast) { return &k_boot1d_replay<minw(), fast()>; });
   hipLaunchKernelGGL(kern, dim3((unsigned)((n_tiles + 3) / 4)), dim3(256), 0, (hipStream_t)stream, d_pk, d_lq, d_v, d_a, d_b,
                      d_tile_ptr, n_tiles, d_slot_K, d_slot_nobs, d_slot_omq, d_slot_row, pcg_state[0], pcg_state[1], pcg_state[2],
-                     pcg_state[3], num_boot, mean_only, ld, d_out_mean, d_out_var, d_w_dump, kmax_dump, g_wave_clock, ca, d_stream,
-                     stream_len, d_stream_overflow);
+                     pcg_state[3], num_boot, mean_only, ld, d_out_mean, d_out_var, d_w_dump, kmax_dump, g_wave_clock, ca);
   MM_LAUNCH_CHECK();
   return MM_OK;
 }
@@ -1206,19 +915,13 @@ int mm_boot1d_free(const double *d_recs, const int64_t *d_slot_rec, int64_t n_ti
                    int64_t ld, double *d_out_mean, double *d_out_var, int32_t *d_w_dump, int32_t kmax_dump, const mm_chain_tiles *chains,
                    void *stream) {
   MM_ARG(d_recs && d_slot_rec && d_slot_K && d_slot_nobs && d_slot_omq && d_slot_row && pcg_state);
-  ChainArgs ca{};
-  if (chains) {
-    MM_ARG(chains->d_tile_chain && chains->d_ops && chains->d_ch_base && chains->d_ch_K && chains->d_ch_nobs && chains->d_ch_omq &&
-           chains->d_ch_row && chains->d_jump);
-    ca = ChainArgs{chains->d_ops, chains->d_ch_base, chains->d_ch_K, chains->d_ch_nobs, chains->d_ch_omq, chains->d_ch_row, chains->d_jump,
-                   chains->d_tile_chain, chains->d_w_dump, chains->kmax_dump, 0};
-  }
+  ChainArgs ca;
+  if (int rc = chain_args_of(chains, &ca)) return rc;
   MM_ARG(d_out_mean && d_out_var && n_tiles >= 0 && num_boot > 0 && ld >= (int64_t)num_boot + 1);
   if (n_tiles == 0) return MM_OK;
   MM_ARG(n_tiles < 2147483647LL);
-  const bool three = n_tiles > 2048;       // the register budgets of mm_boot1d_replay: three waves per SIMD beyond 2,048 tiles
-  auto kern = three ? (g_exact_arith ? k_boot1d_free<3, false> : k_boot1d_free<3, true>)
-                    : (g_exact_arith ? k_boot1d_free<BOOT_MIN_WAVES, false> : k_boot1d_free<BOOT_MIN_WAVES, true>);
+  // the register budgets of mm_boot1d_replay: three waves per SIMD beyond 2,048 tiles
+  auto kern = tile_kernel(n_tiles > 2048, [](auto minw, auto fast) { return &k_boot1d_free<minw(), fast()>; });
   hipLaunchKernelGGL(kern, dim3((unsigned)((n_tiles + 3) / 4)), dim3(256), 0, (hipStream_t)stream, d_recs, d_slot_rec, n_tiles, d_slot_K,
                      d_slot_nobs, d_slot_omq, d_slot_row, pcg_state[0], pcg_state[1], pcg_state[2], pcg_state[3], num_boot, mean_only, ld,
                      d_out_mean, d_out_var, d_w_dump, kmax_dump, g_wave_clock, ca);
@@ -1244,7 +947,7 @@ int mm_boot1d_chain(const double *d_ops, const int64_t *d_ch_base, const int32_t
   MM_ARG(n_chains >= 0 && n_chains < 2147483647LL && num_boot > 0 && ld >= (int64_t)num_boot + 1);
   if (n_chains == 0) return MM_OK;
   auto kern = g_exact_arith ? k_boot1d_chain<false> : k_boot1d_chain<true>;
-  ChainArgs ca{d_ops, d_ch_base, d_ch_K, d_ch_nobs, d_ch_omq, d_ch_row, d_jump, nullptr, d_w_dump, kmax_dump, 0};
+  ChainArgs ca{d_ops, d_ch_base, d_ch_K, d_ch_nobs, d_ch_omq, d_ch_row, d_jump, nullptr, d_w_dump, kmax_dump};
   hipLaunchKernelGGL(kern, dim3((unsigned)((n_chains + 3) / 4)), dim3(256), 0, (hipStream_t)stream, ca, n_chains, pcg_state[0], pcg_state[1],
                      num_boot, mean_only, ld, d_out_mean, d_out_var, g_wave_clock ? g_wave_clock + MM_CHAIN_CLOCK_OFF : nullptr);
   MM_LAUNCH_CHECK();
@@ -1285,8 +988,7 @@ int mm_boot2d_replay(const double *d_pk, const double *d_lq, const double *d_v1,
   MM_ARG(d_pk && d_lq && d_v1 && d_v2 && d_a && d_b && d_tile_ptr && d_slot_K && d_slot_nobs && d_slot_omq && d_slot_row && pcg_state);
   MM_ARG(d_out_corr && n_tiles >= 0 && num_boot > 0 && ld >= (int64_t)num_boot + 1);
   if (n_tiles == 0) return MM_OK;
-  auto kern = n_tiles > 2048 ? (g_exact_arith ? k_boot2d_replay<3, false, false> : k_boot2d_replay<3, true, false>)
-                             : (g_exact_arith ? k_boot2d_replay<BOOT_MIN_WAVES, false, false> : k_boot2d_replay<BOOT_MIN_WAVES, true, false>);
+  auto kern = tile_kernel(n_tiles > 2048, [](auto minw, auto fast) { return &k_boot2d_replay<minw(), fast(), false>; });
   hipLaunchKernelGGL(kern, dim3((unsigned)((n_tiles + 3) / 4)), dim3(256), 0, (hipStream_t)stream, d_pk, d_lq, d_v1, d_v2, d_a, d_b,
                      d_tile_ptr, n_tiles, d_slot_K, d_slot_nobs, d_slot_omq, d_slot_row, pcg_state[0], pcg_state[1], pcg_state[2],
                      pcg_state[3], num_boot, ld, d_out_corr, (const int64_t *)nullptr);
@@ -1300,8 +1002,7 @@ int mm_boot2d_replay_rec(const double *d_recs, const int64_t *d_slot_rec, int64_
   MM_ARG(d_recs && d_slot_rec && d_slot_K && d_slot_nobs && d_slot_omq && d_slot_row && pcg_state);
   MM_ARG(d_out_corr && n_tiles >= 0 && num_boot > 0 && ld >= (int64_t)num_boot + 1);
   if (n_tiles == 0) return MM_OK;
-  auto kern = n_tiles > 2048 ? (g_exact_arith ? k_boot2d_replay<3, false, true> : k_boot2d_replay<3, true, true>)
-                             : (g_exact_arith ? k_boot2d_replay<BOOT_MIN_WAVES, false, true> : k_boot2d_replay<BOOT_MIN_WAVES, true, true>);
+  auto kern = tile_kernel(n_tiles > 2048, [](auto minw, auto fast) { return &k_boot2d_replay<minw(), fast(), true>; });
   const double *nul = nullptr;
   hipLaunchKernelGGL(kern, dim3((unsigned)((n_tiles + 3) / 4)), dim3(256), 0, (hipStream_t)stream, d_recs, nul, nul, nul, nul, nul,
                      (const int64_t *)nullptr, n_tiles, d_slot_K, d_slot_nobs, d_slot_omq, d_slot_row, pcg_state[0], pcg_state[1],

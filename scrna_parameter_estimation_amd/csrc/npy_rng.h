@@ -1,6 +1,6 @@
 // npy_rng.h -- from-scratch restatement of the numpy random path memento's bootstrap calls:
 //   np.random.Generator(np.random.PCG64(5)).multinomial(N, pvals, size=B)
-// (call sites: /root/reference/memento/bootstrap.py:102-103 and :135-137).
+// (call sites: memento/bootstrap.py:102-103 and :135-137).
 //
 // numpy (pinned here: 2.2.6; C sources are NOT in the wheel) implements this as
 //   PCG64 = PCG XSL-RR 128/64 (128-bit LCG, multiplier 0x2360ED051FC65DA44385DF649FCCF645);
@@ -29,21 +29,6 @@
 #pragma clang fp contract(off)
 #endif
 
-#if defined(BOOT_STAMPS) && defined(__HIPCC__)   // diagnostic build: cycle accumulators inside the fast BTPE
-#define NPY_ST_PARAM , uint64_t *npy_st
-#if defined(__HIP_DEVICE_COMPILE__)
-// one asm statement (s_memtime returns out of order with LDS / scalar loads) fenced against instruction scheduling on both sides
-#define NPY_CLOCK(t_) do { __builtin_amdgcn_sched_barrier(0); asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) :: "memory"); \
-                           __builtin_amdgcn_sched_barrier(0); } while (0)
-#define NPY_ST(i) do { uint64_t t_; NPY_CLOCK(t_); npy_st[i] += t_ - npy_st[7]; npy_st[7] = t_; } while (0)
-#else
-#define NPY_CLOCK(t_) ((t_) = 0)
-#define NPY_ST(i) (void)npy_st
-#endif
-#else
-#define NPY_ST_PARAM
-#define NPY_ST(i)
-#endif
 // NPY_KEEP(tk, x, alt): x, written so that the compiler cannot move what is computed from it out of the attempt loop.  ``tk`` is a
 // condition that is true on every pass but that only the run time knows (attempt <= n; BTPE runs for n > 60 and gives up after 16
 // attempts), ``alt`` any other run-time value.  The guarded fast paths keep their rarely taken branches cheap for the common path
@@ -83,14 +68,6 @@ NPY_HD uint64_t mulhi64(uint64_t a, uint64_t b) {
 
 // state = state * MULT + inc  (mod 2^128); output = rotr64(hi ^ lo, hi >> 58) of the NEW state.
 NPY_HD uint64_t pcg64_next64(Pcg64 &g) {
-#ifdef NPY_ABLATE_PCG  // timing experiments only (wrong draws): what the 128-bit multiply of the generator costs
-  {
-    uint64_t x = g.s_lo;
-    x ^= x >> 12; x ^= x << 25; x ^= x >> 27;
-    g.s_lo = x;
-    return x + g.s_hi;
-  }
-#endif
   const uint64_t M_HI = 2549297995355413924ULL, M_LO = 4865540595714422341ULL;
   uint64_t lo = g.s_lo * M_LO;
   uint64_t hi = mulhi64(g.s_lo, M_LO) + g.s_hi * M_LO + g.s_lo * M_HI;
@@ -236,9 +213,6 @@ NPY_HD Int binomial_inversion_pre(Gen &g, Int n, double p, double lq, double U) 
   Int bound = -1;  // computed lazily: np + 10*sqrt(np*q+1) >= 10, so X <= min(n, 9) can never exceed it
   Int X = 0;
   double px = qn;
-#ifdef NPY_ABLATE_INV_LOOP  // timing experiments only: wrong results
-  return (Int)(U > px);
-#endif
   while (U > px) {
     X++;
     bool over = false;
@@ -309,11 +283,7 @@ NPY_HD float f_log1p_small(float d) {
 }
 // log(1 + d) for any d > -1: the series above for |d| <= 0.35, the fp32 logarithm of 1 + d beyond (absolute error <= 5e-7 |log| + 2e-7:
 // callers that multiply it by c add ~1e-6 c to their guard, see binomial_btpe_fast)
-#ifndef NPY_BTPE_ANYD
-#define NPY_BTPE_ANYD 1       // 0: log1p arguments beyond 0.35 send the draw to the exact redo (round 2)
-#endif
 NPY_HD float f_log1p_any(float d) {
-  if (!NPY_BTPE_ANYD) return f_log1p_small(d);
   return fabsf(d) <= 0.35f ? f_log1p_small(d) : f_log(1.0f + d);
 }
 NPY_HD float f_stirling_true(float x) {       // Stirling's series itself, 1/(12x) - 1/(360x^3) + 1/(1260x^5) - 1/(1680x^7) + 1/(1188x^9): numpy's
@@ -343,9 +313,6 @@ NPY_HD float f_stirling(float x) {            // btpe_stirling in fp32: ~1/(12 x
 #define NPY_INV_GX 2.4e-6f
 #define NPY_INV_GS 1e-5f
 #endif
-#ifndef NPY_BTPE_LOGF
-#define NPY_BTPE_LOGF 1       // binomial_btpe_fast: the explicit-product acceptance test through the closed log form where that is accurate
-#endif
 #ifndef NPY_F_GUARD
 #define NPY_F_GUARD 2e-4f     // relative, on v vs f(y)/f(m): fp32 error of a product of <= 64 factors < 3e-5
 #endif
@@ -353,9 +320,6 @@ NPY_HD float f_stirling(float x) {            // btpe_stirling in fp32: ~1/(12 x
 // Inversion search in fp32.  Returns X >= 0 when every decision of the search is outside the guard, -1 otherwise.
 // Decisions of numpy's loop: U_x > px_x for x < X and U_X <= px_X, with U_{x+1} = U_x - px_x; the margins of the x < X
 // decisions are U_{x+1} >= U_X, so two checks at the end cover them all: U_X > G (for X > 0) and px_X - U_X > G.
-#ifndef NPY_INV_NOCAP
-#define NPY_INV_NOCAP 1      // 1: the search's bound is checked once, after the search; 0: in every step (round 2)
-#endif
 // Steps IT .. LAST of the fp32 search as explicitly nested ifs; returns the number of steps taken (= X).  The step number, 1/x and
 // (float)x are literals (a loop the compiler may choose not to unroll costs a conversion and a v_rcp_f32 per step: measured 3.4-3.7 s
 // against 3.0 s for the C3 launch); X as the ladder's return value rather than an assignment in every step measured 1 % faster.
@@ -380,9 +344,6 @@ NPY_HD int32_t binomial_inversion_fast(double U, Int n, double p, double lq) {
   float qn = f_exp(argf);
   float Uf = (float)U, px = qn;
   int32_t X = 0;
-#ifdef NPY_ABLATE_INV_LOOP  // timing experiments only: wrong results
-  return (int32_t)(Uf > px);
-#endif
   // fully unrolled: the step number is a compile-time constant, so 1/X and (float)X are literals and an iteration is five
   // full-rate fp32 instructions (no conversion, no v_rcp_f32); lock-stepped lanes share the trip count anyway.
   // numpy restarts when X exceeds bound = min(n, np + 10 sqrt(npq + 1)) >= min(n, 10): the first nine steps can never reach it, so
@@ -391,7 +352,6 @@ NPY_HD int32_t binomial_inversion_fast(double U, Int n, double p, double lq) {
   // cancellation costs at most (n + 1)/(n + 1 - x) ulps of the factor, i.e. something only for n < ~120 near the end of the support,
   // where it adds < 1e-5 to the absolute error of the running sum (NPY_INV_GS in the guard)
   const float a_s = (nf + 1.0f) * s;
-#if NPY_INV_NOCAP
   // The search may not pass numpy's bound (nor n): checked ONCE, after the search, not in every step.  Past x = n the factor is zero,
   // then negative, px stays (-)0 and the search runs on to its last step, where X > cap sends the draw to the exact path; it takes a U
   // above the whole fp32 CDF to get there (~1e-6 of the draws with n < 60, none otherwise).
@@ -408,38 +368,6 @@ NPY_HD int32_t binomial_inversion_fast(double U, Int n, double p, double lq) {
   const float G = (NPY_INV_G0 + (n < (Int)128 ? NPY_INV_GS : 0.0f)) + NPY_INV_GA * fabsf(argf) + NPY_INV_GX * (float)X;
   bool ok = (px - Uf > G) && (X == 0 || Uf > G) && X <= cap_end;
   return ok ? X : -1;
-#else    // round 2's form: the bound checked in every step (kept for A/B runs)
-  const int32_t cap9 = n < (Int)9 ? (int32_t)n : 9;
-#pragma unroll
-  for (int it = 1; it <= 9; it++) {
-    if (!(Uf > px) || it > cap9) break;
-    X = it;
-    Uf -= px;
-    px = px * __builtin_fmaf(a_s, 1.0f / (float)it, -s);
-  }
-  if (X == 9 && Uf > px) {
-    // stay strictly below numpy's bound (and below 60: longer searches are ~6 sigma events for n*p <= 30 and go to the exact path)
-    float npf = nf * pf;
-    float capf = npf + 10.0f * f_sqrt(npf * qf + 1.0f) - 1.5f;
-    capf = capf < nf ? capf : nf;
-    capf = capf < 60.0f ? capf : 60.0f;
-    // (steps 10 .. 60 stay unrolled with a per-lane ``break`` although every step is then one more level of nested control flow and
-    // the compiler keeps the deeper levels' saved exec masks in VGPR lanes -- two v_writelane per step going in, two v_readlane + s_or
-    // per level coming out: measured at C3, a rolled loop with one exec mask and v_rcp_f32 for 1/x takes 3.37 s against 3.00 s, an
-    // unrolled search without nesting -- stopped lanes keep X, U, px through selects, a wave-uniform branch leaves it -- 3.16 s)
-    int32_t cap = (int32_t)capf;
-#pragma unroll
-    for (int it = 10; it <= 60; it++) {
-      if (!(Uf > px) || it > cap) break;
-      X = it;
-      Uf -= px;
-      px = px * __builtin_fmaf(a_s, 1.0f / (float)it, -s);
-    }
-  }
-  const float G = (NPY_INV_G0 + (n < (Int)128 ? NPY_INV_GS : 0.0f)) + NPY_INV_GA * fabsf(argf) + NPY_INV_GX * (float)X;
-  bool ok = (px - Uf > G) && (X == 0 || Uf > G);   // also false when the search stopped at a cap
-  return ok ? X : -1;
-#endif
 }
 
 // BTPE's explicit evaluation of f(y)/f(m) against v, in fp32.  +1: v <= F (numpy breaks: accept), 0: v > F (numpy continues:
@@ -484,7 +412,7 @@ NPY_HD int btpe_explicit_fast(double v, Int n, Int m, Int y, double r, double q)
 // caller calls again for the same (n, r) and the draw goes on where it stopped, since the set-up depends on (n, r) only and the
 // attempts are independent (the lock-step tile kernel makes one attempt per bin step and lets the lane retry in the next).
 template <typename Int, bool LAZY = false, typename Gen>
-NPY_HD Int binomial_btpe_fast(Gen &g, Int n, double r, int cap NPY_ST_PARAM) {   // r = p <= 0.5
+NPY_HD Int binomial_btpe_fast(Gen &g, Int n, double r, int cap) {   // r = p <= 0.5
   const double q = 1.0 - r;
   const double fm = (double)n * r + r;
   const double md = floor(fm);
@@ -514,13 +442,11 @@ NPY_HD Int binomial_btpe_fast(Gen &g, Int n, double r, int cap NPY_ST_PARAM) {  
   const double p3 = p2 + c * rlaml;
   const double p4 = p3 + c * rlamr;
   const double gu = 1e-11 * p4;                                       // set-up values are within ~1e-15 (relative) of numpy's
-  NPY_ST(0);
   const int max_att = cap > 0 ? cap : g.max_attempts();
   for (int attempt = 0; attempt < max_att; attempt++) {
     const bool tk = (Int)attempt <= n;   // always true (see NPY_KEEP)
     double u = pcg64_next_double(g) * p4;
     double v = pcg64_next_double(g);
-    NPY_ST(1);
     if (fabs(u - p1) < gu || fabs(u - p2) < gu || fabs(u - p3) < gu) return -1;
     if (u <= p1) {                       // triangular region: accepted at once
       double x = xm - p1 * v + u;
@@ -547,7 +473,6 @@ NPY_HD Int binomial_btpe_fast(Gen &g, Int n, double r, int cap NPY_ST_PARAM) {  
       gx = (2e-6 * fabs((double)lv) + 4e-7) * rl + 1e-10 * (fabs(x) + 1.0);
       v = left ? v * (u - p2) * laml : v * (u - p3) * lamr;
     }
-    NPY_ST(2);
     double fx = floor(x);
     if (x - fx < gx || fx + 1.0 - x < gx) return -1;
     if (fx < 0.0 || fx > (double)n) {
@@ -556,7 +481,6 @@ NPY_HD Int binomial_btpe_fast(Gen &g, Int n, double r, int cap NPY_ST_PARAM) {  
     }
     Int y = (Int)fx;
     Int k = y > m ? y - m : m - y;
-    NPY_ST(3);
     // numpy accepts through the explicit product F = f(y)/f(m) (k factors) when k <= 20 or k >= nrq/2 - 1, and through the squeeze +
     // Stirling-corrected log form otherwise.  The log form IS log F (up to the truncation of the Stirling series, < 1e-9 for arguments
     // >= 8), so the explicit case can take it too -- no loop of up to 64 factors that every lane of a wave waits for: v <= F iff
@@ -580,7 +504,6 @@ NPY_HD Int binomial_btpe_fast(Gen &g, Int n, double r, int cap NPY_ST_PARAM) {  
       float t = -(kf * kf) * 0.5f * rnrq;
       float gs = 1e-5f * (1.0f + fabsf(A)) + 6e-6f * (fabsf(t) + rho);
       float lo_ = t - rho, hi_ = t + rho;
-      NPY_ST(5);
       if (A < lo_ - gs) return y;
       if (A > hi_ + gs) continue;
       if (!expl && (A < lo_ + gs || A > hi_ - gs)) return -1;      // numpy's own decision changes at lo / hi: too close to tell
@@ -594,14 +517,13 @@ NPY_HD Int binomial_btpe_fast(Gen &g, Int n, double r, int cap NPY_ST_PARAM) {  
     const bool small_d = !(fabsf(d1) > 0.35f || fabsf(d2) > 0.35f || fabsf(d3) > 0.35f);
     const bool sane_d = d1 > -0.9f && d2 > -0.9f && d3 > -0.9f && d1 < 8.0f && d2 < 8.0f && d3 < 8.0f;   // the fp32 logarithm's range of use
     const Int amin = (y < m ? y : m) < (n - (y > m ? y : m)) ? (y < m ? y : m) : (n - (y > m ? y : m));
-    if (expl && !(NPY_BTPE_LOGF && small_d && amin >= (Int)7)) {
+    if (expl && !(small_d && amin >= (Int)7)) {
       int dec = btpe_explicit_fast<Int>(v, n, m, y, r, NPY_KEEP(tk, q, r));
-      NPY_ST(4);
       if (dec < 0) return -1;
       if (dec == 0) continue;
       return y;
     }
-    if (!expl && !(NPY_BTPE_ANYD ? sane_d : small_d)) return -1;
+    if (!expl && !sane_d) return -1;
     // (a bin with n r of 30-100 and a candidate 21+ away from the mode has |d| > 0.35: the fp32 logarithm then, with its absolute
     // error in the guard -- these were 80 % of the draws that went to the exact redo)
     const float c1 = (float)xm, c2 = (float)(n - m) + 0.5f, c3 = (float)(y - m);
@@ -616,7 +538,6 @@ NPY_HD Int binomial_btpe_fast(Gen &g, Int n, double r, int cap NPY_ST_PARAM) {  
                                        : f_stirling(mf1) + f_stirling(zf) + f_stirling(yf1) + f_stirling(wf));
     float gb = 4e-6f * (fabsf(T1) + fabsf(T2) + fabsf(T3)) + 1e-5f * (1.0f + fabsf(A));
     if (!small_d) gb += 1e-6f * ((fabsf(d1) > 0.35f ? c1 : 0.0f) + (fabsf(d2) > 0.35f ? c2 : 0.0f) + (fabsf(d3) > 0.35f ? fabsf(c3) : 0.0f));
-    NPY_ST(6);
     if (A > bound + gb) continue;
     if (A < bound - gb) return y;
     return -1;
@@ -1148,18 +1069,10 @@ NPY_HD Int binomial_pre(Gen &g, double pk, double lq, Int n) {
     if (FAST && xf < 0) NPY_NOTE_FALLBACK(0);
     X = xf >= 0 ? (Int)xf : binomial_inversion_pre<Int>(g, n, p, lq, U);
   } else {
-#ifdef NPY_ABLATE_BTPE  // timing experiments only: wrong results
-    X = (Int)((double)n * p);
-#else
     if (FAST) {
       g.reserve(34);                   // the fast path gives up after 16 attempts (2 uniforms each)
       typename Gen::Mark saved = g.mark();
-#if defined(BOOT_STAMPS) && defined(__HIPCC__)
-      uint64_t npy_dummy[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-      X = binomial_btpe_fast<Int, LAZY>(g, n, p, 0, npy_dummy);
-#else
       X = binomial_btpe_fast<Int, LAZY>(g, n, p, 0);
-#endif
       if (X < 0) {
         NPY_NOTE_FALLBACK(1);
         g.rewind(saved);
@@ -1168,7 +1081,6 @@ NPY_HD Int binomial_pre(Gen &g, double pk, double lq, Int n) {
     } else {
       X = binomial_btpe<Int>(g, n, p);
     }
-#endif
   }
   return flip ? n - X : X;
 }
@@ -1192,12 +1104,7 @@ NPY_HD Int binomial_pre_capped(Gen &g, double pk, double lq, Int n, int cap, boo
   } else {
     g.reserve(34);
     typename Gen::Mark saved = g.mark();
-#if defined(BOOT_STAMPS) && defined(__HIPCC__)
-    uint64_t npy_dummy[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    X = binomial_btpe_fast<Int, false>(g, n, p, cap, npy_dummy);
-#else
     X = binomial_btpe_fast<Int, false>(g, n, p, cap);
-#endif
     if (X == (Int)-2) {
       pending = true;
       return 0;

@@ -9,6 +9,7 @@ import ctypes
 import os
 
 from ctypes import c_void_p
+from types import SimpleNamespace
 
 import numpy as np
 
@@ -533,19 +534,11 @@ def pcg64_jump_table(seed=5):
     return _JUMP_CACHE[seed]
 
 
-REPLAY_RING = os.environ.get('MM_REPLAY_RING', '0') != '0'       # tile kernel: uniforms produced ahead into an LDS ring (mm_debug_replay_ring);
-                            # OFF: measured slower at every top-up rate (C3: 3.61 / 3.71 / 3.80 s with 2 / 3 / 4 per step against 3.53 s)
 _STREAM_CACHE = {}
-STREAM_TABLE = os.environ.get('MM_STREAM_TABLE', '0') != '0'     # tile kernel: uniforms from the precomputed stream table;
-                            # OFF: measured slower (C3: 4.12-4.16 s against 3.53 s -- a wave's lanes sit at 64 different places of the
-                            # table, and the gather's latency is exposed in every attempt; profiles/README.md)
-STREAM_PER_STEP = 3.0       # table length = this x (longest tile chain's steps) x replicates: a draw takes 1 (inversion) or 2 per
-                            # BTPE attempt (~2.4 on average) uniforms; a chain past the table flags the launch, which is redone
-
-
 def pcg64_stream_table(seed, n):
     """Device table of the first ``n`` uniforms of Generator(PCG64(seed)) (mm_pcg64_stream); cached and grown on demand -- its
-    content depends on nothing but the seed."""
+    content depends on nothing but the seed.  (No kernel reads it: tile lanes that took their uniforms from it instead of stepping
+    PCG64 measured 4.12-4.16 s against 3.53 s at C3, a wave's lanes sit at 64 different places of the table.)"""
     torch = _torch()
     t = _STREAM_CACHE.get(seed)
     if t is None or t.numel() < n:
@@ -568,6 +561,67 @@ def pcg64_state(seed=5):
     st = np.random.PCG64(seed).state["state"]
     m = (1 << 64) - 1
     return (ctypes.c_uint64 * 4)(st["state"] >> 64, st["state"] & m, st["inc"] >> 64, st["inc"] & m)
+
+
+def _replay_order(code, mu, n_cells):
+    """Replay order of ONE chain's bins computed on the host, with the arithmetic of k_bins_order / k_bins_order2d: ``code``
+    ascending (bootstrap.py:62-67), pk = pix / remaining_p, log(1 - p) after the p > 0.5 flip.  Returns (order, pk, lq)."""
+    o = np.argsort(code, kind="stable")
+    if len(o) > 1 and (np.diff(code[o]) == 0).any():
+        raise NotImplementedError("two bins of one pair collided in the replay hash (np.unique would merge them)")
+    pix = mu[o].astype(np.float64) / float(n_cells)
+    rem = np.empty_like(pix)
+    acc = 1.0
+    for k in range(len(pix)):      # sequential rounding, exactly like numpy's remaining_p
+        rem[k] = acc
+        acc -= pix[k]
+    pk = pix / rem
+    peff = np.where(pk <= 0.5, pk, 1.0 - pk)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        lq = np.log(1.0 - peff)
+    return o, pk, lq
+
+
+def _write_chain_operands(recbuf, ops, slot, tile_ptr, vals):
+    """Operands of ONE chain, per bin the values ``vals`` (pk, lq, ...), written where the kernels read them: a CHAIN_SLOT slot = 8-double
+    records in ``recbuf`` (the slot's low bits number the first record), any other slot = its lane of the tile's rows in the planes ``ops``."""
+    if slot & CHAIN_SLOT:
+        rec = np.zeros((len(vals[0]), 8))
+        for i, x in enumerate(vals):
+            rec[:, i] = x
+        r0_ = (slot & (CHAIN_SLOT - 1)) * 8
+        recbuf[r0_:r0_ + rec.size] = dev(rec.reshape(-1))
+        return
+    idx = dev((int(tile_ptr[slot >> 6]) + np.arange(len(vals[0]), dtype=np.int64)) * 64 + (slot & 63))
+    for arr, x in zip(ops, vals):
+        arr[idx] = dev(x)
+
+
+def _per_slot(n_slots, slot_of, vals, fill, dtype):
+    """[n_slots] array with vals[i] in slot slot_of[i] and ``fill`` in the unused slots."""
+    a = np.full(n_slots, fill, dtype=dtype)
+    a[slot_of] = vals
+    return a
+
+
+def _plan_tiles(K, order, slot_of, n_tiles, n_chains, grp_ncells, grp_q, ng):
+    """Slot tables of a tile launch (1D and 2D): chain order[i] (of ``n_chains`` in all, group = chain % ng) runs in slot
+    slot_of[i] = 64 * tile + lane.  tile_ptr: tile t owns operand rows [tile_ptr[t], tile_ptr[t + 1]), as many as its longest chain."""
+    t = SimpleNamespace()
+    t.pair_slot = _per_slot(n_chains, order, slot_of, -1, np.int64)
+    t.slot_pair = _per_slot(n_tiles * 64, slot_of, order, -1, np.int64)
+    t.slot_K = _per_slot(n_tiles * 64, slot_of, K[order], 0, np.int32)
+    t.tile_k = t.slot_K.reshape(n_tiles, 64).max(axis=1) if n_tiles else np.zeros(0, dtype=np.int32)
+    t.tile_ptr = np.concatenate([[0], np.cumsum(t.tile_k.astype(np.int64))]).astype(np.int64)
+    t.nobs = _per_slot(n_tiles * 64, slot_of, grp_ncells[order % ng], 0.0, np.float64)
+    t.omq = _per_slot(n_tiles * 64, slot_of, 1.0 - grp_q[order % ng], 0.0, np.float64)
+    return t
+
+
+def _plan_records(K, rec_pairs):
+    """Chains whose operands are 8-double records, one behind the other: (bins of each, first record of each + the total)."""
+    rec_K = K[rec_pairs].astype(np.int64)
+    return rec_K, np.concatenate([[0], np.cumsum(rec_K)]).astype(np.int64)
 
 
 class Bootstrap1D:
@@ -626,33 +680,11 @@ class Bootstrap1D:
     def _order_on_host(self, p, r1, r0, slot, tile_ptr, ops):
         """Replay order + bootstrap operands of ONE pair computed on the host (same arithmetic as k_bins_order:
         code = count*r1 + r0*approx_sf ascending; pk = pix/remaining_p; log(1-p)) and written into its tile lane."""
-        torch = _torch()
         bi, xi, mu = self.bins_of_pair(p)
         code = xi.astype(np.float64) * r1 + r0 * self.sf_table[bi]
-        o = np.argsort(code, kind="stable")
-        if len(o) > 1 and (np.diff(code[o]) == 0).any():
-            raise NotImplementedError("two bins of one pair collided in the replay hash (np.unique would merge them)")
-        bi, xi, mu = bi[o], xi[o].astype(np.float64), mu[o].astype(np.float64)
-        pix = mu / float(self.blocks.grp_ncells[p % self.ng])
-        rem = np.empty_like(pix)
-        acc = 1.0
-        for k in range(len(pix)):      # sequential rounding, exactly like numpy's remaining_p
-            rem[k] = acc
-            acc -= pix[k]
-        pk = pix / rem
-        peff = np.where(pk <= 0.5, pk, 1.0 - pk)
-        with np.errstate(divide="ignore", invalid="ignore"):
-            lq = np.log(1.0 - peff)
-        sf = self.sf_table[bi]
-        if slot & CHAIN_SLOT:      # 8-double records of the chain kernel, addressed from the start of ops[0]'s allocation
-            rec = np.zeros((len(pk), 8))
-            rec[:, 0], rec[:, 1], rec[:, 2], rec[:, 3], rec[:, 4] = pk, lq, xi, 1.0 / sf, 1.0 / (sf * sf)
-            r0_ = (slot & (CHAIN_SLOT - 1)) * 8
-            self._opsbuf[r0_:r0_ + rec.size] = dev(rec.reshape(-1))
-            return
-        idx = dev((int(tile_ptr[slot >> 6]) + np.arange(len(pk), dtype=np.int64)) * 64 + (slot & 63))
-        for arr, vals in zip(ops, (pk, lq, xi, 1.0 / sf, 1.0 / (sf * sf))):
-            arr[idx] = dev(vals)
+        o, pk, lq = _replay_order(code, mu, self.blocks.grp_ncells[p % self.ng])
+        sf = self.sf_table[bi[o]]      # (records lie behind the operand planes in the one allocation, numbered from its start)
+        _write_chain_operands(self._opsbuf, ops, slot, tile_ptr, (pk, lq, xi[o].astype(np.float64), 1.0 / sf, 1.0 / (sf * sf)))
 
     def weights_of(self, p):
         """Test helper (after run(dump_weights=True)): the int32 multinomial weights [K][B] of pair p, whichever kernel drew them."""
@@ -679,31 +711,47 @@ class Bootstrap1D:
         ``first_pair`` are left untouched (used by the strict replay driver).  ``fill_keys`` [pair] int64: keys of the device
         refill streams (fill_mode 0; default: the row number).  Returns n_invalid
         [n_pairs - first_pair][2] (host): invalid (mean, res_var) replicates per row, -1 = no valid one."""
-        torch = _torch()
-        s = _stream()
-        ng, B, ld = self.ng, self.B, self.ld
         active = (~np.asarray(skip, dtype=bool)) & (self.K >= 2)
         active[:first_pair] = False
+        c = self._choose_kernels(active, fast, target_waves)
+        t = self._lay_out_operands(c, dump_weights)
+        status, ordered = self._order_bins(c, t, r1, r0)
+        launched = self._launch(c, t, fast, mean_only, fill_seed, pcg_seed, dump_weights)
+        st = int(status.item())
+        del ordered, launched      # NB: every device operand must stay referenced until after the call that reads it
+        if st & 2 or st & 4:
+            raise RuntimeError(f"mm_bins_order inconsistency (status {st})")
+        if st & 8:
+            raise NotImplementedError("two bins of one pair collided in the replay hash (np.unique would merge them)")
+        self.raw_mean = self.ym.clone() if dump_weights else None
+        self.raw_var = self.yv.clone() if dump_weights else None
+        n_inv = self._fill_log(mv_fit, fill_mode, fill_seed, first_pair, fill_keys)
+        self.active = active
+        return n_inv
+
+    def _choose_kernels(self, active, fast, target_waves):
+        """Which kernel runs which chain: the longest ones one per wave (mm_boot1d_chain), the others one per lane of a tile
+        (mm_boot1d_replay / _free / _fast) or of an async wave (mm_boot1d_async); then the tiles' packing and dispatch order, and
+        the chains the packer left alone in their tile (they run as chains inside the tile launch)."""
         act = np.flatnonzero(active)
-        order_all = act[np.argsort(-self.K[act], kind="stable")]
-        # the longest chains run one per wave (mm_boot1d_chain), the others one per lane of a tile (mm_boot1d_replay)
+        c = SimpleNamespace()
+        order_all = c.order_all = act[np.argsort(-self.K[act], kind="stable")]
         n_chain = 0 if (fast or not CHAIN_MIN_K) else int(np.searchsorted(-self.K[order_all], -CHAIN_MIN_K, side="right"))
         if not fast and target_waves is None and 0 < len(order_all) <= CHAIN_ALL_MAX:
             n_chain = len(order_all)
-        use_async = TILE_MODE == "async" and not fast and target_waves is None
-        if use_async and ASYNC_CHAIN_MIN_K:
+        c.use_async = TILE_MODE == "async" and not fast and target_waves is None
+        if c.use_async and ASYNC_CHAIN_MIN_K:
             n_chain = max(n_chain, int(np.searchsorted(-self.K[order_all], -ASYNC_CHAIN_MIN_K, side="right")))
         chain_pairs, order = order_all[:n_chain], order_all[n_chain:]
-        async_pairs = order if use_async else order[:0]           # K descending: the 64 chains of a wave have similar lengths
-        if use_async:
+        c.async_pairs = order if c.use_async else order[:0]       # K descending: the 64 chains of a wave have similar lengths
+        if c.use_async:
             order = order[:0]
-        n_async = len(async_pairs)
         # replay: cost-model lane packing (one lane = one sequential chain); fast: dense 64-wide tiles (one WAVE per pair)
         slot_of, n_tiles = pack_lanes(self.K[order], PACK_WAVES if target_waves is None else target_waves, dense=fast)
         if not fast:
             slot_of = pair_tiles(slot_of, n_tiles, self.K[order])
-        n_launch = n_chain                    # chains of the separate mm_boot1d_chain launch (CHAIN_MIN_K / ASYNC_CHAIN_MIN_K rules)
-        tile_chain = None
+        c.n_launch = n_chain                  # chains of the separate mm_boot1d_chain launch (CHAIN_MIN_K / ASYNC_CHAIN_MIN_K rules)
+        c.tile_chain = None
         if CHAIN_LONE and not fast and n_tiles:
             # A chain the packer left alone in its tile takes a whole wave either way: that wave runs it in the wave-uniform
             # form (chain_body inside the tile kernel), at the tile's place in the dispatch order -- the packing and pairing
@@ -711,155 +759,141 @@ class Bootstrap1D:
             tile = slot_of // 64
             lone = np.bincount(tile, minlength=n_tiles)[tile] == 1
             if lone.any():
-                tile_chain = np.full(n_tiles, -1, dtype=np.int32)
-                tile_chain[tile[lone]] = n_chain + np.arange(int(lone.sum()))
+                c.tile_chain = np.full(n_tiles, -1, dtype=np.int32)
+                c.tile_chain[tile[lone]] = n_chain + np.arange(int(lone.sum()))
                 chain_pairs = np.concatenate([chain_pairs, order[lone]])
-                n_chain = len(chain_pairs)
                 order, slot_of = order[~lone], slot_of[~lone]
-        n_act = len(order)
-        self.n_tiles, self.n_chain, self.n_async, self.n_chain_launch = n_tiles, n_chain, n_async, n_launch
-        pair_slot = np.full(self.n_pairs, -1, dtype=np.int64)
-        pair_slot[order] = slot_of
-        slot_pair = np.full(n_tiles * 64, -1, dtype=np.int64)
-        slot_pair[slot_of] = order
-        slot_K = np.zeros(n_tiles * 64, dtype=np.int32)
-        slot_K[slot_of] = self.K[order]
-        tile_k = slot_K.reshape(n_tiles, 64).max(axis=1) if n_tiles else np.zeros(0, dtype=np.int32)
-        tile_ptr = np.concatenate([[0], np.cumsum(tile_k.astype(np.int64))]).astype(np.int64)
-        rows = int(tile_ptr[-1])
+        c.chain_pairs, c.order, c.slot_of, c.n_tiles = chain_pairs, order, slot_of, n_tiles
+        c.use_free = TILE_FREE and not fast and not c.use_async and n_tiles > 0 and len(order) > 0
+        self.n_tiles, self.n_chain, self.n_async, self.n_chain_launch = n_tiles, len(chain_pairs), len(c.async_pairs), c.n_launch
+        self.chain_pairs, self.async_pairs = chain_pairs, c.async_pairs
         self.draws_per_replicate = int(np.maximum(self.K[order_all] - 1, 0).sum())
-        # one allocation: five [rows][64] operand planes of the tiles, then the chains' 8-double records
-        plane = max(1, rows) * 64
-        use_free = TILE_FREE and not fast and not use_async and not REPLAY_RING and not STREAM_TABLE and n_tiles > 0 and len(order) > 0
-        if use_free:
-            plane = 64                                              # no operand rows: every chain of the launch reads records
-        rec_pairs = np.concatenate([chain_pairs, async_pairs, order if use_free else order[:0]])      # chains whose operands are 8-double records
-        rec_K = self.K[rec_pairs].astype(np.int64)
-        rec_base = np.concatenate([[0], np.cumsum(rec_K)]).astype(np.int64)
-        ch_K, ch_base = rec_K[:n_chain], rec_base[:n_chain + 1]
-        self._opsbuf = empty((5 * plane + 8 * max(1, int(rec_base[-1])),), torch.float64)
-        ops = [self._opsbuf[i * plane:(i + 1) * plane] for i in range(5)]
-        pair_slot[rec_pairs] = CHAIN_SLOT | (5 * plane // 8 + rec_base[:-1])
+        return c
+
+    def _lay_out_operands(self, c, dump_weights):
+        """Slot tables of the tile launch and ONE operand allocation: five [rows][64] planes of the tiles, then the 8-double
+        records of every chain that reads records (chain kernel, async kernel, free-running tiles)."""
+        torch = _torch()
+        n_chain, n_async, n_tiles = self.n_chain, self.n_async, c.n_tiles
+        t = _plan_tiles(self.K, c.order, c.slot_of, n_tiles, self.n_pairs, self.blocks.grp_ncells, self.grp_q, self.ng)
+        t.plane = 64 if c.use_free else max(1, int(t.tile_ptr[-1])) * 64       # free-running tiles have no operand rows
+        rec_pairs = np.concatenate([c.chain_pairs, c.async_pairs, c.order if c.use_free else c.order[:0]])
+        t.rec_K, t.rec_base = _plan_records(self.K, rec_pairs)
+        self._opsbuf = empty((5 * t.plane + 8 * max(1, int(t.rec_base[-1])),), torch.float64)
+        t.ops = [self._opsbuf[i * t.plane:(i + 1) * t.plane] for i in range(5)]
+        t.d_recs = c_void_p(self._opsbuf.data_ptr() + 5 * t.plane * 8)
+        self.tile_slot = t.pair_slot.copy()                                 # (tile, lane) slot of the chains that run as lanes of a tile
+        t.pair_slot[rec_pairs] = CHAIN_SLOT | (5 * t.plane // 8 + t.rec_base[:-1])
         self.chain_index = np.full(self.n_pairs, -1, dtype=np.int64)
-        self.chain_index[chain_pairs] = np.arange(n_chain)
+        self.chain_index[c.chain_pairs] = np.arange(n_chain)
         self.async_index = np.full(self.n_pairs, -1, dtype=np.int64)
-        self.async_index[async_pairs] = np.arange(n_async)
-        self.chain_pairs, self.async_pairs = chain_pairs, async_pairs
-        self.tile_slot = np.full(self.n_pairs, -1, dtype=np.int64)          # (tile, lane) slot of the chains that run as lanes of a tile
-        self.tile_slot[order] = slot_of
-        slot_rec = None
-        if use_free:
-            slot_rec = np.full(n_tiles * 64, -1, dtype=np.int64)
-            slot_rec[slot_of] = rec_base[n_chain + n_async:-1]
-        d_pair_slot, d_tile_ptr = dev(pair_slot), dev(tile_ptr)
+        self.async_index[c.async_pairs] = np.arange(n_async)
+        t.slot_rec = _per_slot(n_tiles * 64, c.slot_of, t.rec_base[n_chain + n_async:-1], -1, np.int64) if c.use_free else None
+        self.kmax_dump = int(t.tile_k.max()) if (dump_weights and n_tiles) else 0
+        self.slot_pair, self.slot_K, self.pair_slot, self.tile_ptr = t.slot_pair, t.slot_K, t.pair_slot, t.tile_ptr
+        self._ops, self._nobs = t.ops, t.nobs      # kept for diagnostics (tools/replay_balance.py)
+        return t
+
+    def _order_bins(self, c, t, r1, r0):
+        """mm_bins_order for every chain: its bins in replay order, its operands written to its tile lane or its records.
+        Returns (device status word, the device operands the launches read)."""
+        torch, s = _torch(), _stream()
+        K_all = self.K[c.order_all]
+        d_pair_slot, d_tile_ptr = dev(t.pair_slot), dev(t.tile_ptr)
         status = zeros((1,), torch.int32)
         d_r1, d_r0 = dev(np.asarray(r1, dtype=np.float64)), dev(np.asarray(r0, dtype=np.float64))
         d_sf, d_nc = dev(self.sf_table), dev(self.blocks.grp_ncells.astype(np.float64))
-        small = order_all[self.K[order_all] <= ORDER_SMALL_CAP]
-        big = order_all[(self.K[order_all] > ORDER_SMALL_CAP) & (self.K[order_all] <= ORDER_BIG_CAP)]
-        huge = order_all[self.K[order_all] > ORDER_BIG_CAP]
+        keep = [d_pair_slot, d_tile_ptr, d_r1, d_r0, d_sf, d_nc]
+        small = c.order_all[K_all <= ORDER_SMALL_CAP]
+        big = c.order_all[(K_all > ORDER_SMALL_CAP) & (K_all <= ORDER_BIG_CAP)]
+        huge = c.order_all[K_all > ORDER_BIG_CAP]
         for lst, is_big in ((small, 0), (big, 1)):
             if len(lst):
                 d_lst = dev(lst)
+                keep.append(d_lst)
                 _lib.call("mm_bins_order", P(self.tab), P(self.d_tab_ptr), P(self.d_xcap), P(self.d_K), P(d_lst), len(lst),
-                          is_big, ng, self.n_bins, P(d_sf), P(d_r1), P(d_r0), P(d_pair_slot), P(d_tile_ptr), P(d_nc),
-                          *[P(o) for o in ops], P(status), s)
+                          is_big, self.ng, self.n_bins, P(d_sf), P(d_r1), P(d_r0), P(d_pair_slot), P(d_tile_ptr), P(d_nc),
+                          *[P(o) for o in t.ops], P(status), s)
         for p in huge:   # more bins than the in-LDS sort holds (very highly expressed genes): order them on the host
-            self._order_on_host(int(p), float(r1[p]), float(r0[p]), int(pair_slot[p]), tile_ptr, ops)
-        nobs = np.zeros(n_tiles * 64, dtype=np.float64)
-        nobs[slot_of] = self.blocks.grp_ncells[order % ng]
-        omq = np.zeros(n_tiles * 64, dtype=np.float64)
-        omq[slot_of] = 1.0 - self.grp_q[order % ng]
-        kmax_dump = int(tile_k.max()) if (dump_weights and n_tiles) else 0
+            self._order_on_host(int(p), float(r1[p]), float(r0[p]), int(t.pair_slot[p]), t.tile_ptr, t.ops)
+        t.d_tile_ptr = d_tile_ptr
+        return status, keep
+
+    def _launch(self, c, t, fast, mean_only, fill_seed, pcg_seed, dump_weights):
+        """The chain kernel on the side stream, beside it on the launch stream the async and the tile kernel.  Returns their device operands."""
+        torch, s = _torch(), _stream()
+        ng, B, ld = self.ng, self.B, self.ld
+        n_chain, n_async, n_tiles, n_launch, kmax_dump = self.n_chain, self.n_async, c.n_tiles, c.n_launch, self.kmax_dump
+        chain_pairs, async_pairs = c.chain_pairs, c.async_pairs
         self.w_dump = zeros((n_tiles * 64, kmax_dump, B), torch.int32) if dump_weights else None
-        self.kmax_dump = kmax_dump
-        self.slot_pair, self.slot_K, self.pair_slot, self.tile_ptr = slot_pair, slot_K, pair_slot, tile_ptr
-        self._ops, self._nobs = ops, nobs          # kept for diagnostics (tools/replay_balance.py)
-        d_slot_K, d_nobs, d_omq, d_slot_pair = dev(slot_K), dev(nobs), dev(omq), dev(slot_pair)
+        d_slot_K, d_nobs, d_omq, d_slot_pair = dev(t.slot_K), dev(t.nobs), dev(t.omq), dev(t.slot_pair)
+        keep = [d_slot_K, d_nobs, d_omq, d_slot_pair]
         self.w_dump_chain = None
         chain_tiles = None
         if n_chain:
+            ch_K = t.rec_K[:n_chain]
             kd = int(ch_K.max()) if dump_weights else 0
             self.w_dump_chain = zeros((n_chain, kd, B), torch.int32) if dump_weights else None
-            d_chb, d_chK = dev(ch_base[:-1]), dev(ch_K.astype(np.int32))
+            d_chb, d_chK = dev(t.rec_base[:n_chain]), dev(ch_K.astype(np.int32))
             d_chn, d_cho = dev(self.blocks.grp_ncells[chain_pairs % ng].astype(np.float64)), dev(1.0 - self.grp_q[chain_pairs % ng])
             d_chr = dev(chain_pairs.astype(np.int64))
-            d_recs = c_void_p(self._opsbuf.data_ptr() + 5 * plane * 8)
-            if tile_chain is not None:          # chains that run as waves of the tile kernel's own launch
-                d_tc = dev(tile_chain)
-                chain_tiles = _lib.ChainTiles(P(d_tc), d_recs, P(d_chb), P(d_chK), P(d_chn), P(d_cho), P(d_chr), P(pcg64_jump_table(pcg_seed)),
+            keep += [d_chb, d_chK, d_chn, d_cho, d_chr]
+            if c.tile_chain is not None:        # chains that run as waves of the tile kernel's own launch
+                d_tc = dev(c.tile_chain)
+                chain_tiles = _lib.ChainTiles(P(d_tc), t.d_recs, P(d_chb), P(d_chK), P(d_chn), P(d_cho), P(d_chr), P(pcg64_jump_table(pcg_seed)),
                                               P(self.w_dump_chain), kd)
+                keep += [d_tc, chain_tiles]
         if n_launch:
             # the chain kernel goes out first, on its own stream, and runs beside the tile kernel; the launch stream waits for
             # it before the fill / log pass
             side, main = side_stream(), torch.cuda.current_stream()
             side.wait_stream(main)
-            _lib.call("mm_boot1d_chain", d_recs, P(d_chb), P(d_chK), P(d_chn), P(d_cho), P(d_chr),
+            _lib.call("mm_boot1d_chain", t.d_recs, P(d_chb), P(d_chK), P(d_chn), P(d_cho), P(d_chr),
                       n_launch, P(pcg64_jump_table(pcg_seed)), pcg64_state(pcg_seed), B, int(mean_only), ld, P(self.ym), P(self.yv),
                       P(self.w_dump_chain), kd, c_void_p(side.cuda_stream))
         self.w_dump_async = None
         if n_async:
-            ka = int(rec_K[n_chain:].max()) if dump_weights else 0
+            rec_K, rec_base = t.rec_K[n_chain:n_chain + n_async], t.rec_base[n_chain:n_chain + n_async]
+            ka = int(rec_K.max()) if dump_weights else 0
             # slot = 64 * wave + lane; a wave takes ASYNC_LANES consecutive chains of the K-descending list, its other lanes idle
             L = max(1, min(64, int(ASYNC_LANES)))
             idx = np.arange(n_async)
             a_slot = (idx // L) * 64 + idx % L
             n_slots = int(a_slot[-1]) + 1
             self.async_slot = a_slot
-
-            def spread(vals, dtype):
-                out = np.zeros(n_slots, dtype=dtype)
-                out[a_slot] = vals
-                return dev(out)
-
             self.w_dump_async = zeros((n_slots, ka, B), torch.int32) if dump_weights else None
-            d_ab, d_aK = spread(rec_base[n_chain:-1], np.int64), spread(rec_K[n_chain:], np.int32)
-            d_an, d_ao = spread(self.blocks.grp_ncells[async_pairs % ng], np.float64), spread(1.0 - self.grp_q[async_pairs % ng], np.float64)
-            d_ar = spread(async_pairs, np.int64)
-            _lib.call("mm_boot1d_async", c_void_p(self._opsbuf.data_ptr() + 5 * plane * 8), P(d_ab), P(d_aK), P(d_an), P(d_ao), P(d_ar), n_slots,
+            d_ab, d_aK, d_an, d_ao, d_ar = [dev(_per_slot(n_slots, a_slot, vals, 0, dtype)) for vals, dtype in (
+                (rec_base, np.int64), (rec_K, np.int32), (self.blocks.grp_ncells[async_pairs % ng], np.float64),
+                (1.0 - self.grp_q[async_pairs % ng], np.float64), (async_pairs, np.int64))]
+            keep += [d_ab, d_aK, d_an, d_ao, d_ar]
+            _lib.call("mm_boot1d_async", t.d_recs, P(d_ab), P(d_aK), P(d_an), P(d_ao), P(d_ar), n_slots,
                       pcg64_state(pcg_seed), B, int(mean_only), ld, P(self.ym), P(self.yv), P(self.w_dump_async), ka, s)
+        chains = ctypes.byref(chain_tiles) if chain_tiles is not None else None
         if n_tiles and fast:
-            _lib.call("mm_boot1d_fast", *[P(o) for o in ops], P(d_tile_ptr), n_tiles * 64, P(d_slot_K), P(d_nobs), P(d_omq), P(d_slot_pair),
+            _lib.call("mm_boot1d_fast", *[P(o) for o in t.ops], P(t.d_tile_ptr), n_tiles * 64, P(d_slot_K), P(d_nobs), P(d_omq), P(d_slot_pair),
                       int(fill_seed) & ((1 << 64) - 1), B, int(mean_only), ld, P(self.ym), P(self.yv), s)
-        elif n_tiles and use_free:
-            tab_over = None
-            d_slot_rec = dev(slot_rec)
-            _lib.call("mm_boot1d_free", c_void_p(self._opsbuf.data_ptr() + 5 * plane * 8), P(d_slot_rec), n_tiles, P(d_slot_K), P(d_nobs), P(d_omq),
-                      P(d_slot_pair), pcg64_state(pcg_seed), B, int(mean_only), ld, P(self.ym), P(self.yv), P(self.w_dump), kmax_dump,
-                      ctypes.byref(chain_tiles) if chain_tiles is not None else None, s)
+        elif n_tiles and c.use_free:
+            d_slot_rec = dev(t.slot_rec)
+            keep.append(d_slot_rec)
+            _lib.call("mm_boot1d_free", t.d_recs, P(d_slot_rec), n_tiles, P(d_slot_K), P(d_nobs), P(d_omq),
+                      P(d_slot_pair), pcg64_state(pcg_seed), B, int(mean_only), ld, P(self.ym), P(self.yv), P(self.w_dump), kmax_dump, chains, s)
         elif n_tiles:
-            _lib.call("mm_debug_replay_ring", 1 if REPLAY_RING else 0)
-            _lib.call("mm_debug_replay_rows_mod", int(os.environ.get('MM_DEBUG_ROWS_MOD', '0')))      # timing experiments only
-            d_tab, tab_len, tab_over = None, 0, None
-            if STREAM_TABLE and int(tile_k.max()) > 1:
-                tab_len = int(STREAM_PER_STEP * (int(tile_k.max()) - 1) * B) + 4096
-                d_tab = pcg64_stream_table(pcg_seed, tab_len)
-                tab_over = zeros((1,), torch.int32)
-            _lib.call("mm_boot1d_replay", *[P(o) for o in ops], P(d_tile_ptr), n_tiles, P(d_slot_K), P(d_nobs), P(d_omq), P(d_slot_pair),
-                      pcg64_state(pcg_seed), B, int(mean_only), ld, P(self.ym), P(self.yv), P(self.w_dump), kmax_dump, n_launch,
-                      ctypes.byref(chain_tiles) if chain_tiles is not None else None, P(d_tab), tab_len, P(tab_over), s)
+            _lib.call("mm_boot1d_replay", *[P(o) for o in t.ops], P(t.d_tile_ptr), n_tiles, P(d_slot_K), P(d_nobs), P(d_omq), P(d_slot_pair),
+                      pcg64_state(pcg_seed), B, int(mean_only), ld, P(self.ym), P(self.yv), P(self.w_dump), kmax_dump, n_launch, chains, s)
         if n_launch:
             torch.cuda.current_stream().wait_stream(side)
-        if n_tiles and not fast and tab_over is not None and int(tab_over.item()):
-            # a chain consumed more uniforms than the table holds (never seen): the tile launch again with the arithmetic generator
-            _lib.call("mm_boot1d_replay", *[P(o) for o in ops], P(d_tile_ptr), n_tiles, P(d_slot_K), P(d_nobs), P(d_omq), P(d_slot_pair),
-                      pcg64_state(pcg_seed), B, int(mean_only), ld, P(self.ym), P(self.yv), P(self.w_dump), kmax_dump, n_launch,
-                      ctypes.byref(chain_tiles) if chain_tiles is not None else None, None, 0, None, s)
-        st = int(status.item())
-        if st & 2 or st & 4:
-            raise RuntimeError(f"mm_bins_order inconsistency (status {st})")
-        if st & 8:
-            raise NotImplementedError("two bins of one pair collided in the replay hash (np.unique would merge them)")
-        self.raw_mean = self.ym.clone() if dump_weights else None
-        self.raw_var = self.yv.clone() if dump_weights else None
+        return keep
+
+    def _fill_log(self, mv_fit, fill_mode, fill_seed, first_pair, fill_keys):
+        """mm_boot_fill_log on the rows >= first_pair; returns n_invalid [rows][2] (host)."""
+        torch, ld = _torch(), self.ld
         n_rows = self.n_pairs - first_pair
         n_inv = empty((max(1, n_rows), 2), torch.int32)
         fit = (ctypes.c_double * 3)(*[float(x) for x in mv_fit])
         if n_rows > 0:
             d_keys = dev(np.asarray(fill_keys, dtype=np.int64)[first_pair:]) if fill_keys is not None else None
             _lib.call("mm_boot_fill_log", c_void_p(self.ym.data_ptr() + first_pair * ld * 8), c_void_p(self.yv.data_ptr() + first_pair * ld * 8),
-                      n_rows, ld, B, fit, int(fill_mode), int(fill_seed) & ((1 << 64) - 1), P(n_inv), P(d_keys), s)
-        self.active = active
+                      n_rows, ld, self.B, fit, int(fill_mode), int(fill_seed) & ((1 << 64) - 1), P(n_inv), P(d_keys), _stream())
         return host(n_inv)[:n_rows]
 
     def contract(self, test_gene, W, good, which):
@@ -1107,30 +1141,9 @@ class Bootstrap2D:
         with the same arithmetic as k_bins_order2d: code = (x_i*r[0] + x_j*r[1]) + r0*approx_sf ascending (bootstrap.py:62-67)."""
         bi, xi, xj, mu = self.bins_of(q)
         code = (xi.astype(np.float64) * ra + xj.astype(np.float64) * rb) + r0 * self.sf_table[bi]
-        o = np.argsort(code, kind="stable")
-        if len(o) > 1 and (np.diff(code[o]) == 0).any():
-            raise NotImplementedError("two bins of one pair collided in the replay hash (np.unique would merge them)")
-        bi, xi, xj, mu = bi[o], xi[o].astype(np.float64), xj[o].astype(np.float64), mu[o].astype(np.float64)
-        pix = mu / float(self.blocks.grp_ncells[q % self.ng])
-        rem = np.empty_like(pix)
-        acc = 1.0
-        for k in range(len(pix)):      # sequential rounding, exactly like numpy's remaining_p
-            rem[k] = acc
-            acc -= pix[k]
-        pk = pix / rem
-        peff = np.where(pk <= 0.5, pk, 1.0 - pk)
-        with np.errstate(divide="ignore", invalid="ignore"):
-            lq = np.log(1.0 - peff)
-        sf = self.sf_table[bi]
-        if slot & CHAIN_SLOT:      # 8-double records (mm_boot2d_replay_rec), addressed from the start of ops[0]
-            rec = np.zeros((len(pk), 8))
-            rec[:, 0], rec[:, 1], rec[:, 2], rec[:, 3], rec[:, 4], rec[:, 5] = pk, lq, xi, xj, 1.0 / sf, 1.0 / (sf * sf)
-            r0_ = (slot & (CHAIN_SLOT - 1)) * 8
-            ops[0][r0_:r0_ + rec.size] = dev(rec.reshape(-1))
-            return
-        idx = dev((int(tile_ptr[slot >> 6]) + np.arange(len(pk), dtype=np.int64)) * 64 + (slot & 63))
-        for arr, vals in zip(ops, (pk, lq, xi, xj, 1.0 / sf, 1.0 / (sf * sf))):
-            arr[idx] = dev(vals)
+        o, pk, lq = _replay_order(code, mu, self.blocks.grp_ncells[q % self.ng])
+        sf = self.sf_table[bi[o]]
+        _write_chain_operands(ops[0], ops, slot, tile_ptr, (pk, lq, xi[o].astype(np.float64), xj[o].astype(np.float64), 1.0 / sf, 1.0 / (sf * sf)))
 
     def run(self, skip, r1a, r1b, r0, true_corr, pcg_seed=5, target_waves=None):
         """All arrays are indexed by q = sorted_pair*n_groups + group (see ``self.order``).  Leaves the
@@ -1144,29 +1157,19 @@ class Bootstrap2D:
         slot_of, n_tiles = pack_lanes(self.K[order], PACK_WAVES if target_waves is None else target_waves, consts=PACK2D, cost=PACK_COST_2D)
         slot_of = pair_tiles(slot_of, n_tiles, self.K[order], cost=PACK_COST_2D)
         self.n_tiles = n_tiles
-        pair_slot = np.full(self.n_q, -1, dtype=np.int64)
-        pair_slot[order] = slot_of
-        slot_pair = np.full(n_tiles * 64, -1, dtype=np.int64)
-        slot_pair[slot_of] = order
-        slot_K = np.zeros(n_tiles * 64, dtype=np.int32)
-        slot_K[slot_of] = self.K[order]
-        tile_k = slot_K.reshape(n_tiles, 64).max(axis=1) if n_tiles else np.zeros(0, dtype=np.int32)
-        tile_ptr = np.concatenate([[0], np.cumsum(tile_k.astype(np.int64))]).astype(np.int64)
-        rows = int(tile_ptr[-1])
+        t = _plan_tiles(self.K, order, slot_of, n_tiles, self.n_q, self.blocks.grp_ncells, self.grp_q, ng)
+        pair_slot, tile_ptr = t.pair_slot, t.tile_ptr
         self.draws_per_replicate = int(np.maximum(self.K[order] - 1, 0).sum())
-        self.wave_steps_per_replicate = rows
+        self.wave_steps_per_replicate = rows = int(tile_ptr[-1])
         use_rec = BOOT2D_RECORDS and n_tiles > 0
-        slot_rec = None
         if use_rec:
             # per-chain operand records (8 doubles per bin) instead of [row][64] planes: a lane reads memory of its own wherever it is in
             # its chain, so the kernel can let a rejected BTPE attempt retry in the next bin step (mm_boot2d_replay_rec)
-            rec_K = self.K[order].astype(np.int64)
-            rec_base = np.concatenate([[0], np.cumsum(rec_K)]).astype(np.int64)
+            rec_base = _plan_records(self.K, order)[1]
             ops = [empty((8 * max(1, int(rec_base[-1])),), torch.float64)] + [empty((8,), torch.float64) for _ in range(5)]
             self.tile_slot = pair_slot.copy()
             pair_slot[order] = CHAIN_SLOT | rec_base[:-1]
-            slot_rec = np.full(n_tiles * 64, -1, dtype=np.int64)
-            slot_rec[slot_of] = rec_base[:-1]
+            slot_rec = _per_slot(n_tiles * 64, slot_of, rec_base[:-1], -1, np.int64)
         else:
             ops = [empty((max(1, rows) * 64,), torch.float64) for _ in range(6)]
         d_pair_slot, d_tile_ptr = dev(pair_slot), dev(tile_ptr)
@@ -1184,13 +1187,9 @@ class Bootstrap2D:
                 _lib.call("mm_bins_order2d", P(self.tab), P(self.d_tab_ptr), P(self.d_xi), P(self.d_xj), P(self.d_K), P(d_lst), len(lst),
                           is_big, ng, self.n_bins, P(d_sf), P(d_ra), P(d_rb), P(d_r0), P(d_pair_slot), P(d_tile_ptr), P(d_nc),
                           *[P(o) for o in ops], P(status), s)
-        nobs = np.zeros(n_tiles * 64)
-        nobs[slot_of] = self.blocks.grp_ncells[order % ng]
-        omq = np.zeros(n_tiles * 64)
-        omq[slot_of] = 1.0 - self.grp_q[order % ng]
         self.yc = torch.full((max(1, self.n_q), ld), float("nan"), dtype=torch.float64, device="cuda")
         self.yc[: self.n_q, 0] = dev(np.asarray(true_corr, dtype=np.float64))
-        d_slot_K, d_nobs, d_omq, d_slot_pair = dev(slot_K), dev(nobs), dev(omq), dev(slot_pair)
+        d_slot_K, d_nobs, d_omq, d_slot_pair = dev(t.slot_K), dev(t.nobs), dev(t.omq), dev(t.slot_pair)
         if n_tiles and use_rec:
             d_slot_rec = dev(slot_rec)
             _lib.call("mm_boot2d_replay_rec", P(ops[0]), P(d_slot_rec), n_tiles, P(d_slot_K), P(d_nobs), P(d_omq), P(d_slot_pair),

@@ -215,7 +215,7 @@ def test_four_replay_kernels_agree_bit_for_bit(big, monkeypatch):
 def test_replay_weights_bit_exact_at_scale(big, monkeypatch, tile_mode):
     """BTPE-heavy stress of the samplers on the device: >1e6 draws on 12k-cell (C2) / 48k-cell (C3) groups must equal
     numpy's Generator(PCG64(5)).multinomial draw for draw -- the longer half of the chains through the one-wave-per-chain
-    kernel, the shorter half through the lock-step tile kernel (uniforms from the precomputed stream table) or the
+    kernel, the shorter half through the lock-step tile kernel (every lane steps its own PCG64 generator) or the
     lane-asynchronous tile kernel."""
     engine, torch, csr, gid, blocks, sf = big
     S, sumx, maxx = blocks.moments(1.0 / sf)

@@ -1,5 +1,5 @@
 """The one-wave-per-chain kernel (mm_boot1d_chain) by itself: step time of the N longest chains of a config at several
-occupancies, and -- when the library was built with -DBOOT_STAMPS -- shader cycles per sampler call by sampler.
+occupancies.
 usage: python tools/chain_micro.py [config=C3 | C3@cells[@num_boot]] n_chains [n_chains ...]"""
 import ctypes, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -54,12 +54,6 @@ def main():
                 us = dur / ((Kc - 1) * B) * 1e6
                 line = (f"chain kernel alone, {bs.n_chain} chains (K {Kc.max()}..{Kc.min()}): span {(wc[:, 1].max() - wc[:, 0].min()) / 1e8:.3f} s; "
                         f"us/step first 64: {np.median(us[:64]):.3f}, all: median {np.median(us):.3f} p90 {np.quantile(us, .9):.3f}")
-                if wc[:, 6].any():
-                    s = wc[:64].astype(np.float64)
-                    steps = ((Kc[:64] - 1) * B).astype(np.float64)
-                    line += (f"\n     stamps (first 64 chains): inversion calls {s[:, 2].sum() / steps.sum():.2f}/step at {s[:, 3].sum() / max(1, s[:, 2].sum()):.0f} cyc, "
-                             f"BTPE calls {s[:, 4].sum() / steps.sum():.2f}/step at {s[:, 5].sum() / max(1, s[:, 4].sum()):.0f} cyc, whole step {s[:, 6].sum() / steps.sum():.0f} cyc, "
-                             f"shader clock {s[:, 6].sum() / dur[:64].sum() / 1e9:.2f} GHz")
                 print(line, flush=True)
             else:
                 nt = bs.n_tiles

@@ -42,8 +42,6 @@ def main():
     hist = np.histogram(K, bins=edges)[0]
     print("K histogram:", ", ".join(f"[{a},{b}) {c}" for a, b, c in zip(edges[:-1], edges[1:], hist)), flush=True)
     r = np.random.default_rng(0).random((2, bs.n_pairs))
-    if os.environ.get("MM_ROWS_MOD"):       # timing experiment (WRONG results): tiles read their operand rows out of a cache-resident region
-        _lib.call("mm_debug_replay_rows_mod", int(os.environ["MM_ROWS_MOD"]))
     timer, ms = ctypes.c_void_p(), ctypes.c_float()
     _lib.call("mm_timer_create", ctypes.byref(timer))
     buf = torch.zeros((1 << 20,), dtype=torch.int64, device="cuda")
@@ -110,11 +108,6 @@ def main():
             print(f"   async kernel: {nw} waves, span {(wt[:, 1].max() - wt[:, 0].min()) / 1e8:.3f} s, longest wave {dur.max():.3f} s, sum of wave time {dur.sum():.1f} s; "
                   f"passes per (longest chain's) draw: median {np.median(wt[:, 2] / (kmax * B)):.2f}; us per pass: median {np.median(dur / wt[:, 2]) * 1e6:.2f} "
                   f"(first wave {dur[0] / wt[0, 2] * 1e6:.2f}, last {dur[-1] / wt[-1, 2] * 1e6:.2f}); us per draw of a lane: {np.median(dur * L / (ksum * B)) * 1e6:.3f}", flush=True)
-            ph = raw[(1 << 19): (1 << 19) + nw * 8].reshape(-1, 8)[:, :7].astype(np.float64)
-            if ph.any():
-                per = ph.sum(axis=0) / wt[:, 2].sum()
-                print("   async stamps, shader cycles per pass: " + ", ".join(f"{n} {v:.0f}" for n, v in zip(
-                    ["retire/restart", "start (both set-ups)", "inversion segment + attempt", "attempt outside the triangle", "explicit", "squeeze", "exact redo"], per)) + f"; sum {per.sum():.0f}", flush=True)
         if bs.n_tiles:
             wt = raw[: bs.n_tiles * 4].reshape(-1, 4)
             lanes = (bs.slot_K.reshape(bs.n_tiles, 64) > 0).sum(axis=1)
