@@ -1179,6 +1179,8 @@ class Bootstrap2D:
         small = order[self.K[order] <= ORDER_SMALL_CAP]
         big = order[(self.K[order] > ORDER_SMALL_CAP) & (self.K[order] <= ORDER_BIG_CAP_2D)]
         huge = order[self.K[order] > ORDER_BIG_CAP_2D]
+        self.order_path = {"small": len(small), "big": len(big), "host": len(huge)}     # diagnostics (tests): chains per ordering path
+        self.replay_kernel = None                                                       # ... and the replay kernel launched below
         for q in huge:   # more bins than the in-LDS sort holds (two highly expressed genes): ordered on the host, like the 1D path
             self._order_on_host(int(q), float(r1a[q]), float(r1b[q]), float(r0[q]), int(pair_slot[q]), tile_ptr, ops)
         for lst, is_big in ((small, 0), (big, 1)):
@@ -1194,9 +1196,11 @@ class Bootstrap2D:
             d_slot_rec = dev(slot_rec)
             _lib.call("mm_boot2d_replay_rec", P(ops[0]), P(d_slot_rec), n_tiles, P(d_slot_K), P(d_nobs), P(d_omq), P(d_slot_pair),
                       pcg64_state(pcg_seed), B, ld, P(self.yc), s)
+            self.replay_kernel = "mm_boot2d_replay_rec"
         elif n_tiles:
             _lib.call("mm_boot2d_replay", *[P(o) for o in ops], P(d_tile_ptr), n_tiles, P(d_slot_K), P(d_nobs), P(d_omq), P(d_slot_pair),
                       pcg64_state(pcg_seed), B, ld, P(self.yc), s)
+            self.replay_kernel = "mm_boot2d_replay"
         st = int(status.item())
         if st & 6:
             raise RuntimeError(f"mm_bins_order2d inconsistency (status {st})")
