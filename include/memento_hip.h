@@ -413,6 +413,17 @@ int mm_boot2d_replay_rec(const double *d_recs, const int64_t *d_slot_rec, int64_
                          const double *d_slot_nobs, const double *d_slot_omq, const int64_t *d_slot_row, const uint64_t pcg_state[4],
                          int32_t num_boot, int64_t ld, double *d_out_corr, void *stream);
 
+/* FAST mode of the 2D bootstrap (rng='fast'): one lane = one replicate, one wave = 64 replicates of one (pair, group) chain, read
+ * from the six [row][64] operand planes mm_bins_order2d writes for plain tile slots (n_slots = 64 * n_tiles, slot s = 64 * tile +
+ * lane; d_slot_K[s] <= 0 or d_slot_row[s] < 0 = unused).  Replicate r of slot s owns the PCG64 stream derived from
+ * (seed, d_slot_key[s], r): keys that number the chains independently of chunking and layout make the result independent of both.
+ * Same samplers and replicate arithmetic as mm_boot2d_replay, different random numbers: statistically equivalent to the
+ * reference, not draw-for-draw identical.  d_w_dump (optional, NULL in production): int32 weights [slot][k < kmax_dump][r < num_boot]. */
+int mm_boot2d_fast(const double *d_pk, const double *d_lq, const double *d_v1, const double *d_v2, const double *d_a,
+                   const double *d_b, const int64_t *d_tile_ptr, int64_t n_slots, const int32_t *d_slot_K, const double *d_slot_nobs,
+                   const double *d_slot_omq, const int64_t *d_slot_row, const int64_t *d_slot_key, uint64_t seed, int32_t num_boot,
+                   int64_t ld, double *d_out_corr, int32_t *d_w_dump, int32_t kmax_dump, void *stream);
+
 /* ---- synthetic data generator (replaces memento/simulate.py:52-89 and :91-115) ----
  * Counter-based: transcriptome count z[cell][gene] ~ NB(mean[gene], size theta[gene]) is a pure function of (seed_z, cell, gene),
  * so nothing dense is ever stored.  One launch per pass, selected by `mode`:

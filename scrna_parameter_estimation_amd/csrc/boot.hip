@@ -728,6 +728,33 @@ __global__ __launch_bounds__(256, MINW) void k_boot1d_free(const double *__restr
 #ifndef BOOT2D_BTPE_CAP
 #define BOOT2D_BTPE_CAP 0
 #endif
+// One bin's share of a replicate's five sums and the replicate's correlation from them.  Both 2D kernels below add their bins in chain
+// order through these two (the association of every product is numpy's), as the 1D kernels do through accumulate_1d / close_replicate.
+struct Sums2D {
+  double A1 = 0.0, A2 = 0.0, MX = 0.0, Q1 = 0.0, Q2 = 0.0;
+};
+__device__ __forceinline__ void accumulate_2d(Sums2D &s, int32_t w, double x1, double x2, double aa, double bb, double omq) {
+  double wd = (double)w;
+  s.A1 += (x1 * wd) * aa;
+  s.A2 += (x2 * wd) * aa;
+  s.MX += ((x1 * x2) * wd) * bb;
+  s.Q1 += ((x1 * x1) * wd) * bb - ((omq * x1) * wd) * bb;
+  s.Q2 += ((x2 * x2) * wd) * bb - ((omq * x2) * wd) * bb;
+}
+__device__ __forceinline__ double close_replicate_2d(const Sums2D &s, double nobs) {
+  double m1 = s.A1 / nobs, m2 = s.A2 / nobs;
+  double cov = s.MX / nobs - m1 * m2;
+  double var1 = s.Q1 / nobs - m1 * m1;
+  double var2 = s.Q2 / nobs - m2 * m2;
+  double corr = 5.0;       // estimator._corr_from_cov: the sentinel where a variance is <= 0, clipped below like any other value
+  if (var1 > 0.0 && var2 > 0.0) {
+    double vp = sqrt(var1 * var2);
+    if (isfinite(vp)) corr = cov / vp;
+  }
+  if (corr > 1.0) corr = 1.0;
+  if (corr < -1.0) corr = -1.0;
+  return corr;
+}
 #ifndef BOOT2D_REC_BTPE_CAP
 #define BOOT2D_REC_BTPE_CAP 1    // attempts per bin step when the chains read their own operand records (REC): no shared rows to scatter
 #endif
@@ -774,7 +801,7 @@ __global__ __launch_bounds__(256, MINW) void k_boot2d_replay(const double *__res
     c_pk = pk_[obase]; c_lq = lq_[obase]; c_x1 = v1_[obase]; c_x2 = v2_[obase]; c_a = a[obase]; c_b = b[obase];
   }
   for (int r = 0; r < num_boot; r++) {
-    double A1 = 0.0, A2 = 0.0, MX = 0.0, Q1 = 0.0, Q2 = 0.0;
+    Sums2D sums;
     int32_t dn = n;
     bool live = true;
     // this lane's bin, as in k_boot1d_replay -- but BOOT2D_BTPE_CAP is 0: measured on configs[3]'s share (250 x 2000 pairs, 335 bins
@@ -816,14 +843,7 @@ __global__ __launch_bounds__(256, MINW) void k_boot2d_replay(const double *__res
           w = dn > 0 ? dn : 0;
         }
         if (!pending) {
-          if (w != 0) {
-            double wd = (double)w, x1 = c_x1, x2 = c_x2, aa = c_a, bb = c_b;
-            A1 += (x1 * wd) * aa;
-            A2 += (x2 * wd) * aa;
-            MX += ((x1 * x2) * wd) * bb;
-            Q1 += ((x1 * x1) * wd) * bb - ((omq * x1) * wd) * bb;
-            Q2 += ((x2 * x2) * wd) * bb - ((omq * x2) * wd) * bb;
-          }
+          if (w != 0) accumulate_2d(sums, w, c_x1, c_x2, c_a, c_b, omq);
           adv = true;
         }
       }
@@ -832,21 +852,62 @@ __global__ __launch_bounds__(256, MINW) void k_boot2d_replay(const double *__res
         c_pk = n_pk; c_lq = n_lq; c_x1 = n_x1; c_x2 = n_x2; c_a = n_a; c_b = n_b;
       }
     }
-    if (run) {
-      double m1 = A1 / nobs, m2 = A2 / nobs;
-      double cov = MX / nobs - m1 * m2;
-      double var1 = Q1 / nobs - m1 * m1;
-      double var2 = Q2 / nobs - m2 * m2;
-      double corr = 5.0;
-      if (var1 > 0.0 && var2 > 0.0) {
-        double vp = sqrt(var1 * var2);
-        if (isfinite(vp)) corr = cov / vp;
-      }
-      if (corr > 1.0) corr = 1.0;
-      if (corr < -1.0) corr = -1.0;
-      oc[r] = corr;
-    }
+    if (run) oc[r] = close_replicate_2d(sums, nobs);
   }
+}
+
+// ------------------------------------------------------------------------------------------------
+// 2D FAST mode (rng='fast'): k_boot1d_fast's decomposition with k_boot2d_replay's arithmetic.  One lane = one REPLICATE, one wave
+// = 64 replicates of ONE (pair, group) chain: wave wid = slot * chunks + chunk draws replicates chunk * 64 + lane.  The address of
+// bin k in the six [row][64] planes is wave-uniform (one broadcast load per operand and step, fetched one bin ahead); the lanes hold
+// different remainders, so they may take different samplers at a step.  A chain's critical path is its K draws instead of K x B, and
+// the launch has chains x ceil(B / 64) independent waves.  Replicate r of the chain with key ``slot_key[slot]`` owns the PCG64 stream
+// derived from (seed, key, r) -- the caller's keys number the (pair, group) chains independently of chunking, of the order the pairs
+// are in and of the tile layout, so neither changes a result.  Chains with K >= 1 run (K == 1: every replicate is the observed
+// sample, as in the replay kernel); K <= 0 or row < 0 writes nothing.  Lanes beyond num_boot walk along and store nothing.
+// w_dump (optional): int32 weights [slot][k < kmax_dump][r < num_boot].
+__global__ __launch_bounds__(256) void k_boot2d_fast(const double *__restrict__ pk_, const double *__restrict__ lq_,
+                                                     const double *__restrict__ v1_, const double *__restrict__ v2_,
+                                                     const double *__restrict__ a, const double *__restrict__ b,
+                                                     const int64_t *__restrict__ tile_ptr, int64_t n_slots,
+                                                     const int32_t *__restrict__ slot_K, const double *__restrict__ slot_nobs,
+                                                     const double *__restrict__ slot_omq, const int64_t *__restrict__ slot_row,
+                                                     const int64_t *__restrict__ slot_key, uint64_t seed, int32_t num_boot,
+                                                     int32_t chunks, int64_t ld, double *__restrict__ out_corr,
+                                                     int32_t *__restrict__ w_dump, int32_t kmax_dump) {
+  int lane = mm_lane();
+  int64_t wid = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  int64_t slot = wid / chunks;
+  int chunk = (int)(wid % chunks);
+  if (slot >= n_slots) return;
+  int K = slot_K[slot];
+  int64_t row = slot_row[slot];
+  if (K <= 0 || row < 0) return;
+  int r = chunk * 64 + lane;
+  bool mine = r < num_boot;
+  int64_t obase = tile_ptr[slot >> 6] * 64 + (slot & 63);
+  double nobs = slot_nobs[slot], omq = slot_omq[slot];
+  uint64_t h = mix64(seed ^ mix64((uint64_t)slot_key[slot] * 0x100000001B3ull + (uint64_t)r));
+  npyrng::Pcg64 g{mix64(h), mix64(h + 1), mix64(h + 2), mix64(h + 3) | 1ull};
+  int32_t *wd = (w_dump && mine) ? w_dump + (slot * kmax_dump) * (int64_t)num_boot + r : nullptr;
+  Sums2D sums;
+  int32_t dn = (int32_t)nobs;  // N_g < 2^31 (checked by the host)
+  double c_pk = pk_[obase], c_lq = lq_[obase], c_x1 = v1_[obase], c_x2 = v2_[obase], c_a = a[obase], c_b = b[obase];
+  for (int k = 0; k < K; k++) {
+    int64_t on = obase + (int64_t)(k + 1 < K ? k + 1 : 0) * 64;   // wave-uniform address of the next bin's operands
+    double n_pk = pk_[on], n_lq = lq_[on], n_x1 = v1_[on], n_x2 = v2_[on], n_a = a[on], n_b = b[on];
+    int32_t w;
+    if (k < K - 1) {
+      w = dn > 0 ? npyrng::binomial_pre<int32_t, true>(g, c_pk, c_lq, dn) : 0;
+      dn -= w;
+    } else {
+      w = dn > 0 ? dn : 0;
+    }
+    if (wd && k < kmax_dump) wd[(int64_t)k * num_boot] = w;
+    accumulate_2d(sums, w, c_x1, c_x2, c_a, c_b, omq);
+    c_pk = n_pk; c_lq = n_lq; c_x1 = n_x1; c_x2 = n_x2; c_a = n_a; c_b = n_b;
+  }
+  if (mine) out_corr[row * ld + 1 + r] = close_replicate_2d(sums, nobs);
 }
 
 static int64_t *g_wave_clock = nullptr;  // set by mm_debug_wave_clock; nullptr = no profiling writes
@@ -1007,6 +1068,25 @@ int mm_boot2d_replay_rec(const double *d_recs, const int64_t *d_slot_rec, int64_
   hipLaunchKernelGGL(kern, dim3((unsigned)((n_tiles + 3) / 4)), dim3(256), 0, (hipStream_t)stream, d_recs, nul, nul, nul, nul, nul,
                      (const int64_t *)nullptr, n_tiles, d_slot_K, d_slot_nobs, d_slot_omq, d_slot_row, pcg_state[0], pcg_state[1],
                      pcg_state[2], pcg_state[3], num_boot, ld, d_out_corr, d_slot_rec);
+  MM_LAUNCH_CHECK();
+  return MM_OK;
+}
+
+int mm_boot2d_fast(const double *d_pk, const double *d_lq, const double *d_v1, const double *d_v2, const double *d_a,
+                   const double *d_b, const int64_t *d_tile_ptr, int64_t n_slots, const int32_t *d_slot_K, const double *d_slot_nobs,
+                   const double *d_slot_omq, const int64_t *d_slot_row, const int64_t *d_slot_key, uint64_t seed, int32_t num_boot,
+                   int64_t ld, double *d_out_corr, int32_t *d_w_dump, int32_t kmax_dump, void *stream) {
+  MM_ARG(d_pk && d_lq && d_v1 && d_v2 && d_a && d_b && d_tile_ptr && d_slot_K && d_slot_nobs && d_slot_omq && d_slot_row && d_slot_key);
+  MM_ARG(d_out_corr && n_slots >= 0 && n_slots % 64 == 0 && num_boot > 0 && ld >= (int64_t)num_boot + 1);
+  MM_ARG(!d_w_dump || kmax_dump > 0);
+  if (n_slots == 0) return MM_OK;
+  int32_t chunks = (num_boot + 63) / 64;
+  int64_t waves = n_slots * chunks;
+  int64_t blocks = (waves + 3) / 4;
+  MM_ARG(blocks < 2147483647LL);
+  hipLaunchKernelGGL(k_boot2d_fast, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, d_pk, d_lq, d_v1, d_v2, d_a, d_b, d_tile_ptr,
+                     n_slots, d_slot_K, d_slot_nobs, d_slot_omq, d_slot_row, d_slot_key, seed, num_boot, chunks, ld, d_out_corr, d_w_dump,
+                     kmax_dump);
   MM_LAUNCH_CHECK();
   return MM_OK;
 }

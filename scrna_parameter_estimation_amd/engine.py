@@ -1145,23 +1145,37 @@ class Bootstrap2D:
         sf = self.sf_table[bi[o]]
         _write_chain_operands(ops[0], ops, slot, tile_ptr, (pk, lq, xi[o].astype(np.float64), xj[o].astype(np.float64), 1.0 / sf, 1.0 / (sf * sf)))
 
-    def run(self, skip, r1a, r1b, r0, true_corr, pcg_seed=5, target_waves=None):
+    def weights_of(self, q):
+        """Test helper (after run(fast=True, dump_weights=True)): the int32 multinomial weights [K][B] of chain q."""
+        return host(self.w_dump[int(self.pair_slot[q]), :int(self.K[q]), :])
+
+    def run(self, skip, r1a, r1b, r0, true_corr, pcg_seed=5, target_waves=None, fast=False, fast_seed=0, pair_key=None, dump_weights=False):
         """All arrays are indexed by q = sorted_pair*n_groups + group (see ``self.order``).  Leaves the
-        replicate correlations in self.yc [n_q][B+1] (column 0 = true correlation)."""
+        replicate correlations in self.yc [n_q][B+1] (column 0 = true correlation).
+
+        ``fast``: the replicate-parallel kernel (mm_boot2d_fast) on dense 64-wide tiles of the operand planes instead of the replay
+        kernels: replicate r of chain q draws from its own PCG64 stream derived from (``fast_seed``, ``pair_key[q]``, r) --
+        ``pair_key`` [n_q] int64, default q; keys that do not depend on how the pairs were chunked or ordered make the result
+        independent of both -- and ``pcg_seed`` is ignored.  ``dump_weights`` (fast only): keep the weights for ``weights_of``."""
         torch = _torch()
         s = _stream()
         ng, B, ld = self.ng, self.B, self.ld
+        if dump_weights and not fast:
+            raise ValueError("dump_weights needs fast=True")
         active = (~np.asarray(skip, dtype=bool)) & (self.K >= 1)
         act = np.flatnonzero(active)
         order = act[np.argsort(-self.K[act], kind="stable")]
-        slot_of, n_tiles = pack_lanes(self.K[order], PACK_WAVES if target_waves is None else target_waves, consts=PACK2D, cost=PACK_COST_2D)
-        slot_of = pair_tiles(slot_of, n_tiles, self.K[order], cost=PACK_COST_2D)
+        if fast:    # one WAVE per 64 replicates of a chain, lanes = replicates: plain 64-wide tiles, longest chains dispatched first
+            slot_of, n_tiles = pack_lanes(self.K[order], 0, dense=True)
+        else:
+            slot_of, n_tiles = pack_lanes(self.K[order], PACK_WAVES if target_waves is None else target_waves, consts=PACK2D, cost=PACK_COST_2D)
+            slot_of = pair_tiles(slot_of, n_tiles, self.K[order], cost=PACK_COST_2D)
         self.n_tiles = n_tiles
         t = _plan_tiles(self.K, order, slot_of, n_tiles, self.n_q, self.blocks.grp_ncells, self.grp_q, ng)
         pair_slot, tile_ptr = t.pair_slot, t.tile_ptr
         self.draws_per_replicate = int(np.maximum(self.K[order] - 1, 0).sum())
         self.wave_steps_per_replicate = rows = int(tile_ptr[-1])
-        use_rec = BOOT2D_RECORDS and n_tiles > 0
+        use_rec = BOOT2D_RECORDS and n_tiles > 0 and not fast
         if use_rec:
             # per-chain operand records (8 doubles per bin) instead of [row][64] planes: a lane reads memory of its own wherever it is in
             # its chain, so the kernel can let a rejected BTPE attempt retry in the next bin step (mm_boot2d_replay_rec)
@@ -1192,7 +1206,17 @@ class Bootstrap2D:
         self.yc = torch.full((max(1, self.n_q), ld), float("nan"), dtype=torch.float64, device="cuda")
         self.yc[: self.n_q, 0] = dev(np.asarray(true_corr, dtype=np.float64))
         d_slot_K, d_nobs, d_omq, d_slot_pair = dev(t.slot_K), dev(t.nobs), dev(t.omq), dev(t.slot_pair)
-        if n_tiles and use_rec:
+        self.w_dump = None
+        if n_tiles and fast:
+            keys = np.arange(self.n_q, dtype=np.int64) if pair_key is None else np.asarray(pair_key, dtype=np.int64)
+            d_slot_key = dev(_per_slot(n_tiles * 64, slot_of, keys[order], 0, np.int64))
+            kmax_dump = int(t.tile_k.max()) if dump_weights else 0
+            if dump_weights:
+                self.w_dump = zeros((n_tiles * 64, kmax_dump, B), torch.int32)
+            _lib.call("mm_boot2d_fast", *[P(o) for o in ops], P(d_tile_ptr), n_tiles * 64, P(d_slot_K), P(d_nobs), P(d_omq), P(d_slot_pair),
+                      P(d_slot_key), int(fast_seed) & ((1 << 64) - 1), B, ld, P(self.yc), P(self.w_dump), kmax_dump, s)
+            self.replay_kernel = "mm_boot2d_fast"
+        elif n_tiles and use_rec:
             d_slot_rec = dev(slot_rec)
             _lib.call("mm_boot2d_replay_rec", P(ops[0]), P(d_slot_rec), n_tiles, P(d_slot_K), P(d_nobs), P(d_omq), P(d_slot_pair),
                       pcg64_state(pcg_seed), B, ld, P(self.yc), s)

@@ -8,6 +8,7 @@ Reference signatures mirrored (paths relative to /root/reference/):
   get_groups           :156-168                   get_1d_moments / get_1d_ht_result  :523, :635
 Extra keyword-only knobs (do not disturb the reference's positional order):
   ht_1d_moments(..., rng='replay', strict=False, fill_seed=0)
+  ht_2d_moments(..., fill_seed=0, strict=False, rng='replay')
   compute_1d_moments(..., subset_var=True)
 
 Host code here is argument handling, the uns schema, O(G) post-processing (polyfit, filters, design
@@ -963,9 +964,15 @@ def _pair_plan(m, st, num_boot, max_rows):
 
 
 def ht_2d_moments(adata, covariate, treatment, treatment_for_gene=None, inplace=True, num_boot=10000, verbose=3, num_cpus=1,
-                  max_rows=None, fill_seed=0, strict=False, **kwargs):
+                  max_rows=None, fill_seed=0, strict=False, rng='replay', **kwargs):
     """Bootstrap hypothesis test of correlation differences (reference: memento/main.py:418-520,
-    hypothesis_test._ht_2d :303-364).  Same replay semantics as ht_1d_moments.  ``resample_rep=True``
+    hypothesis_test._ht_2d :303-364).  Same replay semantics as ht_1d_moments.
+    ``rng='fast'``: same samplers and replicate arithmetic, but every (pair, group, replicate) has its own counter-derived
+    PCG64 stream seeded by ``fill_seed`` (mm_boot2d_fast: one wave per 64 replicates of a chain instead of one lane per chain)
+    -- statistically equivalent to the reference, not draw-identical.  The global ``np.random`` stream is consumed as with
+    ``rng='replay'``, so the bins, their order, ``corr_coef``, the NaN pattern and the skip rules are the replay run's; the
+    streams are keyed by the pair's position among the distinct tested pairs, so the result does not depend on ``max_rows``.
+    ``resample_rep=True``
     (hypothesis_test.py:393-404): with ``strict=True`` the reference's two np.random.choice draws per pair are replayed from
     the global stream in pair order (exact agreement with the reference at num_cpus=1); otherwise the group /
     replicate-column assignments are drawn on the device (seeded by ``fill_seed``): statistically equivalent, not
@@ -973,6 +980,10 @@ def ht_2d_moments(adata, covariate, treatment, treatment_for_gene=None, inplace=
     ``treatment_for_gene`` as the reference BEHAVES (main.py:492): a pair's treatment columns are looked up under
     ``frozenset({name of the pair's first gene})`` -- the key is built from idx_1 twice -- and one number per pair is stored,
     so the list must hold exactly one column (the reference raises ValueError on more); pinned by fixture ``api_tfg2d``."""
+    if rng not in ('replay', 'fast'):
+        raise ValueError("rng must be 'replay' or 'fast'")
+    if strict and rng != 'replay':
+        raise ValueError("strict=True needs rng='replay'")
     if 'resampling' not in kwargs:
         raise TypeError("_compute_asl() missing 1 required positional argument: 'resampling'")
     resampling = kwargs['resampling']
@@ -993,6 +1004,7 @@ def ht_2d_moments(adata, covariate, treatment, treatment_for_gene=None, inplace=
     n_conv = idx1.shape[0]
     first, members, c1, c2, true_corr, skip, bounds = _pair_plan(m, st, num_boot, max_rows)
     P_ = len(first)
+    chain_key = np.arange(P_ * ng, dtype=np.int64)        # rng='fast': stream key of (pair k, group) = k * n_groups + group
     tcol = np.zeros(P_, dtype=np.int64)                   # treatment column of every tested pair (column 0 without treatment_for_gene)
     if treatment_for_gene is not None:
         names2, trt_cols = np.asarray(adata.var.index), list(treatment.columns)
@@ -1044,7 +1056,8 @@ def ht_2d_moments(adata, covariate, treatment, treatment_for_gene=None, inplace=
             return a[sl].reshape(n_ch, ng)[so].reshape(-1)
 
         bs.run(to_dev_order(skip.reshape(-1)), to_dev_order(r1a), to_dev_order(r1b), to_dev_order(r0),
-               to_dev_order(np.where(skip, np.nan, true_corr).reshape(-1)))
+               to_dev_order(np.where(skip, np.nan, true_corr).reshape(-1)), fast=(rng == 'fast'), fast_seed=fill_seed,
+               pair_key=to_dev_order(chain_key))
         good = bs.active.reshape(n_ch, ng)                # device order
         cache, rows = {}, []
         tc = tcol[lo:hi][so]                               # device order
@@ -1097,7 +1110,7 @@ def ht_2d_moments(adata, covariate, treatment, treatment_for_gene=None, inplace=
 
 
 def ht_2d_vs_control(adata, control, num_boot=10000, num_cpus=1, fill_seed=0, max_rows=None, approx=False, resampling='bootstrap',
-                     *, treatment_col=None):
+                     rng='replay', *, treatment_col=None):
     """Perturb-seq style batch test of differential COEXPRESSION: the correlation of every pair of ``compute_2d_moments`` in
     every group against one shared ``control``, in one call.  ``control`` / ``treatment_col`` mean what they mean in
     ``ht_1d_vs_control``: without ``treatment_col`` a group label (or index) every other group is tested against; with it the
@@ -1113,10 +1126,13 @@ def ht_2d_vs_control(adata, control, num_boot=10000, num_cpus=1, fill_seed=0, ma
     ``ht_2d_moments`` (unordered duplicates share the first one's result, self pairs stay NaN, a (pair, group) with a NaN or
     +-1 correlation is skipped) and the global ``np.random`` stream is consumed as there (three uniforms per live
     (pair, group), pair-major, up front).  A test with no good guide or control group, or with no stratum holding both arms,
-    is NaN.
+    is NaN.  ``rng='replay'|'fast'`` as in ``ht_2d_moments``: ``'fast'`` draws every (pair, group, replicate) from its own
+    stream seeded by ``fill_seed`` (mm_boot2d_fast), with the same bins, ``corr_coef`` and NaN pattern as ``'replay'``.
 
     Returns a DataFrame (gene_1, gene_2, group, corr_coef, corr_se, corr_pval), pair-major, one row per (requested pair,
     tested guide), and stores the arrays in ``uns['memento']['2d_ht_vs_control']``."""
+    if rng not in ('replay', 'fast'):
+        raise ValueError("rng must be 'replay' or 'fast'")
     m = adata.uns['memento']
     st = m['_hip']
     st.last_bootstrap2d = None                 # (free the previous call's replicate rows before this call allocates its own)
@@ -1134,6 +1150,7 @@ def ht_2d_vs_control(adata, control, num_boot=10000, num_cpus=1, fill_seed=0, ma
     n_conv = idx1.shape[0]
     first, members, c1, c2, true_corr, skip, bounds = _pair_plan(m, st, num_boot, max_rows)
     P_ = len(first)
+    chain_key = np.arange(P_ * ng, dtype=np.int64)        # rng='fast': stream key of (pair k, group) = k * n_groups + group
     live = ~skip.reshape(-1)
     r1a, r1b, r0 = (np.zeros(P_ * ng) for _ in range(3))
     u = np.random.random(3 * int(live.sum()))            # r = random(2) then r0 = random() per live (pair, group), in order
@@ -1153,7 +1170,8 @@ def ht_2d_vs_control(adata, control, num_boot=10000, num_cpus=1, fill_seed=0, ma
             return a[sl].reshape(n_ch, ng)[so].reshape(-1)
 
         bs.run(to_dev_order(skip.reshape(-1)), to_dev_order(r1a), to_dev_order(r1b), to_dev_order(r0),
-               to_dev_order(np.where(skip, np.nan, true_corr).reshape(-1)))
+               to_dev_order(np.where(skip, np.nan, true_corr).reshape(-1)), fast=(rng == 'fast'), fast_seed=fill_seed,
+               pair_key=to_dev_order(chain_key))
         good = bs.active.reshape(n_ch, ng)                # device order
         test_pair = np.repeat(np.arange(n_ch), n_t)       # pair-major: a pair's control rows stay in L2 for its consecutive guides
         if designs is None:

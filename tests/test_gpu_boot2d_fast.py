@@ -1,0 +1,380 @@
+"""GPU tests of rng='fast' on the gene-pair (2D) path: the replicate-parallel kernel mm_boot2d_fast (one wave per 64 replicates of
+one (pair, group) chain, every replicate on its own counter-derived PCG64 stream), Bootstrap2D.run(fast=True), and
+ht_2d_moments / ht_2d_vs_control(rng='fast').
+
+The kernel problem follows test_gpu_kernels_2d: groups of 17,003 (three count blocks) / 8,192 / 300 / 6 cells, 150 genes, the
+6-cell group in one size-factor bin (chains with K == 1), and a pair list with two highly expressed genes (chains of thousands
+of bins, ordered on the host), a never-expressed gene (zero variance: the 5.0 sentinel), a duplicated pair and a pair with its
+reverse.  The fast streams are not numpy's, so nothing is compared draw for draw: the kernel's arithmetic is checked against the
+oracle's formulas on the kernel's OWN dumped weights, the weights against the multinomial law, and the API against the replay
+mode (the parent's kernel, the yardstick) at the Monte-Carlo error of two independent bootstraps.
+"""
+
+import contextlib
+import os
+from types import SimpleNamespace
+
+import numpy as np
+import pandas as pd
+import pytest
+import scipy.sparse as sp
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLDEN = os.path.join(ROOT, "tests", "golden")
+
+N_SF_BINS = 30
+N_GENES = 150
+H0, H1, H2 = 0, 1, 2    # highly expressed genes
+NEVER = 3               # never expressed
+ONE_GROUP = 7           # expressed in group 0 only: (ONE_GROUP, NEVER) has one bin in the 6-cell group
+Q_GROUP = 0.07
+SIZES = (17003, 8192, 300, 6)
+Z_SEED = 11             # fast_seed of the multinomial test; numpy's own multinomial passes the same bound with this seed (checked in the test)
+
+SPECIAL_PAIRS = [(H0, H1), (H1, H0), (H0, H2), (H2, H2), (H0, 70), (30, 30), (40, 41), (41, 40), (50, 51), (50, 51), (20, 21),
+                 (NEVER, 60), (60, NEVER), (ONE_GROUP, NEVER), (63, 64), (127, 128), (N_GENES - 1, 65)] + [(10, j) for j in (100, 101, 102, 149)]
+Z_PAIRS = [(H0, 70), (40, 41), (41, 40), (50, 51), (50, 51), (60, NEVER)]
+
+
+def _problem(seed=2024):
+    rng = np.random.default_rng(seed)
+    ng = len(SIZES)
+    gid = np.concatenate([np.full(s, g, dtype=np.int32) for g, s in enumerate(SIZES)] + [np.full(150, -1, dtype=np.int32)])
+    rng.shuffle(gid)
+    n = len(gid)
+    X = rng.poisson(rng.uniform(0.05, 0.9, size=N_GENES) * rng.gamma(2.0, 0.5, size=(n, N_GENES))).astype(np.int64)
+    X[:, H0] = rng.poisson(rng.gamma(3.0, 2.5, size=n))
+    X[:, H1] = rng.poisson(rng.gamma(3.0, 2.0, size=n))
+    X[:, H2] = rng.poisson(rng.gamma(5.0, 1.1, size=n))
+    X[:, NEVER] = 0
+    X[gid != 0, ONE_GROUP] = 0
+    sf = rng.lognormal(0.0, 0.3, size=n)
+    sf_bin = rng.integers(0, N_SF_BINS, size=n).astype(np.uint8)
+    sf_bin[gid == ng - 1] = 4                                 # the 6-cell group sits in one size-factor bin: chains with K == 1
+    return SimpleNamespace(X=X, csr=sp.csr_matrix(X.astype(np.float32)), gid=gid, ng=ng, sf=sf, sf_bin=sf_bin,
+                           sf_table=np.linspace(0.4, 2.5, N_SF_BINS), sel=[np.flatnonzero(gid == g) for g in range(ng)],
+                           grp_q=np.full(ng, Q_GROUP))
+
+
+def _pairs(special):
+    fill = [(i, j) for i in range(80, 140, 3) for j in range(i + 1, i + 4) if j < N_GENES] if special is SPECIAL_PAIRS else []
+    p = np.array(list(special) + fill, dtype=np.int64)
+    return p[:, 0], p[:, 1]
+
+
+@pytest.fixture(scope="module")
+def eng():
+    from scrna_parameter_estimation_amd import engine
+
+    engine._lib.load(require_gpu=True)
+    return engine
+
+
+@pytest.fixture(scope="module")
+def orc():
+    from oracle import memento_oracle
+
+    return memento_oracle
+
+
+@pytest.fixture(scope="module")
+def prob():
+    return _problem()
+
+
+@pytest.fixture(scope="module")
+def dev_cols(eng, prob):
+    blocks = eng.CountBlocks(eng.DeviceCSR(prob.csr), prob.gid, prob.ng)
+    _, _, maxx = blocks.moments(1.0 / prob.sf)
+    return blocks, eng.GeneColumns(blocks, np.arange(N_GENES)), maxx
+
+
+def _boot(eng, orc, prob, dev_cols, special, B, useed):
+    """Bootstrap2D of a pair list (histograms and bin counts done), its hash uniforms, true correlations and skip flags, all in
+    the device's pair order.  The duplicated pair gets the same uniforms twice and the reversed pair its partner's, swapped: those
+    chains have equal operands bin for bin."""
+    blocks, cols, maxx = dev_cols
+    c1, c2 = _pairs(special)
+    bs = eng.Bootstrap2D(cols, c1, c2, maxx, prob.sf_bin, prob.sf_table, prob.grp_q, B)
+    c1, c2 = c1[bs.order], c2[bs.order]
+    X64 = sp.csc_matrix(prob.X.astype(np.float64))
+    tc = np.empty((len(c1), prob.ng))
+    for g, sel in enumerate(prob.sel):
+        cov = orc.cov_2d_sparse(X64[sel], prob.sf[sel], Q_GROUP, c1, c2)
+        _, var = orc.moments_1d_sparse(X64[sel], prob.sf[sel], Q_GROUP)
+        tc[:, g] = orc.corr_from_cov(cov, var[c1], var[c2])
+    with np.errstate(invalid="ignore"):
+        skip = np.isnan(tc) | (np.abs(tc) == 1)               # the API's rule (hypothesis_test.py:325)
+    skip[(c1 == 60) & (c2 == NEVER)] = False                  # left live on purpose: the kernel itself meets the zero variances
+    skip[(c1 == H2) & (c2 == H2)] = False
+    skip[:, prob.ng - 1] = (c1 == NEVER) & (c2 == 60)         # ... and the chains of the 6-cell group, K == 1 among them
+    u = np.random.default_rng(useed).random((3, len(c1), prob.ng))
+    dup = np.flatnonzero((c1 == 50) & (c2 == 51))
+    fwd, rev = np.flatnonzero((c1 == 40) & (c2 == 41)), np.flatnonzero((c1 == 41) & (c2 == 40))
+    assert len(dup) == 2 and len(fwd) == 1 and len(rev) == 1
+    u[:, dup[1]] = u[:, dup[0]]
+    u[0, rev[0]], u[1, rev[0]], u[2, rev[0]] = u[1, fwd[0]], u[0, fwd[0]], u[2, fwd[0]]
+    return SimpleNamespace(bs=bs, c1=c1, c2=c2, B=B, true_corr=tc.reshape(-1), skip=skip.reshape(-1), ra=u[0].reshape(-1),
+                           rb=u[1].reshape(-1), r0=u[2].reshape(-1), twins=[(dup[0], dup[1]), (fwd[0], rev[0])])
+
+
+def _chain_bins(orc, prob, bt, q):
+    """The oracle's bins of chain q in replay order: (1/sf, 1/sf^2, x_i, x_j, multiplicity) and the per-cell inputs."""
+    p, g = divmod(int(q), prob.ng)
+    sel = prob.sel[g]
+    xi, xj, sf = prob.X[sel, bt.c1[p]].astype(np.float64), prob.X[sel, bt.c2[p]].astype(np.float64), prob.sf_table[prob.sf_bin[sel]]
+    return orc.unique_bins_2d(xi, xj, sf, (bt.ra[q], bt.rb[q]), bt.r0[q]), (xi, xj, sf)
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# 1. the kernel's arithmetic is exact given its own weights
+# ------------------------------------------------------------------------------------------------------------------------
+
+
+@pytest.mark.parametrize("B", [130, 64, 1])
+def test_replicates_are_the_oracles_formulas_on_the_dumped_weights(eng, orc, prob, dev_cols, monkeypatch, B):
+    """Bootstrap2D.run(fast=True, dump_weights=True) at B = 130 (two full 64-replicate chunks and a ragged one of 2), 64 and 1.  For
+    every active chain: every replicate column of the dumped weights is non-negative and sums to the group's cell count, and
+    oracle.bootstrap_2d / corr_from_cov evaluated ON THOSE WEIGHTS (the oracle's own multinomial draw replaced by them, its bins
+    and formulas untouched; 5.0 sentinel and clip included) give yc[q, 1:] at the tolerance of test_replicate_correlations_vs_oracle.
+    Chains with K == 1 equal the replay kernel's rows exactly; skipped and inactive rows are NaN beyond column 0."""
+    bt = _boot(eng, orc, prob, dev_cols, SPECIAL_PAIRS, B, 77)
+    bs = bt.bs
+    bs.run(bt.skip, bt.ra, bt.rb, bt.r0, bt.true_corr, fast=True, fast_seed=3, dump_weights=True)
+    assert bs.replay_kernel == "mm_boot2d_fast" and bs.n_tiles >= 2
+    yc = eng.host(bs.yc).copy()
+    active = ~bt.skip & (bs.K >= 1)
+    np.testing.assert_array_equal(bs.active, active)
+    np.testing.assert_array_equal(yc[:, 0], bt.true_corr)
+    assert np.isnan(yc[~active, 1:]).all() and np.isfinite(yc[active, 1:]).all() and (~active).sum() >= 5
+    assert bs.order_path["host"] >= 1 and bs.order_path["small"] > 64 and bs.K.max() > 4096
+    sentinels = k1 = 0
+    for q in np.flatnonzero(active):
+        (a, b, e1, e2, mult), (xi, xj, sf) = _chain_bins(orc, prob, bt, q)
+        n, K = len(xi), int(bs.K[q])
+        w = bs.weights_of(q)
+        assert w.shape == (K, B) and len(mult) == K and w.dtype == np.int32
+        assert (w >= 0).all() and (w.sum(axis=0) == n).all(), q
+        with monkeypatch.context() as mp:
+            mp.setattr(orc, "multinomial_weights", lambda n_obs, m, nb, w=w: w.astype(np.int64))
+            cov, v1, v2 = orc.bootstrap_2d(xi, xj, sf, Q_GROUP, B, (bt.ra[q], bt.rb[q]), bt.r0[q])
+        want = orc.corr_from_cov(cov, v1, v2)
+        np.testing.assert_allclose(yc[q, 1:], want, rtol=1e-9, atol=1e-12, err_msg=f"chain {q} (K = {K}, {n} cells)")
+        sent = (v1 <= 0) | (v2 <= 0)
+        np.testing.assert_array_equal(yc[q, 1:][sent], want[sent])
+        assert (want[sent] == 1.0).all() and (np.abs(yc[q, 1:]) <= 1).all()
+        sentinels += int(sent.sum())
+        if K == 1:
+            assert (w == n).all()
+            k1 += 1
+    print(f"\nB = {B}: {int(active.sum())} chains in {bs.n_tiles} tiles, {sentinels} sentinel replicates, {k1} chains with K == 1")
+    assert sentinels >= B and k1 >= 1
+    fast_k1 = yc[bs.K == 1]
+    bs.run(bt.skip, bt.ra, bt.rb, bt.r0, bt.true_corr)            # the replay kernel on the same chains
+    assert bs.replay_kernel == "mm_boot2d_replay_rec" and bs.w_dump is None
+    np.testing.assert_array_equal(fast_k1, eng.host(bs.yc)[bs.K == 1])
+    with pytest.raises(ValueError):
+        bs.run(bt.skip, bt.ra, bt.rb, bt.r0, bt.true_corr, dump_weights=True)
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# 2. the weights are multinomial and the streams are distinct
+# ------------------------------------------------------------------------------------------------------------------------
+
+
+def _max_abs_z(mean_w, mult, n, B):
+    p = mult / n
+    return float(np.abs((mean_w - n * p) / np.sqrt(n * p * (1 - p) / B)).max())
+
+
+def test_weights_are_multinomial_and_streams_distinct(eng, orc, prob, dev_cols):
+    """B = 2,048, fast_seed = Z_SEED.  For every bin of every chain with n >= 300 cells (the three large groups of every pair of
+    Z_PAIRS; only the 6-cell group is left out) z = (mean_r w_k - n p_k) / sqrt(n p_k (1 - p_k) / B) has max |z| < 5: with the few
+    thousand bins here a correct sampler misses that by chance less than once in 1e3 seeds (2 * Phi(-5) = 5.7e-7 per bin).
+    numpy's own multinomial with the same seed on the same chains is held to the same bound first, on the host.  Within a chain of
+    K >= 50 no two replicate columns are equal (columns of different 64-chunks and of the same lane in different chunks
+    included), and two chains with equal operands -- the duplicated pair, the pair and its reverse -- share no column."""
+    B = 2048
+    bt = _boot(eng, orc, prob, dev_cols, Z_PAIRS, B, 78)
+    bs = bt.bs
+    active = ~bt.skip & (bs.K >= 1)
+    chains = [q for q in np.flatnonzero(active) if SIZES[q % prob.ng] >= 300]
+    assert len(chains) == 3 * len(Z_PAIRS)                         # every chain of the three large groups is live
+    bins = {q: _chain_bins(orc, prob, bt, q)[0][4] for q in chains}
+    gen = np.random.Generator(np.random.PCG64(Z_SEED))
+    z_numpy = max(_max_abs_z(gen.multinomial(SIZES[q % prob.ng], bins[q] / bins[q].sum(), size=B).mean(axis=0), bins[q], SIZES[q % prob.ng], B)
+                  for q in chains)
+    n_bins = sum(len(m) for m in bins.values())
+    assert z_numpy < 5 and n_bins > 3000, (z_numpy, n_bins)
+    bs.run(bt.skip, bt.ra, bt.rb, bt.r0, bt.true_corr, fast=True, fast_seed=Z_SEED, dump_weights=True)
+    proj = np.random.default_rng(1).integers(1, 1 << 30, size=int(bs.K.max()), dtype=np.int64)
+    z_max, n_long, W = 0.0, 0, {}
+    for q in chains:
+        w = W[q] = bs.weights_of(q)
+        n, K = SIZES[q % prob.ng], int(bs.K[q])
+        assert len(bins[q]) == K and (w.sum(axis=0) == n).all() and (w >= 0).all()
+        z_max = max(z_max, _max_abs_z(w.mean(axis=1), bins[q], n, B))
+        if K >= 50:
+            h = proj[:K] @ w.astype(np.int64)                      # equal columns have equal projections
+            if len(np.unique(h)) < B:
+                assert len(np.unique(w.T, axis=0)) == B, f"chain {q}: two replicates drew the same weights"
+            n_long += 1
+    print(f"\n{len(chains)} chains, {n_bins} bins, B = {B}: max |z| = {z_max:.3f} (numpy's multinomial, seed {Z_SEED}: {z_numpy:.3f}); "
+          f"{n_long} chains with K >= 50")
+    assert n_long >= 10
+    n_twins = 0
+    for pa, pb in bt.twins:
+        for g in range(3):
+            qa, qb = pa * prob.ng + g, pb * prob.ng + g
+            np.testing.assert_array_equal(bins[qa], bins[qb])       # equal operands: same bins in the same order
+            assert (W[qa] != W[qb]).any(axis=0).all() if bs.K[qa] >= 50 else (W[qa] != W[qb]).any(), (qa, qb)
+            n_twins += 1
+    assert n_twins == 6
+    assert z_max < 5, z_max
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# 3. - 5. the API
+# ------------------------------------------------------------------------------------------------------------------------
+
+
+def _api_small_adata(g):
+    from scrna_parameter_estimation_amd import AnnDataLite, memento
+
+    X = sp.csr_matrix((g["in_data"].astype(np.float32), g["in_indices"], g["in_indptr"]), shape=tuple(g["in_shape"]))
+    obs = pd.DataFrame({"cond": g["in_cond"], "rep": g["in_rep"], "q": g["in_q"]}, index=[f"c{i}" for i in range(X.shape[0])])
+    adata = AnnDataLite(X, obs, pd.DataFrame(index=g["in_gene_names"].tolist()))
+    memento.setup_memento(adata, q_column="q")
+    memento.create_groups(adata, label_columns=["cond", "rep"])
+    memento.compute_1d_moments(adata, min_perc_group=0.7)
+    names = np.asarray(adata.var.index)
+    memento.compute_2d_moments(adata, list(zip(names[g["pair_idx1"]].tolist(), names[g["pair_idx2"]].tolist())))
+    gdf = memento.get_groups(adata)
+    cov = pd.DataFrame(g["covariate"], index=gdf.index, columns=["intercept"])
+    trt = pd.DataFrame(g["treatment"], index=gdf.index, columns=["cond"])
+    return memento, adata, cov, trt
+
+
+def _ht2(memento, adata, cov, trt, B, seed, **kw):
+    np.random.seed(seed)
+    memento.ht_2d_moments(adata, covariate=cov, treatment=trt, num_boot=B, num_cpus=1, verbose=0, resampling="bootstrap", **kw)
+    m = adata.uns["memento"]
+    return {k: np.asarray(m["2d_ht"][k]).copy() for k in ("corr_coef", "corr_se", "corr_asl")}, m["_hip"].last_bootstrap2d.replay_kernel
+
+
+@contextlib.contextmanager
+def _replay_with_pcg_seed(eng, seed):
+    """Inside, Bootstrap2D.run replays numpy's PCG64(seed) stream instead of PCG64(5): a second, independent replay bootstrap."""
+    run = eng.Bootstrap2D.run
+
+    def run_seeded(self, *args, **kw):
+        return run(self, *args, **dict(kw, pcg_seed=seed))
+
+    eng.Bootstrap2D.run = run_seeded
+    try:
+        yield
+    finally:
+        eng.Bootstrap2D.run = run
+
+
+def _rel(se_a, se_b):
+    ok = np.isfinite(se_a) & np.isfinite(se_b)
+    return np.abs(se_a[ok] / se_b[ok] - 1)
+
+
+def test_api_is_deterministic_seeded_and_chunk_invariant(api_small):
+    """ht_2d_moments(rng='fast', B = 200, approx=True): the same np.random seed and fill_seed give bit-identical corr_se / corr_asl;
+    so does the same call in >= 3 pair chunks (max_rows); another fill_seed changes corr_se and leaves corr_coef bit-identical."""
+    memento, adata, cov, trt = _api_small_adata(api_small)
+    seed = int(api_small["ht_seed"]) + 1
+    a, kern = _ht2(memento, adata, cov, trt, 200, seed, approx=True, rng="fast", fill_seed=7)
+    assert kern == "mm_boot2d_fast" and np.isfinite(a["corr_se"]).sum() >= 8
+    b, _ = _ht2(memento, adata, cov, trt, 200, seed, approx=True, rng="fast", fill_seed=7)
+    for k in a:
+        np.testing.assert_array_equal(a[k], b[k], err_msg=k)
+    c, _ = _ht2(memento, adata, cov, trt, 200, seed, approx=True, rng="fast", fill_seed=7, max_rows=12)
+    lo, hi = adata.uns["memento"]["_hip"].last_chunk2d
+    n_distinct = len({frozenset(p) for p in zip(api_small["pair_idx1"].tolist(), api_small["pair_idx2"].tolist()) if p[0] != p[1]})
+    assert hi == n_distinct and hi - lo <= 3 and n_distinct > 2 * 3, (lo, hi, n_distinct)      # 12 rows / 4 groups: 3 pairs per chunk
+    for k in a:
+        np.testing.assert_array_equal(a[k], c[k], err_msg=f"{k}: chunked")
+    d, _ = _ht2(memento, adata, cov, trt, 200, seed, approx=True, rng="fast", fill_seed=8)
+    np.testing.assert_array_equal(a["corr_coef"], d["corr_coef"])
+    fin = np.isfinite(a["corr_se"])
+    assert (a["corr_se"][fin] != d["corr_se"][fin]).all()
+
+
+def test_api_small_fast_is_statistically_the_replay_mode(api_small, eng):
+    """api_small's inputs and pair list at B = 2,000: corr_coef equals the fixture's ht2_corr_coef (1e-8) with the same NaN set, and
+    rel = se_fast / se_replay - 1 over the finite SEs has median |rel| < 2 / sqrt(B) and p90 |rel| < 4 / sqrt(B): two independent
+    bootstrap SEs of a near-normal statistic differ by about 1 / sqrt(B) relative sd (2.2 % here).  The replay kernel is the
+    yardstick, and it is held to the same bound against itself first: replay with PCG64(5) against replay with PCG64(6).
+    The test prints both pairs of figures before it asserts."""
+    B = 2000
+    memento, adata, cov, trt = _api_small_adata(api_small)
+    seed = int(api_small["ht_seed"]) + 1
+    rep5, kern = _ht2(memento, adata, cov, trt, B, seed, approx=True)
+    assert kern == "mm_boot2d_replay_rec"
+    with _replay_with_pcg_seed(eng, 6):
+        rep6, _ = _ht2(memento, adata, cov, trt, B, seed, approx=True)
+    fast, kern = _ht2(memento, adata, cov, trt, B, seed, approx=True, rng="fast", fill_seed=1)
+    assert kern == "mm_boot2d_fast"
+    np.testing.assert_allclose(fast["corr_coef"], api_small["ht2_corr_coef"], rtol=1e-8, atol=1e-12, equal_nan=True)
+    np.testing.assert_array_equal(fast["corr_coef"], rep5["corr_coef"])
+    np.testing.assert_array_equal(np.isnan(fast["corr_se"]), np.isnan(rep5["corr_se"]))
+    np.testing.assert_array_equal(np.isnan(fast["corr_se"]), np.isnan(api_small["ht2_corr_se"]))
+    rr, rf = _rel(rep6["corr_se"], rep5["corr_se"]), _rel(fast["corr_se"], rep5["corr_se"])
+    print(f"\nB = {B}, {len(rf)} finite SEs: replay(6) / replay(5): median |rel| {np.median(rr):.4f}, p90 {np.percentile(rr, 90):.4f}; "
+          f"fast / replay(5): median |rel| {np.median(rf):.4f}, p90 {np.percentile(rf, 90):.4f}; bounds {2 / np.sqrt(B):.4f}, {4 / np.sqrt(B):.4f}")
+    assert len(rf) >= 8 and (rep6["corr_se"][np.isfinite(rep6["corr_se"])] != rep5["corr_se"][np.isfinite(rep5["corr_se"])]).all()
+    assert np.median(rr) < 2 / np.sqrt(B) and np.percentile(rr, 90) < 4 / np.sqrt(B)        # the yardstick against itself
+    assert np.median(rf) < 2 / np.sqrt(B) and np.percentile(rf, 90) < 4 / np.sqrt(B)
+
+
+def test_vs_control_fast_matches_replay(eng):
+    """ht_2d_vs_control(rng='fast') on the guide_loop_2d fixture's inputs (B = 2,000): the rows, corr_coef and the NaN pattern are
+    those of the rng='replay' call, the kernel is mm_boot2d_fast, and corr_se stays within the bound of the api_small test
+    (median |se_fast / se_replay - 1| < 2 / sqrt(B), p90 < 4 / sqrt(B)), which two replay runs (PCG64(5), PCG64(6)) meet as well.
+    The test prints both pairs of figures before it asserts."""
+    from scrna_parameter_estimation_amd import AnnDataLite, memento
+
+    B = 2000
+    g = dict(np.load(os.path.join(GOLDEN, "guide_loop_2d.npz"), allow_pickle=False))
+    X = sp.csr_matrix((g["in_data"].astype(np.float32), g["in_indices"], g["in_indptr"]), shape=tuple(g["in_shape"]))
+    obs = pd.DataFrame({"guide": g["in_guide"], "rep": g["in_rep"], "q": g["in_q"]}, index=[f"c{i}" for i in range(X.shape[0])])
+    adata = AnnDataLite(X, obs, pd.DataFrame(index=g["in_gene_names"].tolist()))
+    memento.setup_memento(adata, q_column="q")
+    memento.create_groups(adata, label_columns=["guide"])
+    memento.compute_1d_moments(adata, min_perc_group=0.9)
+    kept = set(memento.main._var_names(adata).tolist())
+    pairs = [(a, b) for a, b in zip(g["in_pair_1"].tolist(), g["in_pair_2"].tolist()) if a in kept and b in kept]
+    assert len(pairs) > 40
+    memento.compute_2d_moments(adata, pairs)
+    st = adata.uns["memento"]["_hip"]
+
+    def call(**kw):
+        np.random.seed(5)
+        df = memento.ht_2d_vs_control(adata, control="sg^0", num_boot=B, num_cpus=1, approx=True, **kw)
+        return df, st.last_bootstrap2d.replay_kernel, np.random.random()
+
+    rep5, kern, after = call()
+    assert kern == "mm_boot2d_replay_rec"
+    with _replay_with_pcg_seed(eng, 6):
+        rep6, _, _ = call(rng="replay")
+    fast, kern, after_fast = call(rng="fast", fill_seed=2)
+    assert kern == "mm_boot2d_fast" and after_fast == after       # the global stream is consumed identically
+    assert len(fast) == len(rep5) == len(pairs) * int(g["n_guides"])
+    for col in ("gene_1", "gene_2", "group"):
+        assert (fast[col].values == rep5[col].values).all()
+    np.testing.assert_array_equal(fast["corr_coef"].values, rep5["corr_coef"].values)
+    for col in ("corr_se", "corr_pval"):
+        np.testing.assert_array_equal(np.isnan(fast[col].values), np.isnan(rep5[col].values))
+    rr, rf = _rel(rep6["corr_se"].values, rep5["corr_se"].values), _rel(fast["corr_se"].values, rep5["corr_se"].values)
+    print(f"\nB = {B}, {len(rf)} finite SEs: replay(6) / replay(5): median |rel| {np.median(rr):.4f}, p90 {np.percentile(rr, 90):.4f}; "
+          f"fast / replay(5): median |rel| {np.median(rf):.4f}, p90 {np.percentile(rf, 90):.4f}; bounds {2 / np.sqrt(B):.4f}, {4 / np.sqrt(B):.4f}")
+    assert len(rf) > 100
+    pv = fast["corr_pval"].values
+    assert ((pv[np.isfinite(pv)] >= 0) & (pv[np.isfinite(pv)] <= 1)).all()
+    assert np.median(rr) < 2 / np.sqrt(B) and np.percentile(rr, 90) < 4 / np.sqrt(B)        # the yardstick against itself
+    assert np.median(rf) < 2 / np.sqrt(B) and np.percentile(rf, 90) < 4 / np.sqrt(B)

@@ -4,7 +4,8 @@ per-guide loop the reference's analyses use (subset to {control, guide} -> ht_2d
 ht_2d_moments over the subsets, timed on --loop-guides guides and scaled to all of them).
 With --strata R every cell also gets a replicate 0..R-1 (column ``rep``): the groups are guide x replicate and the call is
 ht_2d_vs_control(..., treatment_col='guide') with the replicate as covariate.
-usage: python tools/bench_vs_control_2d.py [--strata R] [--loop-guides K] [--repeat N] [cells genes n_guides n_pairs num_boot]"""
+--rng fast runs the batched call with the replicate-parallel bootstrap (mm_boot2d_fast) instead of the replay kernel (the default).
+usage: python tools/bench_vs_control_2d.py [--strata R] [--loop-guides K] [--repeat N] [--rng replay|fast] [cells genes n_guides n_pairs num_boot]"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, pandas as pd, torch, scipy.sparse as sp
@@ -12,10 +13,10 @@ import bench
 from scrna_parameter_estimation_amd import AnnDataLite, engine, memento
 
 
-def _opt(name, default):
+def _opt(name, default, conv=int):
     if name in sys.argv:
         i = sys.argv.index(name)
-        v = int(sys.argv[i + 1])
+        v = conv(sys.argv[i + 1])
         del sys.argv[i:i + 2]
         return v
     return default
@@ -23,6 +24,9 @@ def _opt(name, default):
 
 def main():
     strata, loop_guides, repeat = _opt("--strata", 1), _opt("--loop-guides", 10), _opt("--repeat", 3)
+    rng_mode = _opt("--rng", "replay", str)
+    if rng_mode not in ("replay", "fast"):
+        sys.exit("--rng must be replay or fast")
     cells, genes, n_guides, n_pairs, B = [int(x) for x in sys.argv[1:6]] if len(sys.argv) > 5 else (200_000, 15_000, 500, 2_000, 5_000)
     csr = bench.synth_device_csr(dict(cells=cells, genes=genes, density=0.05), 20250117 + 7, torch)
     rng = np.random.default_rng(20250117 + 7)
@@ -49,6 +53,9 @@ def main():
     torch.cuda.synchronize(); t1 = time.time()
     ctrl = [g for g in m["groups"] if g.split("^")[-1] == "0"][0] if strata == 1 else 0
     kw = dict(treatment_col="guide") if strata > 1 else {}
+    if rng_mode != "replay":
+        kw["rng"] = rng_mode
+        print(f"rng = {rng_mode!r}", flush=True)
     print(f"setup + moments {t1 - t0:.2f}s; genes kept {len(names)} groups {len(m['groups'])} pairs {n_pairs} (among the {n_top} best expressed "
           f"genes) B {B}", flush=True)
     times = []
