@@ -260,14 +260,18 @@ int mm_boot1d_async(const double *d_ops, const int64_t *d_ch_base, const int32_t
                     int32_t mean_only, int64_t ld, double *d_out_mean, double *d_out_var, int32_t *d_w_dump, int32_t kmax_dump,
                     void *stream);
 
-/* FAST mode of K6+K7: one lane = one replicate, one wave = 64 replicates of one pair; every (pair, replicate)
- * has its own PCG64 stream derived from (seed, row, replicate).  Same sampler code and moment arithmetic as the
- * replay kernel, different random numbers: statistically equivalent to the reference, not draw-for-draw
- * identical.  n_slots = number of slots in the tile layout written by mm_bins_order (64 * n_tiles). */
+/* FAST mode of K6+K7 (rng='fast'): one lane = one replicate, one wave = 64 replicates of one (gene, group) chain.  n_slots =
+ * number of slots in the tile layout written by mm_bins_order (64 * n_tiles); d_slot_K[s] < 2 or d_slot_row[s] < 0 = nothing is
+ * written.  Replicate r of slot s owns the PCG64 stream derived from (seed, d_slot_key[s], r) -- d_slot_row[s] addresses the output
+ * row only: keys that number the chains independently of gene chunking, sharding and layout make the result independent of all
+ * three.  Same sampler code and moment arithmetic as the replay kernel, different random numbers: statistically equivalent to
+ * the reference, not draw-for-draw identical.  d_w_dump (optional, NULL in production): int32 weights
+ * [slot][k < kmax_dump][r < num_boot]. */
 int mm_boot1d_fast(const double *d_pk, const double *d_lq, const double *d_v, const double *d_a, const double *d_b,
                    const int64_t *d_tile_ptr, int64_t n_slots, const int32_t *d_slot_K, const double *d_slot_nobs,
-                   const double *d_slot_omq, const int64_t *d_slot_row, uint64_t seed, int32_t num_boot, int32_t mean_only,
-                   int64_t ld, double *d_out_mean, double *d_out_var, void *stream);
+                   const double *d_slot_omq, const int64_t *d_slot_row, const int64_t *d_slot_key, uint64_t seed, int32_t num_boot,
+                   int32_t mean_only, int64_t ld, double *d_out_mean, double *d_out_var, int32_t *d_w_dump, int32_t kmax_dump,
+                   void *stream);
 
 /* ---- K8: residual variance, invalid-replicate fill, log  ---------------------------------------
  * replaces estimator._residual_variance + hypothesis_test._fill + np.log

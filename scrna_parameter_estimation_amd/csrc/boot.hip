@@ -566,17 +566,21 @@ __global__ __launch_bounds__(256) void k_boot_fill_log(double *__restrict__ mean
 // FAST mode (rng='fast'): the same multinomial chain and replicate moments, but one lane = one REPLICATE and
 // one wave = 64 replicates of ONE (gene, group) pair.  Every lane of a wave walks the same bins, so the
 // operands are wave-uniform, lanes take the same sampler (inversion or BTPE) at each step, and pairs x
-// replicates give the chip millions of independent chains.  Each (pair, replicate) owns a PCG64 stream
-// derived from (seed, pair, replicate) -- NOT numpy's single stream: results are statistically equivalent
-// to the reference (same algorithm, different random numbers), not draw-for-draw identical.
+// replicates give the chip millions of independent chains.  Replicate r of the chain with key ``slot_key[slot]`` owns the
+// PCG64 stream derived from (seed, key, r) -- NOT numpy's single stream: results are statistically equivalent
+// to the reference (same algorithm, different random numbers), not draw-for-draw identical.  The caller's keys number the
+// (gene, group) chains independently of gene chunking, of sharding and of the tile layout, so none of them changes a result;
+// ``slot_row`` addresses the output row only.  Lanes beyond num_boot walk along and store nothing.
+// w_dump (optional): int32 weights [slot][k < kmax_dump][r < num_boot].
 __global__ __launch_bounds__(256) void k_boot1d_fast(const double *__restrict__ pk_, const double *__restrict__ lq_,
                                                      const double *__restrict__ v, const double *__restrict__ a,
                                                      const double *__restrict__ b, const int64_t *__restrict__ tile_ptr,
                                                      int64_t n_slots, const int32_t *__restrict__ slot_K,
                                                      const double *__restrict__ slot_nobs, const double *__restrict__ slot_omq,
-                                                     const int64_t *__restrict__ slot_row, uint64_t seed, int32_t num_boot,
-                                                     int32_t mean_only, int32_t chunks, int64_t ld,
-                                                     double *__restrict__ out_mean, double *__restrict__ out_var) {
+                                                     const int64_t *__restrict__ slot_row, const int64_t *__restrict__ slot_key,
+                                                     uint64_t seed, int32_t num_boot, int32_t mean_only, int32_t chunks, int64_t ld,
+                                                     double *__restrict__ out_mean, double *__restrict__ out_var,
+                                                     int32_t *__restrict__ w_dump, int32_t kmax_dump) {
   int lane = mm_lane();
   int64_t wid = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   int64_t slot = wid / chunks;
@@ -590,8 +594,9 @@ __global__ __launch_bounds__(256) void k_boot1d_fast(const double *__restrict__ 
   int64_t obase = tile_ptr[slot >> 6] * 64 + (slot & 63);
   double nobs = slot_nobs[slot], omq = slot_omq[slot];
   int32_t n = (int32_t)nobs;
-  uint64_t h = mix64(seed ^ mix64((uint64_t)row * 0x100000001B3ull + (uint64_t)r));
+  uint64_t h = mix64(seed ^ mix64((uint64_t)slot_key[slot] * 0x100000001B3ull + (uint64_t)r));
   npyrng::Pcg64 g{mix64(h), mix64(h + 1), mix64(h + 2), mix64(h + 3) | 1ull};
+  int32_t *wd = (w_dump && mine) ? w_dump + (slot * kmax_dump) * (int64_t)num_boot + r : nullptr;
   double M1 = 0.0, M2 = 0.0;
   int32_t dn = n;
   for (int k = 0; k < K; k++) {
@@ -603,6 +608,7 @@ __global__ __launch_bounds__(256) void k_boot1d_fast(const double *__restrict__ 
     } else {
       w = dn > 0 ? dn : 0;
     }
+    if (wd && k < kmax_dump) wd[(int64_t)k * num_boot] = w;
     accumulate_1d(M1, M2, w, v[o], a[o], b[o], omq);
   }
   if (mine) {
@@ -1093,17 +1099,20 @@ int mm_boot2d_fast(const double *d_pk, const double *d_lq, const double *d_v1, c
 
 int mm_boot1d_fast(const double *d_pk, const double *d_lq, const double *d_v, const double *d_a, const double *d_b,
                    const int64_t *d_tile_ptr, int64_t n_slots, const int32_t *d_slot_K, const double *d_slot_nobs,
-                   const double *d_slot_omq, const int64_t *d_slot_row, uint64_t seed, int32_t num_boot, int32_t mean_only,
-                   int64_t ld, double *d_out_mean, double *d_out_var, void *stream) {
-  MM_ARG(d_pk && d_lq && d_v && d_a && d_b && d_tile_ptr && d_slot_K && d_slot_nobs && d_slot_omq && d_slot_row);
+                   const double *d_slot_omq, const int64_t *d_slot_row, const int64_t *d_slot_key, uint64_t seed, int32_t num_boot,
+                   int32_t mean_only, int64_t ld, double *d_out_mean, double *d_out_var, int32_t *d_w_dump, int32_t kmax_dump,
+                   void *stream) {
+  MM_ARG(d_pk && d_lq && d_v && d_a && d_b && d_tile_ptr && d_slot_K && d_slot_nobs && d_slot_omq && d_slot_row && d_slot_key);
   MM_ARG(d_out_mean && d_out_var && n_slots >= 0 && num_boot > 0 && ld >= (int64_t)num_boot + 1);
+  MM_ARG(!d_w_dump || kmax_dump > 0);
   if (n_slots == 0) return MM_OK;
   int32_t chunks = (num_boot + 63) / 64;
   int64_t waves = n_slots * chunks;
   int64_t blocks = (waves + 3) / 4;
   MM_ARG(blocks < 2147483647LL);
   hipLaunchKernelGGL(k_boot1d_fast, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, d_pk, d_lq, d_v, d_a, d_b, d_tile_ptr,
-                     n_slots, d_slot_K, d_slot_nobs, d_slot_omq, d_slot_row, seed, num_boot, mean_only, chunks, ld, d_out_mean, d_out_var);
+                     n_slots, d_slot_K, d_slot_nobs, d_slot_omq, d_slot_row, d_slot_key, seed, num_boot, mean_only, chunks, ld, d_out_mean,
+                     d_out_var, d_w_dump, kmax_dump);
   MM_LAUNCH_CHECK();
   return MM_OK;
 }

@@ -704,19 +704,23 @@ class Bootstrap1D:
         self.yv[:, 0] = dev(np.asarray(true_rv_log, dtype=np.float64))
 
     def run(self, skip, r1, r0, mv_fit, fill_mode=0, fill_seed=0, dump_weights=False, pcg_seed=5, first_pair=0, target_waves=None,
-            fast=False, mean_only=False, fill_keys=None):
+            fast=False, mean_only=False, fill_keys=None, chain_keys=None):
         """Order bins, replay the bootstrap and fill/log for every pair >= ``first_pair`` that is not skipped.
 
         ``skip``[pair] bool; ``r1``/``r0``[pair] the two uniforms of bootstrap.py:62,65.  Rows below
         ``first_pair`` are left untouched (used by the strict replay driver).  ``fill_keys`` [pair] int64: keys of the device
-        refill streams (fill_mode 0; default: the row number).  Returns n_invalid
+        refill streams (fill_mode 0; default: the row number).  ``chain_keys`` [pair] int64 (``fast`` only; default: the row number):
+        replicate r of pair p draws from the PCG64 stream derived from (``fill_seed``, ``chain_keys[p]``, r), so keys that number the
+        (gene, group) chains independently of gene chunking and sharding make the result independent of both.  Returns n_invalid
         [n_pairs - first_pair][2] (host): invalid (mean, res_var) replicates per row, -1 = no valid one."""
+        if chain_keys is not None and np.shape(chain_keys) != (self.n_pairs,):
+            raise ValueError("chain_keys must have one key per pair")
         active = (~np.asarray(skip, dtype=bool)) & (self.K >= 2)
         active[:first_pair] = False
         c = self._choose_kernels(active, fast, target_waves)
         t = self._lay_out_operands(c, dump_weights)
         status, ordered = self._order_bins(c, t, r1, r0)
-        launched = self._launch(c, t, fast, mean_only, fill_seed, pcg_seed, dump_weights)
+        launched = self._launch(c, t, fast, mean_only, fill_seed, pcg_seed, dump_weights, chain_keys)
         st = int(status.item())
         del ordered, launched      # NB: every device operand must stay referenced until after the call that reads it
         if st & 2 or st & 4:
@@ -819,7 +823,7 @@ class Bootstrap1D:
         t.d_tile_ptr = d_tile_ptr
         return status, keep
 
-    def _launch(self, c, t, fast, mean_only, fill_seed, pcg_seed, dump_weights):
+    def _launch(self, c, t, fast, mean_only, fill_seed, pcg_seed, dump_weights, chain_keys=None):
         """The chain kernel on the side stream, beside it on the launch stream the async and the tile kernel.  Returns their device operands."""
         torch, s = _torch(), _stream()
         ng, B, ld = self.ng, self.B, self.ld
@@ -870,8 +874,12 @@ class Bootstrap1D:
                       pcg64_state(pcg_seed), B, int(mean_only), ld, P(self.ym), P(self.yv), P(self.w_dump_async), ka, s)
         chains = ctypes.byref(chain_tiles) if chain_tiles is not None else None
         if n_tiles and fast:
+            keys = np.arange(self.n_pairs, dtype=np.int64) if chain_keys is None else np.asarray(chain_keys, dtype=np.int64)
+            d_slot_key = dev(_per_slot(n_tiles * 64, c.slot_of, keys[c.order], 0, np.int64))
+            keep.append(d_slot_key)
             _lib.call("mm_boot1d_fast", *[P(o) for o in t.ops], P(t.d_tile_ptr), n_tiles * 64, P(d_slot_K), P(d_nobs), P(d_omq), P(d_slot_pair),
-                      int(fill_seed) & ((1 << 64) - 1), B, int(mean_only), ld, P(self.ym), P(self.yv), s)
+                      P(d_slot_key), int(fill_seed) & ((1 << 64) - 1), B, int(mean_only), ld, P(self.ym), P(self.yv), P(self.w_dump),
+                      kmax_dump, s)
         elif n_tiles and c.use_free:
             d_slot_rec = dev(t.slot_rec)
             keep.append(d_slot_rec)

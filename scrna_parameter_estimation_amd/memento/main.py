@@ -407,6 +407,8 @@ def ht_1d_moments(adata, covariate, treatment, treatment_for_gene=None, inplace=
     ``np.random`` state per (gene, group) (bootstrap.py:62, :65).
     ``rng='fast'``: same samplers and arithmetic, but every (pair, replicate) has its own counter-derived PCG64
     stream and replicates run in parallel lanes -- statistically equivalent, much faster, not draw-identical.
+    The streams are keyed by (``fill_seed``, the gene's position among the kept genes of the unsharded call, group, replicate),
+    so the result depends neither on ``max_rows`` nor on gene sharding; in a one-chunk unsharded call the key is the chain's row.
     ``strict=True`` additionally replays the reference's ``_fill`` draws from the global stream in gene order
     (exactly reproducible against the reference at ``num_cpus=1``; sequential, meant for validation);
     with ``strict=False`` invalid replicates are re-filled on the device with a counter-based RNG.
@@ -511,8 +513,9 @@ def ht_1d_moments(adata, covariate, treatment, treatment_for_gene=None, inplace=
             else:
                 draw_stream(0)
             keys = (fill_pos[g0:g1, None] * ng + np.arange(ng)[None, :]).reshape(-1)      # refill streams keyed by (gene, group)
+            chain_keys = (chain_pos[g0:g1, None] * ng + np.arange(ng)[None, :]).reshape(-1)     # rng='fast' streams, likewise
             n_inv = bs.run(skip, r1, r0, fit, fill_mode=0, fill_seed=fill_seed, fast=(rng == 'fast'), mean_only=mean_only,
-                           fill_keys=keys)                                                # K6-K8
+                           fill_keys=keys, chain_keys=chain_keys)                         # K6-K8
             bad_fill = (n_inv < 0).any(axis=1)
             # how much of the result depends on the device refill (strict=True replays the reference's own _fill draws instead):
             # chains / genes with at least one refilled replicate -- all others are bit-identical to the strict path
@@ -688,6 +691,12 @@ def ht_1d_moments(adata, covariate, treatment, treatment_for_gene=None, inplace=
     # results do not depend on gene chunking or on the sharding over GPUs
     fill_pos = (np.asarray(st.shard, dtype=np.int64)[st.gene_idx] if getattr(st, 'shard', None) is not None
                 else (gene_pos if gene_pos is not None else np.asarray(st.gene_idx, dtype=np.int64)))
+    # position of every kept gene among the KEPT genes of the unsharded call: keys the rng='fast' streams of its chains, so that
+    # neither gene chunking nor sharding changes a number -- and the key of a chain of an unsharded call is its row number in the
+    # one-chunk call, whose results are therefore those of row-keyed streams
+    chain_pos = np.arange(G_all, dtype=np.int64)
+    if sharded and not strict:
+        chain_pos = np.searchsorted(np.sort(np.concatenate(comm.allgather_objects(gene_pos))), gene_pos).astype(np.int64)
     st.refill_stats = dict(chains=0, chains_refilled=0, genes=0, genes_refilled=0, gene_refilled=np.zeros(G_all, dtype=bool))
     st.last_bootstrap = None                   # the previous call's replicate rows (GBs) go back to the caching allocator BEFORE this call allocates its own
     if max_rows is None:                       # replicate buffers sized to the free HBM (288 GB on MI355X)
@@ -769,6 +778,10 @@ def ht_1d_vs_control(adata, control, num_boot=10000, num_cpus=1, rng='replay', f
     stratum.  A test with no good guide or control group, or with no stratum holding both arms, is NaN.  The ``group``
     column of the result is then the guide value.
 
+    Genes run in chunks of at most ``max_rows`` replicate rows (default: a share of the free device memory).  The device refill
+    streams and, with ``rng='fast'``, the bootstrap streams are keyed by (``fill_seed``, gene, group) with the gene numbered over
+    the whole call, so the chunking changes no number; in a one-chunk call the key is the chain's row.
+
     Returns a DataFrame (gene, group, de_coef, de_se, de_pval, dv_coef, dv_se, dv_pval) and stores the arrays in
     ``uns['memento']['1d_ht_vs_control']``."""
     m = adata.uns['memento']
@@ -804,7 +817,9 @@ def ht_1d_vs_control(adata, control, num_boot=10000, num_cpus=1, rng='replay', f
         live = np.flatnonzero(~skip)
         u = np.random.random(2 * len(live))
         r1[live], r0[live] = u[0::2], u[1::2]
-        n_inv = bs.run(skip, r1, r0, fit, fill_mode=0, fill_seed=fill_seed, fast=(rng == 'fast'), mean_only=mean_only)
+        keys = np.arange(g0 * ng, g1 * ng, dtype=np.int64)      # (g0 + gene) * ng + group: the chain's row in the one-chunk call
+        n_inv = bs.run(skip, r1, r0, fit, fill_mode=0, fill_seed=fill_seed, fast=(rng == 'fast'), mean_only=mean_only,
+                       fill_keys=keys, chain_keys=keys)
         good = ((~skip) & (bs.K >= 2) & ~(n_inv < 0).any(axis=1)).reshape(G, ng)
         st.last_good = good                    # (diagnostics / tests: the good groups of the last gene chunk)
         test_gene = np.repeat(np.arange(G), len(tested))

@@ -57,6 +57,13 @@ np.savez(os.path.join(%(out)r, f"rank{comm.rank}.npz"), size_factor=adata.obs["m
          mean_coef=m["1d_ht"]["mean_coef"], var_coef=m["1d_ht"]["var_coef"], ht_names=np.array(m["1d_ht"]["gene_names"]),
          mean_se=m["1d_ht"]["mean_se"], mean_asl=m["1d_ht"]["mean_asl"], var_se=m["1d_ht"]["var_se"], var_asl=m["1d_ht"]["var_asl"],
          df_genes=np.array(memento.get_1d_ht_result(adata)["gene"].tolist()))
+if %(device_split)r:
+    # rng='fast' over the same two cost-balanced shards: the streams are keyed by the gene's position among ALL kept genes
+    np.random.seed(int(g["ht_seed"]))
+    memento.ht_1d_moments(adata, covariate=cov, treatment=trt, num_boot=int(g["num_boot"]), num_cpus=1, verbose=0, resampling="bootstrap",
+                          approx=True, rng="fast", fill_seed=7)
+    np.savez(os.path.join(%(out)r, f"fast_rank{comm.rank}.npz"), **{k: m["1d_ht"][k] for k in (
+        "mean_coef", "mean_se", "mean_asl", "var_coef", "var_se", "var_asl")})
 # 2D on pair blocks (every rank needs all genes' columns: a second, unsharded state on the same device)
 from scrna_parameter_estimation_amd.dist import shard_pairs, gather_pair_results
 ad2 = AnnDataLite(X, obs.copy(), pd.DataFrame(index=g["in_gene_names"].tolist()))
@@ -138,6 +145,17 @@ def test_two_gene_shards_equal_the_unsharded_reference(api_small, tmp_path, devi
                 np.testing.assert_allclose(p[k], one[k], rtol=1e-12, atol=1e-14, equal_nan=True, err_msg=k)
             for k in ("var_coef", "var_se", "var_asl"):
                 np.testing.assert_allclose(p[k], one[k], rtol=1e-6, atol=1e-9, equal_nan=True, err_msg=k)
+        # rng='fast' likewise: every (gene, group) chain draws from the streams it has in the 1-rank call
+        np.random.seed(int(g["ht_seed"]))
+        memento.ht_1d_moments(adata, covariate=cov, treatment=trt, num_boot=int(g["num_boot"]), num_cpus=1, verbose=0, resampling="bootstrap",
+                              approx=True, rng="fast", fill_seed=7)
+        one = adata.uns["memento"]["1d_ht"]
+        assert np.isfinite(one["mean_se"]).sum() > len(one["mean_se"]) // 2
+        for p in [dict(np.load(tmp_path / f"fast_rank{k}.npz")) for k in range(2)]:
+            for k in ("mean_coef", "mean_se", "mean_asl"):
+                np.testing.assert_allclose(p[k], one[k], rtol=1e-12, atol=1e-14, equal_nan=True, err_msg=f"rng='fast': {k}")
+            for k in ("var_coef", "var_se", "var_asl"):
+                np.testing.assert_allclose(p[k], one[k], rtol=1e-6, atol=1e-9, equal_nan=True, err_msg=f"rng='fast': {k}")
     # 2D: pair blocks reassembled in the caller's order == the unsharded fixture (moments exactly; observed coefficients too)
     pr = [dict(np.load(tmp_path / f"pairs_rank{k}.npz")) for k in range(2)]
     for p in pr:

@@ -149,6 +149,10 @@ def test_single_label_column_equals_the_unstratified_call_and_chunks_agree():
     assert (one["gene"].values == many["gene"].values).all() and (one["group"].values == many["group"].values).all()
     for k in ("de_coef", "dv_coef"):
         np.testing.assert_allclose(many[k].values, one[k].values, rtol=1e-12, atol=1e-12, equal_nan=True, err_msg=k)
+    # the replay streams are per chain and the refill streams are keyed by (gene, group): standard errors and p-values too
+    assert np.isfinite(one["de_se"].values).sum() > len(one) // 4
+    for k in KEYS:
+        np.testing.assert_array_equal(many[k].values, one[k].values, err_msg=k)
 
 
 CHILD = r'''
