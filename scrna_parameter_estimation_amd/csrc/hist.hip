@@ -1,5 +1,6 @@
 // hist.hip -- K5: integer (group, gene, sf_bin, count) histograms from the SELL count blocks, their
-// compaction into bins, and the np.unique replay ORDER of the bins.
+// compaction into bins, and the np.unique replay ORDER of the bins (one kernel, k_bins_order, for the 1D tables and the
+// (x_i, x_j, sf_bin) tables of gene pairs, which pairs.hip fills).
 //
 // Reference behaviour replaced: bootstrap._unique_expr  (memento/bootstrap.py:62-71):
 //     code = expr.dot(np.random.random(1)) + np.random.random()*approx_sf ; np.unique(code, ...)
@@ -104,23 +105,73 @@ __global__ __launch_bounds__(256) void k_bins_count(uint32_t *__restrict__ tab, 
 }
 
 // ------------------------------------------------------------------------------------------------
-// One workgroup per pair: compact the table, compute the replay hash code, bitonic-sort ascending,
-// write the bootstrap operand rows into the pair's lane of its 64-wide tile.
-template <int CAP, int NT>
+// What the ordering kernel needs to know about a pair's table: how a flat cell index decodes into (sf bin, counts), the count
+// term of the hash code, and the payload word that carries (sf bin, counts) through the sort.  load(p) reads the pair's own values.
+// 1D: table [sf_bin][x]; code = x*r1 + r0*approx_sf (bootstrap.py:62-65 with a one-column expr).
+struct Bins1D {
+  using Pay = uint32_t;          // sf_bin << 19 | x
+  static constexpr int NV = 1;   // value fields of a bin: x
+  const int32_t *__restrict__ xcap;
+  const double *__restrict__ r1;
+  double *__restrict__ o_v[NV];
+  int xc;
+  double r;
+  __device__ void load(int64_t p) { xc = xcap[p], r = r1[p]; }
+  __device__ int cells() const { return xc; }   // table cells per sf bin
+  __device__ Pay decode(int i, uint32_t &bin, double &cx) const {
+    uint32_t x = (uint32_t)(i % xc);
+    bin = (uint32_t)(i / xc);
+    cx = (double)x * r;
+    return (bin << 19) | x;
+  }
+  static __device__ uint32_t fields(Pay w, double *v) {
+    v[0] = (double)(w & ((1u << 19) - 1u));
+    return w >> 19;
+  }
+};
+
+// 2D: table [sf_bin][x_i][x_j] of a gene pair; code = (x_i*r[0] + x_j*r[1]) + r0*approx_sf (a two-column expr).
+struct Bins2D {
+  using Pay = uint64_t;          // sf_bin << 40 | x_i << 20 | x_j
+  static constexpr int NV = 2;   // x_i, x_j
+  const int32_t *__restrict__ xcap_i, *__restrict__ xcap_j;
+  const double *__restrict__ r1a, *__restrict__ r1b;
+  double *__restrict__ o_v[NV];
+  int ci, cj;
+  double ra, rb;
+  __device__ void load(int64_t p) { ci = xcap_i[p], cj = xcap_j[p], ra = r1a[p], rb = r1b[p]; }
+  __device__ int cells() const { return ci * cj; }
+  __device__ Pay decode(int i, uint32_t &bin, double &cx) const {
+    uint32_t xj = (uint32_t)(i % cj), xi = (uint32_t)((i / cj) % ci);
+    bin = (uint32_t)(i / (cj * ci));
+    double c1 = (double)xi * ra;
+    double c2 = (double)xj * rb;
+    cx = c1 + c2;
+    return ((uint64_t)bin << 40) | ((uint64_t)xi << 20) | (uint64_t)xj;
+  }
+  static __device__ uint32_t fields(Pay w, double *v) {
+    v[0] = (double)(uint32_t)((w >> 20) & 0xFFFFFu);
+    v[1] = (double)(uint32_t)(w & 0xFFFFFu);
+    return (uint32_t)(w >> 40);
+  }
+};
+
+// One workgroup per pair, for either table shape: compact the table, compute the replay hash code, bitonic-sort ascending,
+// write the bootstrap operand rows into the pair's lane of its 64-wide tile or into its records.
+template <int CAP, int NT, class Bins>
 __global__ __launch_bounds__(NT) void k_bins_order(const uint32_t *__restrict__ tab, const int64_t *__restrict__ tab_ptr,
-                                                   const int32_t *__restrict__ xcap, const int32_t *__restrict__ Karr,
-                                                   const int64_t *__restrict__ pair_list, int64_t n_list, int32_t n_groups,
-                                                   int32_t n_sf_bins, const double *__restrict__ sf_table,
-                                                   const double *__restrict__ r1a, const double *__restrict__ r0a,
+                                                   const int32_t *__restrict__ Karr, const int64_t *__restrict__ pair_list,
+                                                   int64_t n_list, int32_t n_groups, int32_t n_sf_bins,
+                                                   const double *__restrict__ sf_table, const double *__restrict__ r0a,
                                                    const int64_t *__restrict__ pair_slot, const int64_t *__restrict__ tile_ptr,
-                                                   const double *__restrict__ grp_ncells,
-                                                   double *__restrict__ o_pk, double *__restrict__ o_lq, double *__restrict__ o_v,
-                                                   double *__restrict__ o_a, double *__restrict__ o_b,
-                                                   int32_t *__restrict__ status) {
+                                                   const double *__restrict__ grp_ncells, double *__restrict__ o_pk,
+                                                   double *__restrict__ o_lq, double *__restrict__ o_a, double *__restrict__ o_b,
+                                                   int32_t *__restrict__ status, Bins b) {
+  using Pay = typename Bins::Pay;
   extern __shared__ double smem_d[];
   double *code = smem_d;                       // [CAP]
-  uint32_t *pay = (uint32_t *)(code + CAP);    // [CAP]  sf_bin << 19 | count
-  uint32_t *mult = pay + CAP;                  // [CAP]
+  Pay *pay = (Pay *)(code + CAP);              // [CAP]
+  uint32_t *mult = (uint32_t *)(pay + CAP);    // [CAP]
   __shared__ int n_found;
   if (blockIdx.x >= n_list) return;
   int64_t p = pair_list[blockIdx.x];
@@ -133,15 +184,15 @@ __global__ __launch_bounds__(NT) void k_bins_order(const uint32_t *__restrict__ 
   }
   int grp = (int)(p % n_groups);
   int64_t tp = tab_ptr[p];
-  int xc = xcap[p];
-  double r1 = r1a[p], r0 = r0a[p];
+  b.load(p);
+  double r0 = r0a[p];
   int tid = threadIdx.x;
   for (int i = tid; i < CAP; i += NT) code[i] = INFINITY;
   if (tid == 0) n_found = 0;
   __syncthreads();
-  // compaction by wave 0 in canonical (sf_bin major, count minor) order
+  // compaction by wave 0 in canonical (sf_bin major, counts minor) order
   if (tid < 64) {
-    int total = n_sf_bins * xc;
+    int total = n_sf_bins * b.cells();
     int pos = 0;
     for (int i0 = 0; i0 < total; i0 += 64) {
       int i = i0 + tid;
@@ -150,11 +201,12 @@ __global__ __launch_bounds__(NT) void k_bins_order(const uint32_t *__restrict__ 
       if (c != 0) {
         int at = pos + __popcll(m & ((1ull << tid) - 1ull));
         if (at < CAP) {
-          uint32_t bin = (uint32_t)(i / xc), x = (uint32_t)(i % xc);
-          double cx = (double)x * r1;
+          uint32_t bin;
+          double cx;
+          Pay w = b.decode(i, bin, cx);
           double cs = r0 * sf_table[bin];
           code[at] = cx + cs;
-          pay[at] = (bin << 19) | x;
+          pay[at] = w;
           mult[at] = c;
         }
       }
@@ -180,7 +232,7 @@ __global__ __launch_bounds__(NT) void k_bins_order(const uint32_t *__restrict__ 
           if ((ci > cj) == up && ci != cj) {
             code[i] = cj;
             code[ixj] = ci;
-            uint32_t tpay = pay[i];
+            Pay tpay = pay[i];
             pay[i] = pay[ixj];
             pay[ixj] = tpay;
             uint32_t tm = mult[i];
@@ -192,11 +244,11 @@ __global__ __launch_bounds__(NT) void k_bins_order(const uint32_t *__restrict__ 
       __syncthreads();
     }
   }
-  // slot = tile*64 + lane of the 64-wide tile layout, or MM_CHAIN_SLOT | row for a chain of the one-wave-per-chain kernel
-  // (mm_boot1d_chain): its operands go, bin by bin, into 8-double records at o_pk + 8*(row + k)
-  const bool chain = (slot & MM_CHAIN_SLOT) != 0;
+  // slot = tile*64 + lane of the 64-wide tile layout, or MM_CHAIN_SLOT | first record: the chain's operands then go, bin by bin,
+  // into 8-double records at o_pk + 8*(record + k): pk, lq, the value fields, 1/sf, 1/sf^2 (mm_boot1d_chain, mm_boot2d_replay_rec)
+  const bool recs = (slot & MM_CHAIN_SLOT) != 0;
   int64_t tile = slot >> 6, ln = slot & 63;
-  int64_t row0 = chain ? (slot & (MM_CHAIN_SLOT - 1)) : tile_ptr[tile];
+  int64_t row0 = recs ? (slot & (MM_CHAIN_SLOT - 1)) : tile_ptr[tile];
   double N = grp_ncells[grp];
   bool tie = false;
   for (int k = tid; k + 1 < K; k += NT)
@@ -213,157 +265,42 @@ __global__ __launch_bounds__(NT) void k_bins_order(const uint32_t *__restrict__ 
   }
   __syncthreads();
   for (int k = tid; k < K; k += NT) {
-    uint32_t bin = pay[k] >> 19, x = pay[k] & ((1u << 19) - 1u);
-    double sf = sf_table[bin];
-    double pk = ((double)mult[k] / N) / code[k];
-    if (chain) {
-      double *rec = o_pk + (row0 + k) * 8;
-      rec[0] = pk;
-      rec[1] = npyrng::binomial_lq(pk);
-      rec[2] = (double)x;
-      rec[3] = 1.0 / sf;
-      rec[4] = 1.0 / (sf * sf);
-      continue;
-    }
-    int64_t o = (row0 + k) * 64 + ln;
-    o_pk[o] = pk;
-    o_lq[o] = npyrng::binomial_lq(pk);
-    o_v[o] = (double)x;
-    o_a[o] = 1.0 / sf;
-    o_b[o] = 1.0 / (sf * sf);
-  }
-  if (tie) atomicOr(status, 8);  // np.unique would merge these two bins; caller must handle (never seen in practice)
-}
-
-// ------------------------------------------------------------------------------------------------
-// 2D variant: bins over (x_i, x_j, sf_bin) of a gene pair; code = x_i*r[0] + x_j*r[1] + r0*approx_sf
-// (bootstrap.py:62-65 with a two-column expr).  Table layout [sf_bin][x_i][x_j].
-template <int CAP, int NT>
-__global__ __launch_bounds__(NT) void k_bins_order2d(const uint32_t *__restrict__ tab, const int64_t *__restrict__ tab_ptr,
-                                                     const int32_t *__restrict__ xcap_i, const int32_t *__restrict__ xcap_j,
-                                                     const int32_t *__restrict__ Karr, const int64_t *__restrict__ pair_list,
-                                                     int64_t n_list, int32_t n_groups, int32_t n_sf_bins,
-                                                     const double *__restrict__ sf_table, const double *__restrict__ r1a,
-                                                     const double *__restrict__ r1b, const double *__restrict__ r0a,
-                                                     const int64_t *__restrict__ pair_slot, const int64_t *__restrict__ tile_ptr,
-                                                     const double *__restrict__ grp_ncells, double *__restrict__ o_pk,
-                                                     double *__restrict__ o_lq, double *__restrict__ o_v1, double *__restrict__ o_v2,
-                                                     double *__restrict__ o_a, double *__restrict__ o_b, int32_t *__restrict__ status) {
-  extern __shared__ double smem_d[];
-  double *code = smem_d;                              // [CAP]
-  uint64_t *pay = (uint64_t *)(code + CAP);           // [CAP]  sf_bin << 40 | x_i << 20 | x_j
-  uint32_t *mult = (uint32_t *)(pay + CAP);           // [CAP]
-  __shared__ int n_found;
-  if (blockIdx.x >= n_list) return;
-  int64_t p = pair_list[blockIdx.x];
-  int64_t slot = pair_slot[p];
-  if (slot < 0) return;
-  int K = Karr[p];
-  if (K > CAP) {
-    if (threadIdx.x == 0) atomicOr(status, 2);
-    return;
-  }
-  int grp = (int)(p % n_groups);
-  int64_t tp = tab_ptr[p];
-  int ci = xcap_i[p], cj = xcap_j[p];
-  double ra = r1a[p], rb = r1b[p], r0 = r0a[p];
-  int tid = threadIdx.x;
-  for (int i = tid; i < CAP; i += NT) code[i] = INFINITY;
-  if (tid == 0) n_found = 0;
-  __syncthreads();
-  if (tid < 64) {
-    int total = n_sf_bins * ci * cj;
-    int pos = 0;
-    for (int i0 = 0; i0 < total; i0 += 64) {
-      int i = i0 + tid;
-      uint32_t c = i < total ? tab[tp + i] : 0u;
-      unsigned long long m = __ballot(c != 0);
-      if (c != 0) {
-        int at = pos + __popcll(m & ((1ull << tid) - 1ull));
-        if (at < CAP) {
-          uint32_t xj = (uint32_t)(i % cj), xi = (uint32_t)((i / cj) % ci), bin = (uint32_t)(i / (cj * ci));
-          double c1 = (double)xi * ra;
-          double c2 = (double)xj * rb;
-          double cs = r0 * sf_table[bin];
-          code[at] = (c1 + c2) + cs;
-          pay[at] = ((uint64_t)bin << 40) | ((uint64_t)xi << 20) | (uint64_t)xj;
-          mult[at] = c;
-        }
-      }
-      pos += __popcll(m);
-    }
-    if (tid == 0) n_found = pos;
-  }
-  __syncthreads();
-  if (n_found != K) {
-    if (tid == 0) atomicOr(status, 4);
-    return;
-  }
-  int n = 1;
-  while (n < K) n <<= 1;
-  for (int k2 = 2; k2 <= n; k2 <<= 1) {
-    for (int j = k2 >> 1; j > 0; j >>= 1) {
-      for (int i = tid; i < n; i += NT) {
-        int ixj = i ^ j;
-        if (ixj > i) {
-          bool up = (i & k2) == 0;
-          double a_ = code[i], b_ = code[ixj];
-          if ((a_ > b_) == up && a_ != b_) {
-            code[i] = b_;
-            code[ixj] = a_;
-            uint64_t tpay = pay[i];
-            pay[i] = pay[ixj];
-            pay[ixj] = tpay;
-            uint32_t tm = mult[i];
-            mult[i] = mult[ixj];
-            mult[ixj] = tm;
-          }
-        }
-      }
-      __syncthreads();
-    }
-  }
-  // slot = tile*64 + lane of the 64-wide tile layout, or MM_CHAIN_SLOT | first record: the chain's operands then go, bin by bin, into
-  // 8-double records at o_pk + 8*(record + k): pk, lq, x_i, x_j, 1/sf, 1/sf^2 (mm_boot2d_replay_rec)
-  const bool recs = (slot & MM_CHAIN_SLOT) != 0;
-  int64_t tile = slot >> 6, ln = slot & 63;
-  int64_t row0 = recs ? (slot & (MM_CHAIN_SLOT - 1)) : tile_ptr[tile];
-  double N = grp_ncells[grp];
-  bool tie = false;
-  for (int k = tid; k + 1 < K; k += NT)
-    if (code[k] == code[k + 1]) tie = true;
-  __syncthreads();
-  if (tid == 0) {
-    double rem = 1.0;
-    for (int k = 0; k < K; k++) {
-      code[k] = rem;
-      rem -= (double)mult[k] / N;
-    }
-  }
-  __syncthreads();
-  for (int k = tid; k < K; k += NT) {
-    uint32_t bin = (uint32_t)(pay[k] >> 40), xi = (uint32_t)((pay[k] >> 20) & 0xFFFFFu), xj = (uint32_t)(pay[k] & 0xFFFFFu);
+    double v[Bins::NV];
+    uint32_t bin = Bins::fields(pay[k], v);
     double sf = sf_table[bin];
     double pk = ((double)mult[k] / N) / code[k];
     if (recs) {
       double *rec = o_pk + (row0 + k) * 8;
       rec[0] = pk;
       rec[1] = npyrng::binomial_lq(pk);
-      rec[2] = (double)xi;
-      rec[3] = (double)xj;
-      rec[4] = 1.0 / sf;
-      rec[5] = 1.0 / (sf * sf);
+#pragma unroll
+      for (int f = 0; f < Bins::NV; f++) rec[2 + f] = v[f];
+      rec[2 + Bins::NV] = 1.0 / sf;
+      rec[3 + Bins::NV] = 1.0 / (sf * sf);
       continue;
     }
     int64_t o = (row0 + k) * 64 + ln;
     o_pk[o] = pk;
     o_lq[o] = npyrng::binomial_lq(pk);
-    o_v1[o] = (double)xi;
-    o_v2[o] = (double)xj;
+#pragma unroll
+    for (int f = 0; f < Bins::NV; f++) b.o_v[f][o] = v[f];
     o_a[o] = 1.0 / sf;
     o_b[o] = 1.0 / (sf * sf);
   }
-  if (tie) atomicOr(status, 8);
+  if (tie) atomicOr(status, 8);  // np.unique would merge these two bins; caller must handle (never seen in practice)
+}
+
+// The small (one wave) or the big (512 threads) instantiation, 12 + sizeof(Pay) bytes of dynamic LDS per bin.
+template <int CAP_BIG, class Bins, class... Args>
+static int launch_bins_order(int32_t big, int64_t n_list, void *stream, Bins b, Args... args) {
+  auto launch = [&](auto kernel, int cap, int nt) {
+    size_t shm = (size_t)cap * (12 + sizeof(typename Bins::Pay));
+    if (shm > 48 * 1024) MM_HIP(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
+    hipLaunchKernelGGL(kernel, dim3((unsigned)n_list), dim3(nt), shm, (hipStream_t)stream, args..., b);
+    MM_LAUNCH_CHECK();
+    return MM_OK;
+  };
+  return big ? launch(k_bins_order<CAP_BIG, 512, Bins>, CAP_BIG, 512) : launch(k_bins_order<1024, 64, Bins>, 1024, 64);
 }
 
 extern "C" {
@@ -405,22 +342,8 @@ int mm_bins_order(const uint32_t *d_tab, const int64_t *d_tab_ptr, const int32_t
   MM_ARG(d_tab && d_tab_ptr && d_xcap && d_K && d_pair_list && d_sf_table && d_r1 && d_r0 && d_pair_slot && d_tile_ptr);
   MM_ARG(d_grp_ncells && d_pk && d_lq && d_v && d_a && d_b && d_status && n_list >= 0 && n_sf_bins <= 256);
   if (n_list == 0) return MM_OK;
-  if (!big) {
-    constexpr int CAP = 1024, NT = 64;
-    size_t shm = (size_t)CAP * 16;
-    hipLaunchKernelGGL((k_bins_order<CAP, NT>), dim3((unsigned)n_list), dim3(NT), shm, (hipStream_t)stream, d_tab, d_tab_ptr, d_xcap,
-                       d_K, d_pair_list, n_list, n_groups, n_sf_bins, d_sf_table, d_r1, d_r0, d_pair_slot, d_tile_ptr, d_grp_ncells,
-                       d_pk, d_lq, d_v, d_a, d_b, d_status);
-  } else {
-    constexpr int CAP = 8192, NT = 512;
-    size_t shm = (size_t)CAP * 16;
-    MM_HIP(hipFuncSetAttribute((const void *)k_bins_order<CAP, NT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-    hipLaunchKernelGGL((k_bins_order<CAP, NT>), dim3((unsigned)n_list), dim3(NT), shm, (hipStream_t)stream, d_tab, d_tab_ptr, d_xcap,
-                       d_K, d_pair_list, n_list, n_groups, n_sf_bins, d_sf_table, d_r1, d_r0, d_pair_slot, d_tile_ptr, d_grp_ncells,
-                       d_pk, d_lq, d_v, d_a, d_b, d_status);
-  }
-  MM_LAUNCH_CHECK();
-  return MM_OK;
+  return launch_bins_order<8192>(big, n_list, stream, Bins1D{d_xcap, d_r1, {d_v}}, d_tab, d_tab_ptr, d_K, d_pair_list, n_list, n_groups,
+                                 n_sf_bins, d_sf_table, d_r0, d_pair_slot, d_tile_ptr, d_grp_ncells, d_pk, d_lq, d_a, d_b, d_status);
 }
 
 int mm_bins_order2d(const uint32_t *d_tab, const int64_t *d_tab_ptr, const int32_t *d_xcap_i, const int32_t *d_xcap_j,
@@ -431,22 +354,10 @@ int mm_bins_order2d(const uint32_t *d_tab, const int64_t *d_tab_ptr, const int32
   MM_ARG(d_tab && d_tab_ptr && d_xcap_i && d_xcap_j && d_K && d_pair_list && d_sf_table && d_r1a && d_r1b && d_r0 && d_pair_slot);
   MM_ARG(d_tile_ptr && d_grp_ncells && d_pk && d_lq && d_v1 && d_v2 && d_a && d_b && d_status && n_list >= 0 && n_sf_bins <= 256);
   if (n_list == 0) return MM_OK;
-  if (!big) {
-    constexpr int CAP = 1024, NT = 64;
-    size_t shm = (size_t)CAP * 20;
-    hipLaunchKernelGGL((k_bins_order2d<CAP, NT>), dim3((unsigned)n_list), dim3(NT), shm, (hipStream_t)stream, d_tab, d_tab_ptr, d_xcap_i,
-                       d_xcap_j, d_K, d_pair_list, n_list, n_groups, n_sf_bins, d_sf_table, d_r1a, d_r1b, d_r0, d_pair_slot, d_tile_ptr,
-                       d_grp_ncells, d_pk, d_lq, d_v1, d_v2, d_a, d_b, d_status);
-  } else {
-    constexpr int CAP = 4096, NT = 512;  // 20 B per bin: 80 KiB of LDS
-    size_t shm = (size_t)CAP * 20;
-    MM_HIP(hipFuncSetAttribute((const void *)k_bins_order2d<CAP, NT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-    hipLaunchKernelGGL((k_bins_order2d<CAP, NT>), dim3((unsigned)n_list), dim3(NT), shm, (hipStream_t)stream, d_tab, d_tab_ptr, d_xcap_i,
-                       d_xcap_j, d_K, d_pair_list, n_list, n_groups, n_sf_bins, d_sf_table, d_r1a, d_r1b, d_r0, d_pair_slot, d_tile_ptr,
-                       d_grp_ncells, d_pk, d_lq, d_v1, d_v2, d_a, d_b, d_status);
-  }
-  MM_LAUNCH_CHECK();
-  return MM_OK;
+  // 20 B per bin: 80 KiB of LDS in the big instantiation
+  return launch_bins_order<4096>(big, n_list, stream, Bins2D{d_xcap_i, d_xcap_j, d_r1a, d_r1b, {d_v1, d_v2}}, d_tab, d_tab_ptr, d_K,
+                                 d_pair_list, n_list, n_groups, n_sf_bins, d_sf_table, d_r0, d_pair_slot, d_tile_ptr, d_grp_ncells, d_pk,
+                                 d_lq, d_a, d_b, d_status);
 }
 
 }  // extern "C"

@@ -564,7 +564,7 @@ def pcg64_state(seed=5):
 
 
 def _replay_order(code, mu, n_cells):
-    """Replay order of ONE chain's bins computed on the host, with the arithmetic of k_bins_order / k_bins_order2d: ``code``
+    """Replay order of ONE chain's bins computed on the host, with the arithmetic of k_bins_order: ``code``
     ascending (bootstrap.py:62-67), pk = pix / remaining_p, log(1 - p) after the p > 0.5 flip.  Returns (order, pk, lq)."""
     o = np.argsort(code, kind="stable")
     if len(o) > 1 and (np.diff(code[o]) == 0).any():
@@ -622,6 +622,36 @@ def _plan_records(K, rec_pairs):
     """Chains whose operands are 8-double records, one behind the other: (bins of each, first record of each + the total)."""
     rec_K = K[rec_pairs].astype(np.int64)
     return rec_K, np.concatenate([[0], np.cumsum(rec_K)]).astype(np.int64)
+
+
+def _order_bins(bs, kernel, d_xcaps, big_cap, order, t, r):
+    """Replay order of the chains ``order`` (K descending) of ``bs`` written to t.ops by ``kernel`` (table arguments ``d_xcaps``, uniforms ``r``): one
+    wave up to ORDER_SMALL_CAP bins, 512 threads up to ``big_cap``, the host beyond.  Returns (device status word, the device operands to keep)."""
+    K = bs.K[order]
+    small, big, on_host = order[K <= ORDER_SMALL_CAP], order[(K > ORDER_SMALL_CAP) & (K <= big_cap)], order[K > big_cap]
+    bs.order_path = {"small": len(small), "big": len(big), "host": len(on_host)}     # diagnostics (tests)
+    d_pair_slot, t.d_tile_ptr = dev(t.pair_slot), dev(t.tile_ptr)
+    status = zeros((1,), _torch().int32)
+    d_r = [dev(np.asarray(x, dtype=np.float64)) for x in r]
+    d_sf, d_nc = dev(bs.sf_table), dev(bs.blocks.grp_ncells.astype(np.float64))
+    keep = [d_pair_slot, t.d_tile_ptr, d_sf, d_nc, *d_r]
+    for lst, is_big in ((small, 0), (big, 1)):
+        if len(lst):
+            keep.append(dev(lst))
+            _lib.call(kernel, P(bs.tab), P(bs.d_tab_ptr), *map(P, d_xcaps), P(bs.d_K), P(keep[-1]), len(lst), is_big, bs.ng, bs.n_bins,
+                      P(d_sf), *map(P, d_r), P(d_pair_slot), P(t.d_tile_ptr), P(d_nc), *map(P, t.ops), P(status), _stream())
+    for p in on_host:    # more bins than the in-LDS sort holds (very highly expressed genes)
+        bs._order_on_host(int(p), *[float(x[p]) for x in r], int(t.pair_slot[p]), t.tile_ptr, t.ops)
+    return status, keep
+
+
+def _check_order_status(status, kernel):
+    """The device status word of ``kernel`` (2 = more bins than the kernel holds, 4 = bins found != K, 8 = two equal codes) as exceptions."""
+    st = int(status.item())
+    if st & 6:
+        raise RuntimeError(f"{kernel} inconsistency (status {st})")
+    if st & 8:
+        raise NotImplementedError("two bins of one pair collided in the replay hash (np.unique would merge them)")
 
 
 class Bootstrap1D:
@@ -719,14 +749,10 @@ class Bootstrap1D:
         active[:first_pair] = False
         c = self._choose_kernels(active, fast, target_waves)
         t = self._lay_out_operands(c, dump_weights)
-        status, ordered = self._order_bins(c, t, r1, r0)
+        status, ordered = _order_bins(self, "mm_bins_order", (self.d_xcap,), ORDER_BIG_CAP, c.order_all, t, (r1, r0))
         launched = self._launch(c, t, fast, mean_only, fill_seed, pcg_seed, dump_weights, chain_keys)
-        st = int(status.item())
+        _check_order_status(status, "mm_bins_order")      # (reads the word: after the launches are enqueued)
         del ordered, launched      # NB: every device operand must stay referenced until after the call that reads it
-        if st & 2 or st & 4:
-            raise RuntimeError(f"mm_bins_order inconsistency (status {st})")
-        if st & 8:
-            raise NotImplementedError("two bins of one pair collided in the replay hash (np.unique would merge them)")
         self.raw_mean = self.ym.clone() if dump_weights else None
         self.raw_var = self.yv.clone() if dump_weights else None
         n_inv = self._fill_log(mv_fit, fill_mode, fill_seed, first_pair, fill_keys)
@@ -797,31 +823,6 @@ class Bootstrap1D:
         self.slot_pair, self.slot_K, self.pair_slot, self.tile_ptr = t.slot_pair, t.slot_K, t.pair_slot, t.tile_ptr
         self._ops, self._nobs = t.ops, t.nobs      # kept for diagnostics (tools/replay_balance.py)
         return t
-
-    def _order_bins(self, c, t, r1, r0):
-        """mm_bins_order for every chain: its bins in replay order, its operands written to its tile lane or its records.
-        Returns (device status word, the device operands the launches read)."""
-        torch, s = _torch(), _stream()
-        K_all = self.K[c.order_all]
-        d_pair_slot, d_tile_ptr = dev(t.pair_slot), dev(t.tile_ptr)
-        status = zeros((1,), torch.int32)
-        d_r1, d_r0 = dev(np.asarray(r1, dtype=np.float64)), dev(np.asarray(r0, dtype=np.float64))
-        d_sf, d_nc = dev(self.sf_table), dev(self.blocks.grp_ncells.astype(np.float64))
-        keep = [d_pair_slot, d_tile_ptr, d_r1, d_r0, d_sf, d_nc]
-        small = c.order_all[K_all <= ORDER_SMALL_CAP]
-        big = c.order_all[(K_all > ORDER_SMALL_CAP) & (K_all <= ORDER_BIG_CAP)]
-        huge = c.order_all[K_all > ORDER_BIG_CAP]
-        for lst, is_big in ((small, 0), (big, 1)):
-            if len(lst):
-                d_lst = dev(lst)
-                keep.append(d_lst)
-                _lib.call("mm_bins_order", P(self.tab), P(self.d_tab_ptr), P(self.d_xcap), P(self.d_K), P(d_lst), len(lst),
-                          is_big, self.ng, self.n_bins, P(d_sf), P(d_r1), P(d_r0), P(d_pair_slot), P(d_tile_ptr), P(d_nc),
-                          *[P(o) for o in t.ops], P(status), s)
-        for p in huge:   # more bins than the in-LDS sort holds (very highly expressed genes): order them on the host
-            self._order_on_host(int(p), float(r1[p]), float(r0[p]), int(t.pair_slot[p]), t.tile_ptr, t.ops)
-        t.d_tile_ptr = d_tile_ptr
-        return status, keep
 
     def _launch(self, c, t, fast, mean_only, fill_seed, pcg_seed, dump_weights, chain_keys=None):
         """The chain kernel on the side stream, beside it on the launch stream the async and the tile kernel.  Returns their device operands."""
@@ -1146,7 +1147,7 @@ class Bootstrap2D:
 
     def _order_on_host(self, q, ra, rb, r0, slot, tile_ptr, ops):
         """Replay order + bootstrap operands of ONE (pair, group) with more bins than the in-LDS sort holds, computed on the host
-        with the same arithmetic as k_bins_order2d: code = (x_i*r[0] + x_j*r[1]) + r0*approx_sf ascending (bootstrap.py:62-67)."""
+        with the same arithmetic as k_bins_order: code = (x_i*r[0] + x_j*r[1]) + r0*approx_sf ascending (bootstrap.py:62-67)."""
         bi, xi, xj, mu = self.bins_of(q)
         code = (xi.astype(np.float64) * ra + xj.astype(np.float64) * rb) + r0 * self.sf_table[bi]
         o, pk, lq = _replay_order(code, mu, self.blocks.grp_ncells[q % self.ng])
@@ -1165,81 +1166,80 @@ class Bootstrap2D:
         kernels: replicate r of chain q draws from its own PCG64 stream derived from (``fast_seed``, ``pair_key[q]``, r) --
         ``pair_key`` [n_q] int64, default q; keys that do not depend on how the pairs were chunked or ordered make the result
         independent of both -- and ``pcg_seed`` is ignored.  ``dump_weights`` (fast only): keep the weights for ``weights_of``."""
-        torch = _torch()
-        s = _stream()
-        ng, B, ld = self.ng, self.B, self.ld
         if dump_weights and not fast:
             raise ValueError("dump_weights needs fast=True")
         active = (~np.asarray(skip, dtype=bool)) & (self.K >= 1)
+        c = self._choose_packing(active, fast, target_waves)
+        t = self._lay_out_operands(c, fast)
+        self.replay_kernel = None      # diagnostics (tests): the kernel launched
+        status, ordered = _order_bins(self, "mm_bins_order2d", (self.d_xi, self.d_xj), ORDER_BIG_CAP_2D, c.order, t, (r1a, r1b, r0))
+        launched = self._launch(c, t, fast, true_corr, pcg_seed, fast_seed, pair_key, dump_weights)
+        _check_order_status(status, "mm_bins_order2d")
+        del ordered, launched      # NB: every device operand must stay referenced until after the call that reads it
+        self.active = active
+        self.pair_slot = t.pair_slot
+
+    def _choose_packing(self, active, fast, target_waves):
+        """The chains, longest first, and their (tile, lane) slots.  fast: one WAVE per 64 replicates of a chain, lanes = replicates: plain
+        64-wide tiles, longest chains dispatched first; replay: the cost-model lane packing and dispatch order of the 2D kernel."""
         act = np.flatnonzero(active)
-        order = act[np.argsort(-self.K[act], kind="stable")]
-        if fast:    # one WAVE per 64 replicates of a chain, lanes = replicates: plain 64-wide tiles, longest chains dispatched first
-            slot_of, n_tiles = pack_lanes(self.K[order], 0, dense=True)
+        c = SimpleNamespace()
+        order = c.order = act[np.argsort(-self.K[act], kind="stable")]
+        if fast:
+            c.slot_of, c.n_tiles = pack_lanes(self.K[order], 0, dense=True)
         else:
-            slot_of, n_tiles = pack_lanes(self.K[order], PACK_WAVES if target_waves is None else target_waves, consts=PACK2D, cost=PACK_COST_2D)
-            slot_of = pair_tiles(slot_of, n_tiles, self.K[order], cost=PACK_COST_2D)
-        self.n_tiles = n_tiles
-        t = _plan_tiles(self.K, order, slot_of, n_tiles, self.n_q, self.blocks.grp_ncells, self.grp_q, ng)
-        pair_slot, tile_ptr = t.pair_slot, t.tile_ptr
+            slot_of, c.n_tiles = pack_lanes(self.K[order], PACK_WAVES if target_waves is None else target_waves, consts=PACK2D, cost=PACK_COST_2D)
+            c.slot_of = pair_tiles(slot_of, c.n_tiles, self.K[order], cost=PACK_COST_2D)
+        self.n_tiles = c.n_tiles
         self.draws_per_replicate = int(np.maximum(self.K[order] - 1, 0).sum())
-        self.wave_steps_per_replicate = rows = int(tile_ptr[-1])
-        use_rec = BOOT2D_RECORDS and n_tiles > 0 and not fast
-        if use_rec:
+        return c
+
+    def _lay_out_operands(self, c, fast):
+        """Slot tables of the tile launch and the operands: six [rows][64] planes, or (mm_boot2d_replay_rec) 8-double records."""
+        torch = _torch()
+        t = _plan_tiles(self.K, c.order, c.slot_of, c.n_tiles, self.n_q, self.blocks.grp_ncells, self.grp_q, self.ng)
+        self.wave_steps_per_replicate = rows = int(t.tile_ptr[-1])
+        t.use_rec = BOOT2D_RECORDS and c.n_tiles > 0 and not fast
+        if t.use_rec:
             # per-chain operand records (8 doubles per bin) instead of [row][64] planes: a lane reads memory of its own wherever it is in
             # its chain, so the kernel can let a rejected BTPE attempt retry in the next bin step (mm_boot2d_replay_rec)
-            rec_base = _plan_records(self.K, order)[1]
-            ops = [empty((8 * max(1, int(rec_base[-1])),), torch.float64)] + [empty((8,), torch.float64) for _ in range(5)]
-            self.tile_slot = pair_slot.copy()
-            pair_slot[order] = CHAIN_SLOT | rec_base[:-1]
-            slot_rec = _per_slot(n_tiles * 64, slot_of, rec_base[:-1], -1, np.int64)
+            rec_base = _plan_records(self.K, c.order)[1]
+            t.ops = [empty((8 * max(1, int(rec_base[-1])),), torch.float64)] + [empty((8,), torch.float64) for _ in range(5)]
+            self.tile_slot = t.pair_slot.copy()
+            t.pair_slot[c.order] = CHAIN_SLOT | rec_base[:-1]
+            t.slot_rec = _per_slot(c.n_tiles * 64, c.slot_of, rec_base[:-1], -1, np.int64)
         else:
-            ops = [empty((max(1, rows) * 64,), torch.float64) for _ in range(6)]
-        d_pair_slot, d_tile_ptr = dev(pair_slot), dev(tile_ptr)
-        status = zeros((1,), torch.int32)
-        d_ra, d_rb, d_r0 = dev(np.asarray(r1a, np.float64)), dev(np.asarray(r1b, np.float64)), dev(np.asarray(r0, np.float64))
-        d_sf, d_nc = dev(self.sf_table), dev(self.blocks.grp_ncells.astype(np.float64))
-        small = order[self.K[order] <= ORDER_SMALL_CAP]
-        big = order[(self.K[order] > ORDER_SMALL_CAP) & (self.K[order] <= ORDER_BIG_CAP_2D)]
-        huge = order[self.K[order] > ORDER_BIG_CAP_2D]
-        self.order_path = {"small": len(small), "big": len(big), "host": len(huge)}     # diagnostics (tests): chains per ordering path
-        self.replay_kernel = None                                                       # ... and the replay kernel launched below
-        for q in huge:   # more bins than the in-LDS sort holds (two highly expressed genes): ordered on the host, like the 1D path
-            self._order_on_host(int(q), float(r1a[q]), float(r1b[q]), float(r0[q]), int(pair_slot[q]), tile_ptr, ops)
-        for lst, is_big in ((small, 0), (big, 1)):
-            if len(lst):
-                d_lst = dev(lst)
-                _lib.call("mm_bins_order2d", P(self.tab), P(self.d_tab_ptr), P(self.d_xi), P(self.d_xj), P(self.d_K), P(d_lst), len(lst),
-                          is_big, ng, self.n_bins, P(d_sf), P(d_ra), P(d_rb), P(d_r0), P(d_pair_slot), P(d_tile_ptr), P(d_nc),
-                          *[P(o) for o in ops], P(status), s)
+            t.ops = [empty((max(1, rows) * 64,), torch.float64) for _ in range(6)]
+        return t
+
+    def _launch(self, c, t, fast, true_corr, pcg_seed, fast_seed, pair_key, dump_weights):
+        """The replicate rows self.yc and the tile kernel that fills them.  Returns its device operands."""
+        torch, s = _torch(), _stream()
+        B, ld, n_tiles = self.B, self.ld, c.n_tiles
         self.yc = torch.full((max(1, self.n_q), ld), float("nan"), dtype=torch.float64, device="cuda")
         self.yc[: self.n_q, 0] = dev(np.asarray(true_corr, dtype=np.float64))
         d_slot_K, d_nobs, d_omq, d_slot_pair = dev(t.slot_K), dev(t.nobs), dev(t.omq), dev(t.slot_pair)
-        self.w_dump = None
+        keep = [d_slot_K, d_nobs, d_omq, d_slot_pair]
+        kmax_dump = int(t.tile_k.max()) if dump_weights and n_tiles else 0      # (dump_weights: fast only)
+        self.w_dump = zeros((n_tiles * 64, kmax_dump, B), torch.int32) if dump_weights and n_tiles else None
         if n_tiles and fast:
             keys = np.arange(self.n_q, dtype=np.int64) if pair_key is None else np.asarray(pair_key, dtype=np.int64)
-            d_slot_key = dev(_per_slot(n_tiles * 64, slot_of, keys[order], 0, np.int64))
-            kmax_dump = int(t.tile_k.max()) if dump_weights else 0
-            if dump_weights:
-                self.w_dump = zeros((n_tiles * 64, kmax_dump, B), torch.int32)
-            _lib.call("mm_boot2d_fast", *[P(o) for o in ops], P(d_tile_ptr), n_tiles * 64, P(d_slot_K), P(d_nobs), P(d_omq), P(d_slot_pair),
+            d_slot_key = dev(_per_slot(n_tiles * 64, c.slot_of, keys[c.order], 0, np.int64))
+            keep.append(d_slot_key)
+            _lib.call("mm_boot2d_fast", *map(P, t.ops), P(t.d_tile_ptr), n_tiles * 64, P(d_slot_K), P(d_nobs), P(d_omq), P(d_slot_pair),
                       P(d_slot_key), int(fast_seed) & ((1 << 64) - 1), B, ld, P(self.yc), P(self.w_dump), kmax_dump, s)
             self.replay_kernel = "mm_boot2d_fast"
-        elif n_tiles and use_rec:
-            d_slot_rec = dev(slot_rec)
-            _lib.call("mm_boot2d_replay_rec", P(ops[0]), P(d_slot_rec), n_tiles, P(d_slot_K), P(d_nobs), P(d_omq), P(d_slot_pair),
+        elif n_tiles and t.use_rec:
+            d_slot_rec = dev(t.slot_rec)
+            keep.append(d_slot_rec)
+            _lib.call("mm_boot2d_replay_rec", P(t.ops[0]), P(d_slot_rec), n_tiles, P(d_slot_K), P(d_nobs), P(d_omq), P(d_slot_pair),
                       pcg64_state(pcg_seed), B, ld, P(self.yc), s)
             self.replay_kernel = "mm_boot2d_replay_rec"
         elif n_tiles:
-            _lib.call("mm_boot2d_replay", *[P(o) for o in ops], P(d_tile_ptr), n_tiles, P(d_slot_K), P(d_nobs), P(d_omq), P(d_slot_pair),
+            _lib.call("mm_boot2d_replay", *map(P, t.ops), P(t.d_tile_ptr), n_tiles, P(d_slot_K), P(d_nobs), P(d_omq), P(d_slot_pair),
                       pcg64_state(pcg_seed), B, ld, P(self.yc), s)
             self.replay_kernel = "mm_boot2d_replay"
-        st = int(status.item())
-        if st & 6:
-            raise RuntimeError(f"mm_bins_order2d inconsistency (status {st})")
-        if st & 8:
-            raise NotImplementedError("two bins of one pair collided in the replay hash (np.unique would merge them)")
-        self.active = active
-        self.pair_slot = pair_slot
+        return keep
 
     def valid_cols(self, good):
         """hypothesis_test.py:372-373 on the device (see Bootstrap1D.valid_cols)."""

@@ -85,6 +85,13 @@ def test_replay_weights_edge_and_host_order_fallback(eng, monkeypatch):
         bs.alloc_outputs(zeros, zeros)
         bs.run(np.zeros(bs.n_pairs, bool), r[0], r[1], [0.0, 1.0, 0.0], fill_mode=1, dump_weights=True)
         rm = eng.host(bs.raw_mean)
+        live = bs.K[bs.K >= 2]
+        want = {"small": int((live <= caps[0]).sum()), "big": int(((live > caps[0]) & (live <= caps[1])).sum()), "host": int((live > caps[1]).sum())}
+        assert bs.order_path == want
+        if caps == (4, 6):
+            assert min(want.values()) > 0
+        else:
+            assert want["small"] == len(live) > 0
         for p in range(bs.n_pairs):
             gene, k = divmod(p, ng)
             sel = np.flatnonzero(gid == k)
@@ -119,7 +126,7 @@ def test_explicitly_stored_zeros_are_accepted(eng):
 
 def test_2d_host_ordering_fallback_equals_device_order(api_small, monkeypatch):
     """A (pair, group) with more unique bins than the in-LDS sort holds is ordered on the host (engine.Bootstrap2D._order_on_host,
-    the same arithmetic as k_bins_order2d): forcing EVERY pair through that path gives bit-identical replicate correlations."""
+    the same arithmetic as k_bins_order on the pair table): forcing EVERY pair through that path gives bit-identical replicate correlations."""
     import pandas as pd
 
     from scrna_parameter_estimation_amd import AnnDataLite, engine, memento

@@ -158,6 +158,37 @@ def test_bins_exact(eng, orc, api_small):
             assert bs.K[gs * ng + k] == len(want)
 
 
+@pytest.mark.parametrize("caps", [(1024, 8192), (0, 8192), (0, 0)], ids=["small-kernel", "big-kernel", "host"])
+@pytest.mark.parametrize("fast", [False, True], ids=["records", "planes"])
+def test_hash_collision_is_reported(eng, monkeypatch, caps, fast):
+    """With r1 == r0 == 0.25 the code of a bin is 0.25 * (x + sf) exactly, so bins with equal x + sf collide, which np.unique would
+    merge -- among them (count 2, sf 1) and (count 1, sf 2) at 0.75, which the two forced cells guarantee for gene 0 whatever the
+    Poisson draw gives: every ordering path must report it, whether the chains take records (replay: few chains, one per wave) or
+    planes (fast) -- NotImplementedError from the status word; nothing faults."""
+    rng = np.random.default_rng(5)
+    n = 200
+    X = rng.poisson(0.7, size=(n, 2)).astype(np.int64)
+    sf_bin = rng.integers(0, 4, size=n).astype(np.uint8)
+    X[10, 0], sf_bin[10] = 2, 0
+    X[20, 0], sf_bin[20] = 1, 1
+    sf_table = np.array([1.0, 2.0, 3.0, 4.0])
+    blocks = eng.CountBlocks(eng.DeviceCSR(sp.csr_matrix(X.astype(np.float32))), np.zeros(n, dtype=np.int32), 1)
+    _, _, maxx = blocks.moments(np.ones(n))
+    bs = eng.Bootstrap1D(blocks, np.arange(2), maxx, sf_bin, sf_table, np.full(1, 0.1), 8)
+    monkeypatch.setattr(eng, "ORDER_SMALL_CAP", caps[0])
+    monkeypatch.setattr(eng, "ORDER_BIG_CAP", caps[1])
+    skip, zeros = np.zeros(2, dtype=bool), np.zeros(2)
+    bs.alloc_outputs(zeros, zeros)
+    r1, r0 = rng.random((2, 2))
+    bs.run(skip, r1, r0, [0.0, 1.0, 0.0], fast=fast)                                # generic multipliers: no collision
+    assert np.isfinite(eng.host(bs.ym)).all()
+    path = "small" if caps[0] else "big" if caps[1] else "host"
+    assert bs.order_path[path] == 2 and sum(bs.order_path.values()) == 2
+    np.testing.assert_array_equal((bs.pair_slot & eng.CHAIN_SLOT) != 0, np.full(2, not fast))      # records / planes
+    with pytest.raises(NotImplementedError):
+        bs.run(skip, np.full(2, 0.25), np.full(2, 0.25), [0.0, 1.0, 0.0], fast=fast)
+
+
 def test_replay_bootstrap_bit_exact(eng, orc, api_small):
     g = api_small
     B = 40
