@@ -281,7 +281,15 @@ int mm_boot1d_fast(const double *d_pk, const double *d_lq, const double *d_v, co
  *   RNG (own stream: statistically equivalent to np.random.choice, not the same draws);
  * fill_mode 1: leave invalid entries as NaN (the strict host driver patches them with np.random).
  * d_n_invalid[row][2] = number of invalid (mean, res_var) replicates; a row with no valid entry is
- * reported as -1. */
+ * reported as -1.
+ * The draw rule of fill_mode 0 (restated in numpy in tests/_replicate_ref.py).  mix() is the splitmix64 output function
+ * (x += 0x9E3779B97F4A7C15; x = (x ^ x >> 30) * 0xBF58476D1CE4E5B9; x = (x ^ x >> 27) * 0x94D049BB133111EB; x ^ x >> 31), all
+ * arithmetic is uint64.  Invalid replicate r (0-based, stored in column r + 1) of plane p (0 mean, 1 res_var) of the row with
+ * key k (d_row_key[row], or the row number) starts from c = mix(fill_seed ^ mix(2 k + p) ^ (r << 20)) and makes up to 4096
+ * attempts a = 0, 1, ...: c = mix(c + a), index = c mod num_boot; the first index that is an originally valid replicate of that
+ * plane is taken.  If all 4096 miss (probability (1 - V / num_boot)^4096 with V valid replicates), the entry takes the valid
+ * replicate of rank mix(~c0) mod V in ascending position, c0 being the starting value above.  So every invalid entry of a plane
+ * with V >= 1 is filled, uniformly over the V valid ones; a plane with V = 0 stays NaN. */
 int mm_boot_fill_log(double *d_mean, double *d_var, int64_t n_rows, int64_t ld, int32_t num_boot, const double mv_fit[3],
                      int32_t fill_mode, uint64_t fill_seed, int32_t *d_n_invalid,
                      const int64_t *d_row_key /* optional [n_rows]: the refill stream of a row is keyed by this instead of the row
@@ -307,7 +315,8 @@ int mm_contract_stats(const double *d_ym, const double *d_yv, int64_t ld, int32_
  * replaces hypothesis_test._regress_1d :249-254, :273-286, _regress_2d :372-377, :393-404 and _cross_coef_resampled :231-239.
  * mm_valid_cols: the replicate columns that survive valid_boostrap_iters (:249-251): d_col_map[gene][k] = k-th column in
  * which every good group is finite in BOTH d_ym and d_yv (pass the same pointer twice for the 2D correlation rows),
- * d_n_valid[gene] = their number.  d_col_map is [n_genes][num_boot + 1].
+ * d_n_valid[gene] = their number.  d_col_map is [n_genes][num_boot + 1]; entries beyond d_n_valid[gene] are unspecified.
+ * num_boot = 0 (column 0 alone) is accepted.
  * mm_residualize: d_dst = M d_src on the [n_genes*n_groups][ld] rows (columns 0..n_cols-1; d_dst must not alias d_src);
  * gene g uses the n_groups x n_groups matrix d_M[d_gene_mask[g]] (zero rows/columns on invalid groups -> NaN rows).
  * Any number of groups (one group per donor: analysis/lupus/run_memento.py:31-52). */
@@ -319,7 +328,13 @@ int mm_residualize(const double *d_src, double *d_dst, int64_t ld, int32_t n_col
  * d_col_map / d_n_valid are NULL).  d_tt[test][group] = residualised treatment; d_rep/d_bcol [gene][n_groups][num_boot] =
  * group index (into the gene's valid groups) and index (1..nb, into the surviving columns) of the replicate column drawn for
  * row i of column c (np.random.choice replay), or both NULL to draw them on the device.  Columns whose drawn groups all share
- * one treatment value (0/0 in the reference) are reported as NaN. */
+ * one treatment value (0/0 in the reference) are reported as NaN.
+ * The device draws (d_rep == NULL; restated in numpy in tests/_replicate_ref.py), with mix() the splitmix64 output function as
+ * in mm_boot_fill_log and uint64 arithmetic: row i (position among the n good groups of gene g = d_test_gene[t]) of column
+ * c >= 1 takes h = mix(seed ^ mix((g << 32) ^ (i << 24) ^ c)), group r = h mod n and surviving column bb = mix(h) mod nb + 1;
+ * column 0 is the identity (r = i, bb = 0).  The draws depend on the gene, not on the test.  The packing keeps (g, i, c)
+ * apart for i < 256 and c < 2^24; from 256 good groups on the bits of i run into those of g, so distinct (g, i) can share a
+ * stream (left as is: repacking would move every device-drawn result). */
 int mm_cross_resampled(const double *d_yt, int64_t ld, int32_t num_boot, int32_t n_groups, const int32_t *d_test_gene,
                        const double *d_tt, const uint8_t *d_good, const double *d_Nc, const int16_t *d_rep, const int32_t *d_bcol,
                        const int32_t *d_col_map, const int32_t *d_n_valid, uint64_t seed, int64_t n_tests, double *d_coef,
@@ -329,7 +344,8 @@ int mm_cross_resampled(const double *d_yt, int64_t ld, int32_t num_boot, int32_t
  * test t: coef_b = y[test_gene[t], test_grp[t]][b] - y[test_gene[t], ctrl][b] -- what _regress_1d computes for the two
  * groups {control, guide} with a binary treatment (hypothesis_test.py:269-291); the control's bootstrap is shared by all
  * guides instead of being recomputed per guide as in the reference's per-guide loop.  stats layout as mm_contract_stats,
- * for the mean and the variability response in one launch; nothing per-replicate is stored. */
+ * for the mean and the variability response in one launch; nothing per-replicate is stored.  A column counts only if all four
+ * operands (guide and control, mean and variability) are finite; if column 0 does not, coef0 is NaN on both planes. */
 int mm_contrast_stats(const double *d_ym, const double *d_yv, int64_t ld, int32_t num_boot, int32_t n_groups, int32_t ctrl,
                       const int32_t *d_test_gene, const int32_t *d_test_grp, const uint8_t *d_good, int64_t n_tests,
                       double *d_stats_mean, double *d_stats_var, void *stream);

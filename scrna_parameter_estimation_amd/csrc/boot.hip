@@ -486,9 +486,17 @@ __device__ __forceinline__ uint64_t mix64(uint64_t x) {  // splitmix64 finaliser
   return x ^ (x >> 31);
 }
 
+// counter of the refill draws of replicate r in plane ``which`` (0 mean, 1 res_var) of the row with key ``key``
+__device__ __forceinline__ uint64_t fill_ctr(uint64_t seed, uint64_t key, int which, int r) {
+  return mix64(seed ^ mix64(key * 2 + which) ^ ((uint64_t)r << 20));
+}
+
 // One wave per row.  Pass 1: res_var, validity, counts.  Pass 2 (fill_mode 0): each invalid entry takes
-// a uniformly chosen VALID replicate (stored negated so later readers still see it as "not original").
-// Pass 3: log.
+// a uniformly chosen VALID replicate (stored negated so later readers still see it as "not original"): up to FILL_ATTEMPTS
+// rejection draws per lane, then, for what those left (rows with very few valid replicates), the wave resolves the entries
+// one at a time: rank = hash mod V, found by a ballot / popcount scan over the row.  Valid entries are never written in pass 2,
+// so the scan races with nothing.  The draw rule is part of the C-ABI contract (include/memento_hip.h).  Pass 3: log.
+#define FILL_ATTEMPTS 4096
 __global__ __launch_bounds__(256) void k_boot_fill_log(double *__restrict__ mean, double *__restrict__ var, int64_t n_rows,
                                                        int64_t ld, int32_t num_boot, double f0, double f1, double f2,
                                                        int32_t fill_mode, uint64_t seed, int32_t *__restrict__ n_invalid,
@@ -535,12 +543,13 @@ __global__ __launch_bounds__(256) void k_boot_fill_log(double *__restrict__ mean
       double *x = which ? s : m;
       int nb = which ? bad_v : bad_m;
       if (nb == 0 || nb == num_boot) continue;
+      bool left = false;
       for (int r = lane; r < num_boot; r += 64) {
         double cur = x[r];
         if (!(cur > 0.0) && !(cur < 0.0)) {  // NaN => invalid and not yet filled
-          uint64_t ctr = mix64(seed ^ mix64(key * 2 + which) ^ ((uint64_t)r << 20));
+          uint64_t ctr = fill_ctr(seed, key, which, r);
           double pick = NAN;
-          for (int attempt = 0; attempt < 4096; attempt++) {
+          for (int attempt = 0; attempt < FILL_ATTEMPTS; attempt++) {
             ctr = mix64(ctr + attempt);
             int idx = (int)(ctr % (uint64_t)num_boot);
             double c = x[idx];
@@ -550,6 +559,31 @@ __global__ __launch_bounds__(256) void k_boot_fill_log(double *__restrict__ mean
             }
           }
           x[r] = -pick;
+          left = left || !(pick > 0.0);
+        }
+      }
+      __threadfence_block();
+      if (!__any(left)) continue;
+      // the entries the rejection draws left NaN (probability (1 - V / num_boot)^FILL_ATTEMPTS each, V = valid replicates): the
+      // whole wave takes them in ascending order and gives each the rank-th valid entry of the row, rank = hash mod V
+      const uint64_t n_ok = (uint64_t)(num_boot - nb);
+      for (int r0 = 0; r0 < num_boot; r0 += 64) {
+        double cur = r0 + lane < num_boot ? x[r0 + lane] : 1.0;
+        uint64_t todo = __ballot(!(cur > 0.0) && !(cur < 0.0));
+        while (todo) {
+          int r = r0 + __ffsll((unsigned long long)todo) - 1;
+          todo &= todo - 1;
+          uint64_t rank = mix64(~fill_ctr(seed, key, which, r)) % n_ok;
+          for (int c0 = 0; c0 < num_boot; c0 += 64) {
+            double c = c0 + lane < num_boot ? x[c0 + lane] : NAN;
+            uint64_t bal = __ballot(c > 0.0);
+            uint64_t cnt = (uint64_t)__popcll(bal);
+            if (rank < cnt) {
+              if (c > 0.0 && (uint64_t)__popcll(bal & ((1ull << lane) - 1ull)) == rank) x[r] = -c;
+              break;
+            }
+            rank -= cnt;
+          }
         }
       }
       __threadfence_block();

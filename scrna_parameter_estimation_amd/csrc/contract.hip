@@ -50,7 +50,7 @@ __device__ __forceinline__ void write_nan_record(double *st) {   // a test with 
 }
 
 // Fill the records st[0..NP) of one test from ``coef_at(c, v)``: it puts the NP coefficients of replicate column c into v and
-// returns whether the column is valid (one verdict for all planes; v of column 0 is reported as coef0 either way).  Called
+// returns whether the column is valid (one verdict for all planes) and leaves NaN in v where it is not: coef0 = v of column 0.  Called
 // by all K9_THREADS threads of the workgroup.  Pass A: count / sum / min / max; pass B: squared deviations and the extreme
 // counts.  STORED = false: pass B calls coef_at again (nothing per-replicate is stored; row is unused).  STORED = true
 // (NP == 1): pass A stores the coefficient row in ``row``, which is also an output, and pass B reads it back; invalid
@@ -380,9 +380,10 @@ __global__ __launch_bounds__(K9_THREADS) void k_contrast_stats(const double *__r
   const double *va = yv + ((int64_t)gene * n_groups + grp) * ld, *vc = yv + ((int64_t)gene * n_groups + ctrl) * ld;
   auto coef_at = [&](int c, double(&v)[2]) {
     double a = ma[c], b = mc[c], p = va[c], q = vc[c];
-    v[0] = a - b;
-    v[1] = p - q;
-    return isfinite(a) && isfinite(b) && isfinite(p) && isfinite(q);
+    bool ok = isfinite(a) && isfinite(b) && isfinite(p) && isfinite(q);
+    v[0] = ok ? a - b : NAN;   // as k_contrast_rows: an invalid column 0 gives coef0 = NaN on both planes
+    v[1] = ok ? p - q : NAN;
+    return ok;
   };
   fill_records<2, false>(coef_at, num_boot + 1, nullptr, st, red);
 }
@@ -543,7 +544,7 @@ int mm_contract_stats(const double *d_ym, const double *d_yv, int64_t ld, int32_
 
 int mm_valid_cols(const double *d_ym, const double *d_yv, int64_t ld, int32_t num_boot, int32_t n_groups, const uint8_t *d_good,
                   int64_t n_genes, int32_t *d_col_map, int32_t *d_n_valid, void *stream) {
-  MM_ARG(d_ym && d_yv && d_good && d_col_map && d_n_valid && n_groups > 0 && num_boot > 0 && ld >= (int64_t)num_boot + 1);
+  MM_ARG(d_ym && d_yv && d_good && d_col_map && d_n_valid && n_groups > 0 && num_boot >= 0 && ld >= (int64_t)num_boot + 1);
   MM_ARG(n_genes >= 0 && n_genes < 2147483647LL);
   if (n_genes == 0) return MM_OK;
   size_t shm = (size_t)n_groups * 4;

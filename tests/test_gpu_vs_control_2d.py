@@ -11,23 +11,12 @@ import pandas as pd
 import pytest
 import scipy.sparse as sp
 
+from _replicate_ref import _np_stats
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 KEYS = ["corr_coef", "corr_se", "corr_pval"]
-
-
-def _np_stats(row):
-    """The 8-double record of the contrast kernels restated in numpy for one coefficient row (NaN = dropped column)."""
-    c0 = row[0]
-    ok = np.isfinite(row)
-    v = row[1:][ok[1:]]
-    n = len(v)
-    mean1 = v.mean() if n else np.nan
-    allv = row[ok]
-    lo, hi = (allv.min(), allv.max()) if len(allv) else (np.inf, -np.inf)
-    return np.array([c0, np.sqrt(((v - mean1) ** 2).sum() / n) if n else np.nan, n, (np.abs(v - c0) > abs(c0)).sum(), mean1 - c0,
-                     1.0 if lo == hi else 0.0, (np.abs(v) > abs(c0)).sum(), hi - lo])
 
 
 def _plane(yc, ng, B, ld):
