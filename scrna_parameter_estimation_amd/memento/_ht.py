@@ -1,0 +1,271 @@
+"""What the four hypothesis-test drivers of ``main.py`` share: argument checks, the moments view of a 1D call, the chunk loops
+(one per dimension), the hash-uniform draw, the pair plan and the per-mask design tables.
+
+The chunk loops are generators that yield the opened chunk.  Both follow one rule, release-before-allocate: the previous
+chunk's ``Bootstrap1D`` / ``Bootstrap2D`` (tables, replicate rows, row closures) is dropped BEFORE the next one is constructed, so
+that the caching allocator hands the same buffers back and a call never holds two chunks' rows.  They can only drop their own
+references: a driver does a chunk's work in a function of its own, whose locals die when it returns.
+"""
+
+from types import SimpleNamespace
+
+import numpy as np
+
+from .. import engine
+from . import design as _design
+
+
+def check_args(rng, strict=False, **kwargs):
+    """The ``rng`` / ``strict`` checks of all four drivers and the reference's keyword arguments of the two ``*_moments`` drivers:
+    -> (resampling, resample_rep, approx).  The ``rng`` check comes first: it runs before ``adata`` is touched."""
+    if rng not in ('replay', 'fast'):
+        raise ValueError("rng must be 'replay' or 'fast'")
+    if strict and rng != 'replay':
+        raise ValueError("strict=True needs rng='replay'")
+    if 'resampling' not in kwargs:
+        raise TypeError("_compute_asl() missing 1 required positional argument: 'resampling'")
+    # 'bootstrap' centres the null on the observed value, anything else does not (hypothesis_test.py:66-70)
+    return kwargs['resampling'], bool(kwargs.get('resample_rep', False)), bool(kwargs.get('approx', False))
+
+
+def moments_view(m):
+    """What a 1D test reads from ``uns['memento']``: the groups, their q and cell counts, the true moments [group][gene] and the
+    mean-variance fit."""
+    groups = m['groups']
+    return SimpleNamespace(
+        groups=groups, ng=len(groups), mean_only=m['estimator_type'] == 'mean_only',
+        Nc_list=np.array([m['group_cells'][g].shape[0] for g in groups], dtype=np.float64),
+        gq=np.array([m['group_q'][g] for g in groups]),
+        true_mean=np.stack([m['1d_moments'][g][0] for g in groups]),
+        true_rv=np.stack([m['1d_moments'][g][2] for g in groups]),
+        fit=m['mv_regressor'][groups[0]])
+
+
+def pair_skip(true_mean, true_rv):
+    """hypothesis_test.py:167-171, vectorised over [n_groups][G] -> [pair] (gene-major)."""
+    with np.errstate(invalid="ignore"):
+        skip = np.isnan(true_mean) | np.isnan(true_rv) | (true_mean == 0) | (true_rv < 0)
+    return skip.T.reshape(-1)
+
+
+def hash_uniforms(live, k):
+    """The ``k`` hash uniforms of every live chain from the global ``np.random`` stream, in chain order: -> [k][chain], dead
+    chains keep 0.  The reference draws per chain -- ``random(1)`` then ``random()`` in 1D (bootstrap.py:62, :65), ``random(2)``
+    then ``random()`` per (pair, group) in 2D -- and ONE ``random(k * n)`` call takes the same stream positions."""
+    idx = np.flatnonzero(live)
+    out = np.zeros((k, len(live)))
+    u = np.random.random(k * len(idx))
+    for j in range(k):
+        out[j, idx] = u[j::k]
+    return out
+
+
+# ----------------------------------------------------------------------------------------------
+# 1D: gene chunks
+# ----------------------------------------------------------------------------------------------
+
+
+def chunks_1d(st, mv, num_boot, chunk):
+    """Open the genes in chunks of ``chunk``: yields ``c`` with ``g0``, ``g1``, ``G``, ``bs`` (K5 done, outputs allocated) and
+    ``skip`` [pair]; no gene kept, no chunk.  ``c`` is ONE object, emptied before the next chunk is opened
+    (release-before-allocate).  ``st.last_bootstrap`` / ``st.last_chunk`` hold the last chunk afterwards
+    (diagnostics / tests / bench: the last gene chunk's replicate rows)."""
+    G_all = len(st.gene_idx)
+    c = SimpleNamespace(bs=None, g0=0, g1=0)
+    for g0 in range(0, G_all, max(1, chunk)):
+        c.__dict__.clear()      # release the previous chunk's replicate rows first: the caching allocator hands them back
+        c.g0, c.g1 = g0, min(G_all, g0 + max(1, chunk))
+        c.G = c.g1 - g0
+        true_mean, true_rv = mv.true_mean[:, g0:c.g1], mv.true_rv[:, g0:c.g1]
+        c.bs = engine.Bootstrap1D(st.blocks, st.gene_idx[g0:c.g1], st.maxx, st.sf_bin, st.sf_table, mv.gq, num_boot)   # K5
+        c.skip = pair_skip(true_mean, true_rv)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            tm_log = np.where(c.skip, np.nan, np.log(true_mean.T.reshape(-1)))
+            tv_log = np.where(c.skip, np.nan, np.log(true_rv.T.reshape(-1)))
+        c.bs.alloc_outputs(tm_log, tv_log)
+        yield c
+    st.last_bootstrap, st.last_chunk = c.bs, (c.g0, c.g1)
+
+
+def gene_columns(treatment, treatment_for_gene, names):
+    """Treatment columns of every gene, looked up once per call: a tuple of column positions, or None = all columns."""
+    if treatment_for_gene is None:
+        return [None] * len(names)
+    trt_cols = list(treatment.columns)
+    return [tuple(trt_cols.index(c) for c in treatment_for_gene[n]) for n in names]
+
+
+# ----------------------------------------------------------------------------------------------
+# per-mask design tables
+# ----------------------------------------------------------------------------------------------
+
+
+def _take(trt, cols):
+    return trt if cols is None else trt[:, list(cols)]
+
+
+def design_tables(good, cols, cov, trt, Nc, resampled=False, rr_cols=None, first_only=False):
+    """The design of every test of a chunk: row ``k`` of ``good`` [rows][groups] (a gene or a pair) is tested once per treatment
+    column ``cols[k]`` (a tuple; None = all columns), gene-major x treatment column (main.py:399-404), or -- ``first_only`` -- on
+    the first of them.  Everything is built once per distinct (good mask, columns) and shared by the rows that have it.
+
+    -> ``test_row`` [test], ``Wmat`` [test][group] (``design.weight_rows``) and, when ``resampled``: ``tt_mat`` [test][group] /
+    ``Mstack`` [mask][group][group] (``design.residual_parts``), ``row_mask`` [row] (index into ``Mstack``) and ``rr_test``
+    [test].  ``rr_test`` is false where the treatment of the good groups is all ones -- those tests keep the weighted-average
+    branch (hypothesis_test.py:262-265, :384-386) and are not resampled -- and for a row without a good group.
+    ``rr_cols``: the columns the residual parts and the all-ones verdict are taken over, when they are not ``cols``."""
+    good = np.asarray(good, dtype=bool)
+    n_rows, ng = good.shape
+    rr_cols = cols if rr_cols is None else rr_cols
+    w_cache, r_cache = {}, {}
+    test_row, w_rows, tt_rows, Ms, rr = [], [], [], [], []
+    row_mask = np.zeros(n_rows, dtype=np.int32)
+    for k in range(n_rows):
+        key = (good[k].tobytes(), cols[k])
+        W = w_cache.get(key)
+        if W is None:
+            W = _design.weight_rows(cov, _take(trt, cols[k]), Nc, good[k])
+            W = w_cache[key] = W[:1] if first_only else W
+        test_row.extend([k] * len(W))
+        w_rows.append(W)
+        if not resampled:
+            continue
+        key = (good[k].tobytes(), rr_cols[k])
+        if key not in r_cache:
+            t = _take(trt, rr_cols[k])
+            Mg, ttg = _design.residual_parts(cov, t, Nc, good[k])
+            allones = (t[good[k]] == 1).mean() == 1 if good[k].any() else True
+            r_cache[key] = (len(Ms), ttg[:1] if first_only else ttg, not allones)
+            Ms.append(Mg)
+        row_mask[k], ttg, resample = r_cache[key]
+        tt_rows.append(ttg)
+        rr.extend([resample] * len(ttg))
+    d = SimpleNamespace(test_row=np.asarray(test_row, dtype=np.int64), tt_mat=None, Mstack=None, row_mask=None, rr_test=None,
+                        Wmat=np.concatenate(w_rows, axis=0) if w_rows else np.zeros((0, ng)))
+    if resampled:
+        d.tt_mat = np.concatenate(tt_rows, axis=0) if tt_rows else np.zeros((0, ng))
+        d.Mstack = np.stack(Ms) if Ms else np.zeros((0, ng, ng))
+        d.row_mask, d.rr_test = row_mask, np.asarray(rr, dtype=bool)
+    return d
+
+
+def pair_design_tables(good, tcol, per_gene, cov, trt, Nc, resampled=False):
+    """``design_tables`` for gene pairs: one test per pair, on treatment column ``tcol[k]``.  ``per_gene`` = the call has a
+    ``treatment_for_gene``.  Without one, the weight row is that of column 0 but the residual parts and the all-ones verdict are
+    taken over the WHOLE treatment (and row 0 of the result kept), as the reference does: with several treatment columns a pair is
+    resampled unless all of them are all ones."""
+    cols = [(int(t),) for t in tcol]
+    return design_tables(good, cols, cov, trt, Nc, resampled, rr_cols=cols if per_gene else [None] * len(cols), first_only=True)
+
+
+def surviving_cols(bs, good, num_boot):
+    """The replicate columns that survive hypothesis_test.py:249-251 / :372-373 (``bs.valid_cols``); (None, None) when nothing
+    was dropped (the usual case): identity map."""
+    col_map, n_valid = bs.valid_cols(good)
+    if (n_valid[good.any(axis=1)] == num_boot + 1).all():
+        return None, None
+    return col_map, n_valid
+
+
+def merge_resampled(coef, stt, coef_r, stt_r, rr_test):
+    """Coefficient rows (device) and statistics (host) of all tests: the resampled ones where ``rr_test``, else the plain ones."""
+    rr_idx = engine.dev(np.flatnonzero(rr_test))
+    coef[rr_idx] = coef_r[rr_idx]
+    return coef, np.where(rr_test[:, None], stt_r, stt)
+
+
+# ----------------------------------------------------------------------------------------------
+# 2D: pair chunks
+# ----------------------------------------------------------------------------------------------
+
+
+def distinct_pairs(idx1, idx2):
+    """The distinct unordered pairs of a pair list: ``first`` = position of every distinct pair's first appearance (self pairs
+    skipped; main.py:467-482), ``members[k]`` = all positions that share pair k's result."""
+    first, members, seen = [], [], {}
+    for c in range(len(idx1)):
+        a, b = int(idx1[c]), int(idx2[c])
+        if a == b:
+            continue
+        k = seen.setdefault(frozenset((a, b)), len(first))
+        if k == len(first):
+            first.append(c)
+            members.append([])
+        members[k].append(c)
+    return np.asarray(first, dtype=np.int64), members
+
+
+def pair_plan(m, st, num_boot, max_rows):
+    """The pairs of ``compute_2d_moments`` as the 2D tests run them: ``first`` / ``members`` (``distinct_pairs`` over the
+    ``n_conv`` requested pairs), ``c1`` / ``c2`` = the distinct pairs' column slots, ``true_corr`` [pair][group], ``skip``
+    (hypothesis_test.py:325), ``chain_key`` and the chunk ``bounds``: pairs are independent, so they run in chunks of at most
+    ``max_rows`` replicate rows ([pair x group][B+1] fp64) AND at most a third of the free HBM in histogram tables."""
+    groups = m['groups']
+    ng = len(groups)
+    idx1, idx2 = m['2d_moments']['gene_idx_1'], m['2d_moments']['gene_idx_2']
+    first, members = distinct_pairs(idx1, idx2)
+    P_ = len(first)
+    slot = {int(g): i for i, g in enumerate(st.cols_local)}
+    c1 = np.array([slot[int(idx1[c])] for c in first], dtype=np.int64)
+    c2 = np.array([slot[int(idx2[c])] for c in first], dtype=np.int64)
+    true_corr = np.stack([m['2d_moments'][g]['corr'][first] for g in groups], axis=1) if P_ else np.zeros((0, ng))   # [pair][group]
+    with np.errstate(invalid="ignore"):
+        skip = np.isnan(true_corr) | (np.abs(true_corr) == 1)
+    if max_rows is None:
+        max_rows = min(1 << 19, engine.auto_max_rows(num_boot + 1, arrays=1))   # also bounds the per-pair 2D tables
+    chunk = max(1, int(max_rows) // max(1, ng))
+    tab_bytes = engine.pair_table_bytes(st.maxx, st.cols.genes, c1, c2, ng, len(st.sf_table)) if P_ else np.zeros(0, dtype=np.int64)
+    budget = max(1 << 28, engine._torch().cuda.mem_get_info()[0] // 3)
+    bounds, acc = [0], 0
+    for k in range(P_):
+        if k - bounds[-1] >= chunk or (acc + int(tab_bytes[k]) > budget and k > bounds[-1]):
+            bounds.append(k)
+            acc = 0
+        acc += int(tab_bytes[k])
+    bounds.append(P_)
+    return SimpleNamespace(
+        ng=ng, n_conv=idx1.shape[0], idx1=idx1, first=first, members=members, P_=P_, c1=c1, c2=c2, true_corr=true_corr, skip=skip,
+        bounds=bounds, gq=np.array([m['group_q'][g] for g in groups]),
+        chain_key=np.arange(P_ * ng, dtype=np.int64))        # rng='fast': stream key of (pair k, group) = k * n_groups + group
+
+
+def chunks_2d(st, plan, num_boot):
+    """Open the distinct pairs in the chunks of ``plan.bounds``: yields ``c`` with ``lo``, ``hi``, ``n_ch``, ``bs`` (pair tables
+    built) and ``so`` = the device pair order (sorted by left column).  ``c`` is ONE object, emptied before the next chunk is opened
+    (release-before-allocate).  ``st.last_bootstrap2d`` / ``st.last_chunk2d`` hold the last chunk afterwards (diagnostics / tests:
+    pair range of the last chunk)."""
+    c = SimpleNamespace(bs=None)
+    for lo, hi in zip(plan.bounds[:-1], plan.bounds[1:]):
+        if hi <= lo:
+            continue
+        c.__dict__.clear()      # release the previous chunk's tables and replicate rows first: the caching allocator hands them back
+        c.lo, c.hi, c.n_ch = lo, hi, hi - lo
+        c.bs = engine.Bootstrap2D(st.cols, plan.c1[lo:hi], plan.c2[lo:hi], st.maxx, st.sf_bin, st.sf_table, plan.gq, num_boot)
+        c.so = c.bs.order
+        yield c
+    st.last_bootstrap2d = c.bs
+    st.last_chunk2d = (plan.bounds[-2], plan.bounds[-1]) if plan.P_ else (0, 0)
+
+
+def run_chunk_2d(c, plan, uniforms, rng, fill_seed):
+    """Bootstrap the chunk's chains with the hash ``uniforms`` [3][pair x group] of the whole call; -> ``good`` [pair][group] in
+    device pair order."""
+    ng = plan.ng
+
+    def to_dev_order(a):
+        return a[c.lo * ng:c.hi * ng].reshape(c.n_ch, ng)[c.so].reshape(-1)
+
+    r1a, r1b, r0 = uniforms
+    c.bs.run(to_dev_order(plan.skip.reshape(-1)), to_dev_order(r1a), to_dev_order(r1b), to_dev_order(r0),
+             to_dev_order(np.where(plan.skip, np.nan, plan.true_corr).reshape(-1)), fast=(rng == 'fast'), fast_seed=fill_seed,
+             pair_key=to_dev_order(plan.chain_key))
+    return c.bs.active.reshape(c.n_ch, ng)
+
+
+def scatter_pairs(c, plan, dst, src, keep=None):
+    """Results of the chunk's pairs (``src`` [pair][...], device pair order) to every requested pair that shares them
+    (``dst`` [n_conv][...]); ``keep`` [pair]: the pairs that have a result."""
+    src = np.asarray(src).reshape(c.n_ch, -1)
+    for k in range(c.n_ch):
+        if keep is None or keep[k]:
+            dst[plan.members[c.lo + c.so[k]]] = src[k]

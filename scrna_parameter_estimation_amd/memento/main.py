@@ -15,6 +15,7 @@ Host code here is argument handling, the uns schema, O(G) post-processing (polyf
 matrix, p-values); every O(nnz) or O(G x groups x B) step is a kernel launch via ``engine``.
 """
 
+import functools
 import itertools
 
 import numpy as np
@@ -23,6 +24,7 @@ import scipy.stats as stats
 from scipy.sparse import csr_matrix
 
 from .. import engine
+from . import _ht, _strict1d
 from . import asl as _asl
 from . import design as _design
 
@@ -379,25 +381,6 @@ def _var_names(adata):
 # ----------------------------------------------------------------------------------------------
 
 
-def _pair_skip(true_mean, true_rv):
-    """hypothesis_test.py:167-171, vectorised over [n_groups][G] -> [pair] (gene-major)."""
-    with np.errstate(invalid="ignore"):
-        skip = np.isnan(true_mean) | np.isnan(true_rv) | (true_mean == 0) | (true_rv < 0)
-    return skip.T.reshape(-1)
-
-
-def _host_fill(row):
-    """hypothesis_test._fill on an already-logged row: NaN = invalid; draws from the global np.random
-    stream exactly like np.random.choice(val[~cond], num_invalid) (hypothesis_test.py:23-33)."""
-    bad = np.isnan(row)
-    nbad = int(bad.sum())
-    if nbad == row.shape[0]:
-        return None
-    row = row.copy()
-    row[bad] = np.random.choice(row[~bad], nbad)
-    return row
-
-
 def ht_1d_moments(adata, covariate, treatment, treatment_for_gene=None, inplace=True, num_boot=10000, verbose=1, num_cpus=1,
                   rng='replay', strict=False, fill_seed=0, max_rows=None, **kwargs):
     """Bootstrap hypothesis test of mean / residual-variance differences (reference: memento/main.py:341-415).
@@ -414,253 +397,20 @@ def ht_1d_moments(adata, covariate, treatment, treatment_for_gene=None, inplace=
     with ``strict=False`` invalid replicates are re-filled on the device with a counter-based RNG.
     kwargs: ``resampling`` (required, as in the reference), ``approx``, ``resample_rep``.
     """
-    if 'resampling' not in kwargs:
-        raise TypeError("_compute_asl() missing 1 required positional argument: 'resampling'")
-    resampling = kwargs['resampling']       # 'bootstrap' centres the null on the observed value, anything else does not (:66-70)
-    resample_rep = bool(kwargs.get('resample_rep', False))
-    if rng not in ('replay', 'fast'):
-        raise ValueError("rng must be 'replay' or 'fast'")
-    if strict and rng != 'replay':
-        raise ValueError("strict=True needs rng='replay'")
-    approx = bool(kwargs.get('approx', False))
+    resampling, resample_rep, approx = _ht.check_args(rng, strict, **kwargs)
     if not inplace:
         adata = adata.copy()
     m = adata.uns['memento']
     st = m['_hip']
-    mean_only = m['estimator_type'] == 'mean_only'
-    groups = m['groups']
-    ng = len(groups)
+    mv = _ht.moments_view(m)
+    ng = mv.ng
     names = _var_names(adata)
-    G = len(st.gene_idx)
-    Nc_list = np.array([m['group_cells'][g].shape[0] for g in groups], dtype=np.float64)
+    G_all = len(st.gene_idx)
     cov = np.asarray(covariate.values, dtype=np.float64)
     trt_all = np.asarray(treatment.values, dtype=np.float64)
-    trt_cols = list(treatment.columns)
-    gq = np.array([m['group_q'][g] for g in groups])
-    true_mean = np.stack([m['1d_moments'][g][0] for g in groups])
-    true_rv = np.stack([m['1d_moments'][g][2] for g in groups])
-    fit = m['mv_regressor'][groups[0]]
+    gene_cols = _ht.gene_columns(treatment, treatment_for_gene, names[:G_all])
     if st.sf_bin is None:
         raise NotImplementedError("more than 255 size-factor bins")
-
-    def run_range(g0, g1):
-        """One chunk of genes [g0, g1): K5 histograms -> bootstrap -> contraction -> p-values."""
-        G = g1 - g0
-        bs = engine.Bootstrap1D(st.blocks, st.gene_idx[g0:g1], st.maxx, st.sf_bin, st.sf_table, gq, num_boot)   # K5
-        skip = _pair_skip(true_mean[:, g0:g1], true_rv[:, g0:g1])
-        with np.errstate(invalid="ignore", divide="ignore"):
-            tm_log = np.where(skip, np.nan, np.log(true_mean[:, g0:g1].T.reshape(-1)))
-            tv_log = np.where(skip, np.nan, np.log(true_rv[:, g0:g1].T.reshape(-1)))
-        bs.alloc_outputs(tm_log, tv_log)
-        n_pairs = bs.n_pairs
-        r1, r0 = np.zeros(n_pairs), np.zeros(n_pairs)
-        live = np.flatnonzero(~skip)
-
-        pair_gene = np.arange(n_pairs) // ng
-        known_bad = np.zeros(n_pairs, dtype=bool)       # pairs whose fill found no valid replicate (strict mode bookkeeping)
-        rep_assign = bcol_assign = None
-        if resample_rep and strict:
-            rep_assign = np.zeros((G, ng, num_boot), dtype=np.int16)
-            bcol_assign = np.zeros((G, ng, num_boot), dtype=np.int32)
-
-        def gene_uses_resampling(gi, n_good):
-            if not resample_rep or n_good == 0:
-                return False
-            cols = None if treatment_for_gene is None else [trt_cols.index(c) for c in treatment_for_gene[names[g0 + gi]]]
-            t = trt_all if cols is None else trt_all[:, cols]
-            gmask = ((~skip) & (bs.K >= 2) & ~known_bad)[gi * ng:(gi + 1) * ng]
-            return not (t[gmask] == 1).mean() == 1                                                   # hypothesis_test.py:262
-
-        nb_eff = {}      # genes whose replicate columns are not all finite: columns left after hypothesis_test.py:249-251, minus one
-
-        def draw_assignments(gi):
-            n = int(((~skip) & (bs.K >= 2) & ~known_bad)[gi * ng:(gi + 1) * ng].sum())
-            if gene_uses_resampling(gi, n):
-                nb = nb_eff.get(gi, num_boot)                                  # hypothesis_test.py:253
-                if nb < 1:
-                    return
-                ra = np.random.choice(n, size=(n, nb))                         # hypothesis_test.py:275-278
-                ra[:, 0] = np.arange(n)
-                ba = np.random.choice(nb, (n, nb)) + 1
-                ba[:, 0] = 0
-                rep_assign[gi, :n, :nb], bcol_assign[gi, :n, :nb] = ra, ba
-
-        def draw_stream(first, stop_pair=None, pending=None):
-            """Consume the global np.random stream exactly as the reference does from pair ``first`` on: per gene the two
-            hash uniforms of every live group (bootstrap.py:62,65) and -- with resample_rep -- the two np.random.choice
-            draws of _regress_1d (hypothesis_test.py:275-278) after the gene's last group.  ``pending``: a gene whose
-            groups are all done but whose choice draws are still due; ``stop_pair``: stop right after that pair's hash."""
-            if not (resample_rep and strict):
-                idx = live[live >= first] if stop_pair is None else live[(live >= first) & (live <= stop_pair)]
-                u = np.random.random(2 * len(idx))      # same stream positions as random(1) then random() per pair
-                r1[idx], r0[idx] = u[0::2], u[1::2]
-                return
-            if pending is not None:
-                draw_assignments(pending)
-            for gi in range(int(first // ng), G):
-                lo_p = max(first, gi * ng)
-                hi_p = (gi + 1) * ng - 1 if stop_pair is None else min((gi + 1) * ng - 1, stop_pair)
-                idx = live[(live >= lo_p) & (live <= hi_p)]
-                u = np.random.random(2 * len(idx))
-                r1[idx], r0[idx] = u[0::2], u[1::2]
-                if stop_pair is not None and stop_pair < (gi + 1) * ng:
-                    return
-                draw_assignments(gi)
-
-        if not strict:
-            if shard_stream is not None:      # gene-sharded: this rank's slice of the ONE global stream (see below)
-                r1[:], r0[:] = shard_stream[0][g0 * ng:g1 * ng], shard_stream[1][g0 * ng:g1 * ng]
-            else:
-                draw_stream(0)
-            keys = (fill_pos[g0:g1, None] * ng + np.arange(ng)[None, :]).reshape(-1)      # refill streams keyed by (gene, group)
-            chain_keys = (chain_pos[g0:g1, None] * ng + np.arange(ng)[None, :]).reshape(-1)     # rng='fast' streams, likewise
-            n_inv = bs.run(skip, r1, r0, fit, fill_mode=0, fill_seed=fill_seed, fast=(rng == 'fast'), mean_only=mean_only,
-                           fill_keys=keys, chain_keys=chain_keys)                         # K6-K8
-            bad_fill = (n_inv < 0).any(axis=1)
-            # how much of the result depends on the device refill (strict=True replays the reference's own _fill draws instead):
-            # chains / genes with at least one refilled replicate -- all others are bit-identical to the strict path
-            refilled = (n_inv > 0).any(axis=1) & ~skip
-            rs = st.refill_stats
-            rs['chains'] += int(((~skip) & (bs.K >= 2)).sum())
-            rs['chains_refilled'] += int(refilled.sum())
-            rs['genes'] += G
-            rs['genes_refilled'] += int(refilled.reshape(G, ng).any(axis=1).sum())
-            rs['gene_refilled'][g0:g1] = refilled.reshape(G, ng).any(axis=1)
-        else:
-            def strict_pass():
-                """One sequential replay of the reference's global-stream consumption over all genes (speculate, then roll back to
-                the first pair whose _fill draws -- or, under resample_rep, shrinking num_rep -- shift the stream)."""
-                n_inv_all = np.zeros((n_pairs, 2), dtype=np.int32)
-                first, pending = 0, None
-                while first < n_pairs:
-                    saved = np.random.get_state()
-                    draw_stream(first, pending=pending)
-                    after = np.random.get_state()
-                    n_inv = bs.run(skip, r1, r0, fit, fill_mode=1, first_pair=first, mean_only=mean_only)
-                    n_inv_all[first:] = n_inv
-                    event = (n_inv > 0).any(axis=1)
-                    if resample_rep:
-                        event |= (n_inv < 0).any(axis=1) & ~known_bad[first:]      # a group without valid replicates shrinks num_rep
-                    needs = np.flatnonzero((~skip[first:]) & event) + first
-                    if len(needs) == 0:
-                        np.random.set_state(after)
-                        pending = None
-                        break
-                    p = int(needs[0])
-                    np.random.set_state(saved)
-                    draw_stream(first, stop_pair=p, pending=pending)                # everything the reference drew up to pair p's hash
-                    for t, col in ((bs.ym, 0), (bs.yv, 1)):
-                        if n_inv_all[p, col] > 0:
-                            row = engine.host(t[p, 1:])
-                            t[p, 1:] = engine.dev(_host_fill(row))
-                            n_inv_all[p, col] = 0
-                    if (n_inv_all[p] < 0).any():
-                        known_bad[p] = True
-                    pending = p // ng if (resample_rep and p % ng == ng - 1) else None
-                    first = p + 1
-                if pending is not None:
-                    draw_assignments(pending)
-                return (n_inv_all < 0).any(axis=1)
-
-            stream0 = np.random.get_state()
-            for _attempt in range(3):
-                bad_fill = strict_pass()
-                if not resample_rep:
-                    break
-                # The reference draws a gene's assignments for the replicate columns that SURVIVE hypothesis_test.py:249-251,
-                # which is known only after its bootstrap: when a resampled gene lost columns, replay once more with that count.
-                good_now = ((~skip) & (bs.K >= 2) & ~bad_fill).reshape(G, ng)
-                _, nv = bs.valid_cols(good_now)
-                redo = False
-                for gi in np.flatnonzero(nv != num_boot + 1):
-                    gi = int(gi)
-                    if gene_uses_resampling(gi, int(good_now[gi].sum())) and nb_eff.get(gi, num_boot) != int(nv[gi]) - 1:
-                        nb_eff[gi] = int(nv[gi]) - 1
-                        redo = True
-                if not redo:
-                    break
-                np.random.set_state(stream0)
-                known_bad[:] = False
-
-        active_all = (~skip) & (bs.K >= 2)                       # bootstrap.py:97-98: a single bin gives NaN replicates
-        good = (active_all & ~bad_fill).reshape(G, ng)           # hypothesis_test.py:193-200
-
-        # tests: gene-major x treatment column (main.py:399-404)
-        test_gene, test_rows = [], []
-        cache = {}
-        for gi in range(G):
-            if treatment_for_gene is None:
-                cols = None
-                nt = trt_all.shape[1]
-            else:
-                cols = [trt_cols.index(c) for c in treatment_for_gene[names[g0 + gi]]]
-                nt = len(cols)
-            key = (good[gi].tobytes(), None if cols is None else tuple(cols))
-            W = cache.get(key)
-            if W is None:
-                t = trt_all if cols is None else trt_all[:, cols]
-                W = _design.weight_rows(cov, t, Nc_list, good[gi])
-                if W.shape[0] != nt:
-                    W = np.repeat(W[:1], nt, axis=0)
-                cache[key] = W
-            test_gene.extend([gi] * nt)
-            test_rows.append(W)
-        n_tests = len(test_gene)
-        Wmat = np.concatenate(test_rows, axis=0) if test_rows else np.zeros((0, ng))
-        out = {}
-        use_rr = resample_rep and n_tests > 0
-        if use_rr:
-            # residual maker / residualised treatment per valid-group mask; tests whose treatment is all ones keep the
-            # weighted-average branch (hypothesis_test.py:262-265) and are not resampled
-            masks, gene_mask, tt_rows, rr_test = {}, np.zeros(G, dtype=np.int32), [], np.zeros(n_tests, dtype=bool)
-            Ms = []
-            ti = 0
-            for gi in range(G):
-                cols = None if treatment_for_gene is None else [trt_cols.index(c) for c in treatment_for_gene[names[g0 + gi]]]
-                t = trt_all if cols is None else trt_all[:, cols]
-                key = (good[gi].tobytes(), None if cols is None else tuple(cols))
-                if key not in masks:
-                    Mg, ttg = _design.residual_parts(cov, t, Nc_list, good[gi])
-                    masks[key] = (len(Ms), ttg)
-                    Ms.append(Mg)
-                gene_mask[gi], ttg = masks[key]
-                nt = t.shape[1]
-                allones = good[gi].any() and (t[good[gi]] == 1).mean() == 1
-                tt_rows.append(ttg)
-                rr_test[ti:ti + nt] = not allones
-                ti += nt
-            tt_mat = np.concatenate(tt_rows, axis=0)
-            Mstack = np.stack(Ms)
-        col_map = n_valid = None
-        if use_rr and rr_test.any():
-            col_map, n_valid = bs.valid_cols(good)                  # hypothesis_test.py:249-251
-            if (n_valid[good.any(axis=1)] == num_boot + 1).all():
-                col_map = n_valid = None                            # nothing dropped (the usual case): identity map
-        for which, tag in ((0, 'mean'), (1, 'var')):
-            coef, stt = bs.contract(test_gene, Wmat, good, which)                                         # K9+K10
-            if use_rr and rr_test.any():
-                coef_r, stt_r = bs.contract_resampled(test_gene, tt_mat, good, which, gene_mask, Mstack, Nc_list,
-                                                      rep_assign, bcol_assign, seed=fill_seed + 17, col_map=col_map, n_valid=n_valid)
-                stt = np.where(rr_test[:, None], stt_r, stt)
-                rr_idx = engine.dev(np.flatnonzero(rr_test))
-                coef[rr_idx] = coef_r[rr_idx]
-            no_group = ~good[np.asarray(test_gene, dtype=np.int64)].any(axis=1) if n_tests else np.zeros(0, bool)
-            c0, se = stt[:, 0].copy(), stt[:, 1].copy()
-            # the tail fits of the mean tests run in the worker pool while the variance contraction is enqueued
-            fin = _asl.asl_from_stats(stt, approx, lambda idx, coef=coef: engine.host(coef[engine.dev(np.asarray(idx, dtype=np.int64))]),
-                                      num_cpus, resampling, defer=True)
-            c0[no_group], se[no_group] = np.nan, np.nan                                                   # hypothesis_test.py:203-204
-            out[tag + '_coef'], out[tag + '_se'], out[tag + '_asl'] = c0, se, (fin, no_group)
-        for tag in ('mean', 'var'):
-            fin, no_group = out[tag + '_asl']
-            p = fin()
-            p[no_group] = np.nan
-            out[tag + '_asl'] = p
-        st.last_bootstrap = bs
-        st.last_assignments = (rep_assign, bcol_assign)
-        return out
-
-    G_all = len(st.gene_idx)
     comm = getattr(st, 'comm', None)
     sharded = comm is not None and comm.world > 1
     shard_stream = gene_pos = None
@@ -686,7 +436,7 @@ def ht_1d_moments(adata, covariate, treatment, treatment_for_gene=None, inplace=
                                           "(setup_memento(shard='contiguous') or a pre-sliced range); cost-balanced shards interleave")
         else:
             from ..dist import shard_stream_uniforms
-            shard_stream = shard_stream_uniforms(comm, gene_pos, (~_pair_skip(true_mean, true_rv)).reshape(G_all, ng))
+            shard_stream = shard_stream_uniforms(comm, gene_pos, (~_ht.pair_skip(mv.true_mean, mv.true_rv)).reshape(G_all, ng))
     # position of every kept gene in the unsharded, unfiltered gene order: keys the device refill streams, so that the timed mode's
     # results do not depend on gene chunking or on the sharding over GPUs
     fill_pos = (np.asarray(st.shard, dtype=np.int64)[st.gene_idx] if getattr(st, 'shard', None) is not None
@@ -697,6 +447,68 @@ def ht_1d_moments(adata, covariate, treatment, treatment_for_gene=None, inplace=
     chain_pos = np.arange(G_all, dtype=np.int64)
     if sharded and not strict:
         chain_pos = np.searchsorted(np.sort(np.concatenate(comm.allgather_objects(gene_pos))), gene_pos).astype(np.int64)
+
+    def run_range(c):
+        """One chunk of genes [g0, g1), opened (K5 histograms): bootstrap -> contraction -> p-values."""
+        g0, g1, G, bs, skip = c.g0, c.g1, c.G, c.bs, c.skip
+        rep_assign = bcol_assign = None
+        if not strict:
+            if shard_stream is not None:      # gene-sharded: this rank's slice of the ONE global stream (see above)
+                r1, r0 = shard_stream[0][g0 * ng:g1 * ng], shard_stream[1][g0 * ng:g1 * ng]
+            else:
+                r1, r0 = _ht.hash_uniforms(~skip, 2)
+            keys = (fill_pos[g0:g1, None] * ng + np.arange(ng)[None, :]).reshape(-1)      # refill streams keyed by (gene, group)
+            chain_keys = (chain_pos[g0:g1, None] * ng + np.arange(ng)[None, :]).reshape(-1)     # rng='fast' streams, likewise
+            n_inv = bs.run(skip, r1, r0, mv.fit, fill_mode=0, fill_seed=fill_seed, fast=(rng == 'fast'), mean_only=mv.mean_only,
+                           fill_keys=keys, chain_keys=chain_keys)                         # K6-K8
+            bad_fill = (n_inv < 0).any(axis=1)
+            # how much of the result depends on the device refill (strict=True replays the reference's own _fill draws instead):
+            # chains / genes with at least one refilled replicate -- all others are bit-identical to the strict path
+            refilled = (n_inv > 0).any(axis=1) & ~skip
+            rs = st.refill_stats
+            rs['chains'] += int(((~skip) & (bs.K >= 2)).sum())
+            rs['chains_refilled'] += int(refilled.sum())
+            rs['genes'] += G
+            rs['genes_refilled'] += int(refilled.reshape(G, ng).any(axis=1).sum())
+            rs['gene_refilled'][g0:g1] = refilled.reshape(G, ng).any(axis=1)
+        else:
+            run_from = functools.partial(bs.run, skip, mv_fit=mv.fit, fill_mode=1, mean_only=mv.mean_only)
+            gene_trt = [trt_all if k is None else trt_all[:, list(k)] for k in gene_cols[g0:g1]] if resample_rep else None
+            replay = _strict1d.StrictReplay(c, run_from, gene_trt)
+            bad_fill = replay.run()
+            rep_assign, bcol_assign = replay.rep_assign, replay.bcol_assign
+
+        active_all = (~skip) & (bs.K >= 2)                       # bootstrap.py:97-98: a single bin gives NaN replicates
+        good = (active_all & ~bad_fill).reshape(G, ng)           # hypothesis_test.py:193-200
+        # tests: gene-major x treatment column (main.py:399-404)
+        d = _ht.design_tables(good, gene_cols[g0:g1], cov, trt_all, mv.Nc_list, resampled=resample_rep)
+        test_gene = d.test_row
+        no_group = ~good[test_gene].any(axis=1)
+        use_rr = resample_rep and d.rr_test.any()
+        col_map = n_valid = None
+        if use_rr:
+            col_map, n_valid = _ht.surviving_cols(bs, good, num_boot)                                     # hypothesis_test.py:249-251
+        out = {}
+        for which, tag in ((0, 'mean'), (1, 'var')):
+            coef, stt = bs.contract(test_gene, d.Wmat, good, which)                                       # K9+K10
+            if use_rr:
+                coef_r, stt_r = bs.contract_resampled(test_gene, d.tt_mat, good, which, d.row_mask, d.Mstack, mv.Nc_list,
+                                                      rep_assign, bcol_assign, seed=fill_seed + 17, col_map=col_map, n_valid=n_valid)
+                coef, stt = _ht.merge_resampled(coef, stt, coef_r, stt_r, d.rr_test)
+            c0, se = stt[:, 0].copy(), stt[:, 1].copy()
+            # the tail fits of the mean tests run in the worker pool while the variance contraction is enqueued
+            fin = _asl.asl_from_stats(stt, approx, lambda idx, coef=coef: engine.host(coef[engine.dev(np.asarray(idx, dtype=np.int64))]),
+                                      num_cpus, resampling, defer=True)
+            c0[no_group], se[no_group] = np.nan, np.nan                                                   # hypothesis_test.py:203-204
+            out[tag + '_coef'], out[tag + '_se'], out[tag + '_asl'] = c0, se, (fin, no_group)
+        for tag in ('mean', 'var'):
+            fin, no_group = out[tag + '_asl']
+            p = fin()
+            p[no_group] = np.nan
+            out[tag + '_asl'] = p
+        st.last_assignments = (rep_assign, bcol_assign)
+        return out
+
     st.refill_stats = dict(chains=0, chains_refilled=0, genes=0, genes_refilled=0, gene_refilled=np.zeros(G_all, dtype=bool))
     st.last_bootstrap = None                   # the previous call's replicate rows (GBs) go back to the caching allocator BEFORE this call allocates its own
     if max_rows is None:                       # replicate buffers sized to the free HBM (288 GB on MI355X)
@@ -706,11 +518,11 @@ def ht_1d_moments(adata, covariate, treatment, treatment_for_gene=None, inplace=
         parts = []
         for turn in range(comm.world):                # rank after rank, the np.random state handed on
             if turn == comm.rank:
-                parts = [run_range(g0, min(G_all, g0 + chunk)) for g0 in range(0, G_all, chunk)] if G_all else []
+                parts = [run_range(c) for c in _ht.chunks_1d(st, mv, num_boot, chunk)]
             states = comm.allgather_objects(np.random.get_state() if turn == comm.rank else None)
             np.random.set_state(states[turn])
     else:
-        parts = [run_range(g0, min(G_all, g0 + chunk)) for g0 in range(0, G_all, chunk)] if G_all else []
+        parts = [run_range(c) for c in _ht.chunks_1d(st, mv, num_boot, chunk)]
     keys = ('mean_coef', 'mean_se', 'mean_asl', 'var_coef', 'var_se', 'var_asl')
     out = {k: (np.concatenate([p_[k] for p_ in parts]) if parts else np.zeros(0)) for k in keys}
     m['1d_ht'] = {}
@@ -718,15 +530,14 @@ def ht_1d_moments(adata, covariate, treatment, treatment_for_gene=None, inplace=
         # gene-sharded run: scatter-back of the reference (main.py:399-412) across ranks -- every rank ends with the flat result
         # vectors of ALL genes in the unsharded run's order, plus the gene names they belong to
         from ..dist import gather_1d_ht
-        nt_gene = (np.full(G_all, trt_all.shape[1], dtype=np.int64) if treatment_for_gene is None
-                   else np.array([len(treatment_for_gene[n_]) for n_ in names[:G_all]], dtype=np.int64))
+        nt_gene = np.array([trt_all.shape[1] if k is None else len(k) for k in gene_cols], dtype=np.int64)
         st.local_ht = {k: np.asarray(v).copy() for k, v in out.items()}          # this rank's own tests (bench: per-rank accounting)
         m['1d_ht']['gene_names'], out = gather_1d_ht(comm, names, out, gene_pos=gene_pos, n_tests=nt_gene)
     if treatment_for_gene is not None:
         m['1d_ht']['treatment_for_gene'] = treatment_for_gene
     m['1d_ht']['treatment'] = treatment
     m['1d_ht']['covariate'] = covariate
-    for k in ('mean_coef', 'mean_se', 'mean_asl', 'var_coef', 'var_se', 'var_asl'):
+    for k in keys:
         m['1d_ht'][k] = out[k]
     if not inplace:
         return adata
@@ -784,41 +595,26 @@ def ht_1d_vs_control(adata, control, num_boot=10000, num_cpus=1, rng='replay', f
 
     Returns a DataFrame (gene, group, de_coef, de_se, de_pval, dv_coef, dv_se, dv_pval) and stores the arrays in
     ``uns['memento']['1d_ht_vs_control']``."""
+    _ht.check_args(rng, resampling=resampling)
     m = adata.uns['memento']
     st = m['_hip']
-    groups = m['groups']
-    ng = len(groups)
     tested, designs, (ctrl, others), meta = _vs_control_plan(m, control, treatment_col)
-    mean_only = m['estimator_type'] == 'mean_only'
+    mv = _ht.moments_view(m)
+    ng = mv.ng
     names = _var_names(adata)
-    gq = np.array([m['group_q'][g] for g in groups])
-    true_mean = np.stack([m['1d_moments'][g][0] for g in groups])
-    true_rv = np.stack([m['1d_moments'][g][2] for g in groups])
-    fit = m['mv_regressor'][groups[0]]
     G_all = len(st.gene_idx)
     if max_rows is None:                       # (40 % of the free HBM: BASELINE configs[4] then runs in two chunks, the second reusing the
         max_rows = engine.auto_max_rows(num_boot + 1, arrays=2)   # first one's buffers; ONE 108 GB chunk is 1 s faster in a warm process but 1.6 s
                                                                  # slower in a fresh one -- mapping fresh device memory costs ~30 ms per GB)
     chunk = max(1, int(max_rows) // max(1, ng))
     cols = {k: [] for k in ('mean_coef', 'mean_se', 'mean_asl', 'var_coef', 'var_se', 'var_asl')}
-    bs = rows = None
     st.last_bootstrap = st.last_good = None    # (see ht_1d_moments: free the previous call's replicate rows first)
-    for g0 in range(0, G_all, chunk):
-        g1 = min(G_all, g0 + chunk)
-        G = g1 - g0
-        del bs, rows            # release the previous chunk's replicate rows first: the caching allocator hands them back
-        bs = engine.Bootstrap1D(st.blocks, st.gene_idx[g0:g1], st.maxx, st.sf_bin, st.sf_table, gq, num_boot)
-        skip = _pair_skip(true_mean[:, g0:g1], true_rv[:, g0:g1])
-        with np.errstate(invalid="ignore", divide="ignore"):
-            tm_log = np.where(skip, np.nan, np.log(true_mean[:, g0:g1].T.reshape(-1)))
-            tv_log = np.where(skip, np.nan, np.log(true_rv[:, g0:g1].T.reshape(-1)))
-        bs.alloc_outputs(tm_log, tv_log)
-        r1, r0 = np.zeros(bs.n_pairs), np.zeros(bs.n_pairs)
-        live = np.flatnonzero(~skip)
-        u = np.random.random(2 * len(live))
-        r1[live], r0[live] = u[0::2], u[1::2]
+
+    def run_chunk(c):
+        g0, g1, G, bs, skip = c.g0, c.g1, c.G, c.bs, c.skip
+        r1, r0 = _ht.hash_uniforms(~skip, 2)
         keys = np.arange(g0 * ng, g1 * ng, dtype=np.int64)      # (g0 + gene) * ng + group: the chain's row in the one-chunk call
-        n_inv = bs.run(skip, r1, r0, fit, fill_mode=0, fill_seed=fill_seed, fast=(rng == 'fast'), mean_only=mean_only,
+        n_inv = bs.run(skip, r1, r0, mv.fit, fill_mode=0, fill_seed=fill_seed, fast=(rng == 'fast'), mean_only=mv.mean_only,
                        fill_keys=keys, chain_keys=keys)
         good = ((~skip) & (bs.K >= 2) & ~(n_inv < 0).any(axis=1)).reshape(G, ng)
         st.last_good = good                    # (diagnostics / tests: the good groups of the last gene chunk)
@@ -834,8 +630,10 @@ def ht_1d_vs_control(adata, control, num_boot=10000, num_cpus=1, rng='replay', f
             cols[tag + '_coef'].append(stt[:, 0])
             cols[tag + '_se'].append(stt[:, 1])
             cols[tag + '_asl'].append(p)
+
+    for c in _ht.chunks_1d(st, mv, num_boot, chunk):
+        run_chunk(c)
     out = {k: (np.concatenate(v) if v else np.zeros(0)) for k, v in cols.items()}
-    st.last_bootstrap, st.last_chunk = bs, ((g0, g1) if G_all else (0, 0))       # diagnostics / tests: the last gene chunk's replicate rows
     m['1d_ht_vs_control'] = dict(out, **meta)
     df = pd.DataFrame({'gene': np.repeat(names, len(tested)), 'group': np.tile(tested, G_all)})
     df['de_coef'], df['de_se'], df['de_pval'] = out['mean_coef'], out['mean_se'], out['mean_asl']
@@ -936,46 +734,32 @@ def get_corr_matrix(adata, group):
     return corr
 
 
-def _pair_plan(m, st, num_boot, max_rows):
-    """The pairs of ``compute_2d_moments`` as the 2D tests run them: ``first`` = convolution index of every distinct unordered
-    pair (first appearance wins, self pairs skipped; main.py:467-482), ``members[k]`` = all convolution indices that share
-    pair k's result, ``c1`` / ``c2`` = its column slots, ``true_corr`` [pair][group], ``skip`` (hypothesis_test.py:325) and the
-    chunk ``bounds``: pairs are independent, so they run in chunks of at most ``max_rows`` replicate rows
-    ([pair x group][B+1] fp64) AND at most a third of the free HBM in histogram tables."""
-    groups = m['groups']
-    ng = len(groups)
-    idx1, idx2 = m['2d_moments']['gene_idx_1'], m['2d_moments']['gene_idx_2']
-    first, members, seen = [], [], {}
-    for c in range(idx1.shape[0]):
-        a, b = int(idx1[c]), int(idx2[c])
-        if a == b:
-            continue
-        k = seen.setdefault(frozenset((a, b)), len(first))
-        if k == len(first):
-            first.append(c)
-            members.append([])
-        members[k].append(c)
-    first = np.asarray(first, dtype=np.int64)
-    P_ = len(first)
-    slot = {int(g): i for i, g in enumerate(st.cols_local)}
-    c1 = np.array([slot[int(idx1[c])] for c in first], dtype=np.int64)
-    c2 = np.array([slot[int(idx2[c])] for c in first], dtype=np.int64)
-    true_corr = np.stack([m['2d_moments'][g]['corr'][first] for g in groups], axis=1) if P_ else np.zeros((0, ng))   # [pair][group]
-    with np.errstate(invalid="ignore"):
-        skip = np.isnan(true_corr) | (np.abs(true_corr) == 1)
-    if max_rows is None:
-        max_rows = min(1 << 19, engine.auto_max_rows(num_boot + 1, arrays=1))   # also bounds the per-pair 2D tables
-    chunk = max(1, int(max_rows) // max(1, ng))
-    tab_bytes = engine.pair_table_bytes(st.maxx, st.cols.genes, c1, c2, ng, len(st.sf_table)) if P_ else np.zeros(0, dtype=np.int64)
-    budget = max(1 << 28, engine._torch().cuda.mem_get_info()[0] // 3)
-    bounds, acc = [0], 0
-    for k in range(P_):
-        if k - bounds[-1] >= chunk or (acc + int(tab_bytes[k]) > budget and k > bounds[-1]):
-            bounds.append(k)
-            acc = 0
-        acc += int(tab_bytes[k])
-    bounds.append(P_)
-    return first, members, c1, c2, true_corr, skip, bounds
+def _replay_pair_draws(c, plan, uniforms, trt, tcol, per_gene, num_boot):
+    """``ht_2d_moments(strict=True, resample_rep=True)``: the global-stream order of the reference for the pairs of chunk ``c``
+    (_ht_2d :319-343, _regress_2d :395-398): per pair three uniforms per live group (into ``uniforms``), then -- unless the
+    treatment of the good groups is all ones -- the two np.random.choice draws.  -> (rep_assign, bcol_assign), device pair order."""
+    r1a, r1b, r0 = uniforms
+    lo, n_ch, ng = c.lo, c.n_ch, plan.ng
+    inv = np.empty(n_ch, dtype=np.int64)
+    inv[c.so] = np.arange(n_ch)
+    K_orig = c.bs.K.reshape(n_ch, ng)[inv]                                # bins per (pair, group), original pair order
+    rep_assign = np.zeros((n_ch, ng, num_boot), dtype=np.int16)          # device pair order
+    bcol_assign = np.zeros((n_ch, ng, num_boot), dtype=np.int32)
+    for pi in range(n_ch):
+        lv = ~plan.skip[lo + pi]
+        idx = (lo + pi) * ng + np.flatnonzero(lv)
+        uu = np.random.random(3 * len(idx))
+        r1a[idx], r1b[idx], r0[idx] = uu[0::3], uu[1::3], uu[2::3]
+        gd = lv & (K_orig[pi] >= 1)
+        n = int(gd.sum())
+        t_pi = trt[:, [tcol[lo + pi]]] if per_gene else trt
+        if n and not (t_pi[gd] == 1).mean() == 1:
+            ra = np.random.choice(n, size=(n, num_boot))
+            ra[:, 0] = np.arange(n)
+            ba = np.random.choice(num_boot, (n, num_boot)) + 1
+            ba[:, 0] = 0
+            rep_assign[inv[pi], :n], bcol_assign[inv[pi], :n] = ra, ba
+    return rep_assign, bcol_assign
 
 
 def ht_2d_moments(adata, covariate, treatment, treatment_for_gene=None, inplace=True, num_boot=10000, verbose=3, num_cpus=1,
@@ -995,131 +779,53 @@ def ht_2d_moments(adata, covariate, treatment, treatment_for_gene=None, inplace=
     ``treatment_for_gene`` as the reference BEHAVES (main.py:492): a pair's treatment columns are looked up under
     ``frozenset({name of the pair's first gene})`` -- the key is built from idx_1 twice -- and one number per pair is stored,
     so the list must hold exactly one column (the reference raises ValueError on more); pinned by fixture ``api_tfg2d``."""
-    if rng not in ('replay', 'fast'):
-        raise ValueError("rng must be 'replay' or 'fast'")
-    if strict and rng != 'replay':
-        raise ValueError("strict=True needs rng='replay'")
-    if 'resampling' not in kwargs:
-        raise TypeError("_compute_asl() missing 1 required positional argument: 'resampling'")
-    resampling = kwargs['resampling']
-    resample_rep = bool(kwargs.get('resample_rep', False))
-    approx = bool(kwargs.get('approx', False))
+    resampling, resample_rep, approx = _ht.check_args(rng, strict, **kwargs)
     if not inplace:
         adata = adata.copy()
     m = adata.uns['memento']
     st = m['_hip']
     st.last_bootstrap2d = None                 # (free the previous call's replicate rows before this call allocates its own)
-    groups = m['groups']
-    ng = len(groups)
-    Nc_list = np.array([m['group_cells'][g].shape[0] for g in groups], dtype=np.float64)
+    Nc_list = np.array([m['group_cells'][g].shape[0] for g in m['groups']], dtype=np.float64)
     cov = np.asarray(covariate.values, dtype=np.float64)
     trt = np.asarray(treatment.values, dtype=np.float64)
-    gq = np.array([m['group_q'][g] for g in groups])
-    idx1, idx2 = m['2d_moments']['gene_idx_1'], m['2d_moments']['gene_idx_2']
-    n_conv = idx1.shape[0]
-    first, members, c1, c2, true_corr, skip, bounds = _pair_plan(m, st, num_boot, max_rows)
-    P_ = len(first)
-    chain_key = np.arange(P_ * ng, dtype=np.int64)        # rng='fast': stream key of (pair k, group) = k * n_groups + group
-    tcol = np.zeros(P_, dtype=np.int64)                   # treatment column of every tested pair (column 0 without treatment_for_gene)
-    if treatment_for_gene is not None:
+    plan = _ht.pair_plan(m, st, num_boot, max_rows)
+    tcol = np.zeros(plan.P_, dtype=np.int64)              # treatment column of every tested pair (column 0 without treatment_for_gene)
+    per_gene = treatment_for_gene is not None
+    if per_gene:
         names2, trt_cols = np.asarray(adata.var.index), list(treatment.columns)
-        for k, c in enumerate(first):
-            cols = treatment_for_gene[frozenset({names2[int(idx1[c])]})]
+        for k, c in enumerate(plan.first):
+            cols = treatment_for_gene[frozenset({names2[int(plan.idx1[c])]})]
             if len(cols) != 1:
                 raise ValueError("setting an array element with a sequence.")          # what main.py:507 does with more columns
             tcol[k] = trt_cols.index(cols[0])
-    live = ~skip.reshape(-1)
-    r1a, r1b, r0 = (np.zeros(P_ * ng) for _ in range(3))
     replay_rr = resample_rep and strict                   # the choice draws interleave with the hash uniforms, pair by pair
-    if not replay_rr:
-        u = np.random.random(3 * int(live.sum()))        # r = random(2) then r0 = random() per live (pair, group), in order
-        r1a[live], r1b[live], r0[live] = u[0::3], u[1::3], u[2::3]
-    corr_coef, corr_se, corr_asl = (np.full(n_conv, np.nan) for _ in range(3))
-    bs = None
-    for lo, hi in zip(bounds[:-1], bounds[1:]):
-        if hi <= lo:
-            continue
-        n_ch = hi - lo
-        bs = engine.Bootstrap2D(st.cols, c1[lo:hi], c2[lo:hi], st.maxx, st.sf_bin, st.sf_table, gq, num_boot)
-        so = bs.order                                     # device pair order (sorted by left column)
-        sl = slice(lo * ng, hi * ng)
+    uniforms = np.zeros((3, plan.P_ * plan.ng)) if replay_rr else _ht.hash_uniforms(~plan.skip.reshape(-1), 3)
+    corr_coef, corr_se, corr_asl = (np.full(plan.n_conv, np.nan) for _ in range(3))
+
+    def run_chunk(c):
+        bs = c.bs
         rep_assign = bcol_assign = None
         if replay_rr:
-            # global-stream order of the reference for one pair (_ht_2d :319-343, _regress_2d :395-398): three uniforms per
-            # live group, then -- unless the treatment of the good groups is all ones -- the two np.random.choice draws
-            inv = np.empty(n_ch, dtype=np.int64)
-            inv[so] = np.arange(n_ch)
-            K_orig = bs.K.reshape(n_ch, ng)[inv]                                  # bins per (pair, group), original pair order
-            rep_assign = np.zeros((n_ch, ng, num_boot), dtype=np.int16)          # device pair order
-            bcol_assign = np.zeros((n_ch, ng, num_boot), dtype=np.int32)
-            for pi in range(n_ch):
-                lv = ~skip[lo + pi]
-                idx = (lo + pi) * ng + np.flatnonzero(lv)
-                uu = np.random.random(3 * len(idx))
-                r1a[idx], r1b[idx], r0[idx] = uu[0::3], uu[1::3], uu[2::3]
-                gd = lv & (K_orig[pi] >= 1)
-                n = int(gd.sum())
-                t_pi = trt if treatment_for_gene is None else trt[:, [tcol[lo + pi]]]
-                if n and not (t_pi[gd] == 1).mean() == 1:
-                    ra = np.random.choice(n, size=(n, num_boot))
-                    ra[:, 0] = np.arange(n)
-                    ba = np.random.choice(num_boot, (n, num_boot)) + 1
-                    ba[:, 0] = 0
-                    rep_assign[inv[pi], :n], bcol_assign[inv[pi], :n] = ra, ba
-
-        def to_dev_order(a):
-            return a[sl].reshape(n_ch, ng)[so].reshape(-1)
-
-        bs.run(to_dev_order(skip.reshape(-1)), to_dev_order(r1a), to_dev_order(r1b), to_dev_order(r0),
-               to_dev_order(np.where(skip, np.nan, true_corr).reshape(-1)), fast=(rng == 'fast'), fast_seed=fill_seed,
-               pair_key=to_dev_order(chain_key))
-        good = bs.active.reshape(n_ch, ng)                # device order
-        cache, rows = {}, []
-        tc = tcol[lo:hi][so]                               # device order
-        for k in range(n_ch):
-            key = (good[k].tobytes(), int(tc[k]))
-            W = cache.get(key)
-            if W is None:
-                W = cache[key] = _design.weight_rows(cov, trt[:, [tc[k]]], Nc_list, good[k])[:1]
-            rows.append(W)
-        Wmat = np.concatenate(rows, axis=0) if rows else np.zeros((0, ng))
-        coef, stt = bs.contract(np.arange(n_ch), Wmat, good)
-        if resample_rep and n_ch:
-            # residual maker / residualised treatment per valid-group mask; an all-ones treatment keeps the weighted-average
-            # branch (hypothesis_test.py:384-386) and is not resampled
-            masks, pair_mask, tt_rows, rr_test, Ms = {}, np.zeros(n_ch, dtype=np.int32), [], np.zeros(n_ch, dtype=bool), []
-            for k in range(n_ch):
-                key = (good[k].tobytes(), int(tc[k]))
-                if key not in masks:
-                    t_k = trt if treatment_for_gene is None else trt[:, [tc[k]]]
-                    Mg, ttg = _design.residual_parts(cov, t_k, Nc_list, good[k])
-                    masks[key] = (len(Ms), ttg[:1], bool(good[k].any() and (t_k[good[k]] == 1).mean() == 1))
-                    Ms.append(Mg)
-                pair_mask[k], ttg, allones = masks[key]
-                tt_rows.append(ttg)
-                rr_test[k] = good[k].any() and not allones
-            if rr_test.any():
-                col_map, n_valid = bs.valid_cols(good)                            # hypothesis_test.py:372-373
-                if (n_valid[good.any(axis=1)] == num_boot + 1).all():
-                    col_map = n_valid = None
-                elif replay_rr:
-                    raise NotImplementedError("strict replay of resample_rep with non-finite correlation replicates")
-                coef_r, stt_r = bs.contract_resampled(np.arange(n_ch), np.concatenate(tt_rows, axis=0), good, pair_mask, np.stack(Ms),
-                                                      Nc_list, rep=rep_assign, bcol=bcol_assign, seed=fill_seed + 17 + lo,
-                                                      col_map=col_map, n_valid=n_valid)
-                stt = np.where(rr_test[:, None], stt_r, stt)
-                rr_idx = engine.dev(np.flatnonzero(rr_test))
-                coef[rr_idx] = coef_r[rr_idx]
+            rep_assign, bcol_assign = _replay_pair_draws(c, plan, uniforms, trt, tcol, per_gene, num_boot)
+        good = _ht.run_chunk_2d(c, plan, uniforms, rng, fill_seed)                 # device order
+        d = _ht.pair_design_tables(good, tcol[c.lo:c.hi][c.so], per_gene, cov, trt, Nc_list, resampled=resample_rep)
+        coef, stt = bs.contract(d.test_row, d.Wmat, good)
+        if resample_rep and d.rr_test.any():
+            col_map, n_valid = _ht.surviving_cols(bs, good, num_boot)             # hypothesis_test.py:372-373
+            if n_valid is not None and replay_rr:
+                raise NotImplementedError("strict replay of resample_rep with non-finite correlation replicates")
+            coef_r, stt_r = bs.contract_resampled(d.test_row, d.tt_mat, good, d.row_mask, d.Mstack, Nc_list, rep=rep_assign,
+                                                  bcol=bcol_assign, seed=fill_seed + 17 + c.lo, col_map=col_map, n_valid=n_valid)
+            coef, stt = _ht.merge_resampled(coef, stt, coef_r, stt_r, d.rr_test)
         pvals = _asl.asl_from_stats(stt, approx, lambda idx: engine.host(coef[engine.dev(np.asarray(idx, dtype=np.int64))]), num_cpus, resampling)
-        for k in range(n_ch):
-            if good[k].any():
-                cc = members[lo + so[k]]
-                corr_coef[cc], corr_se[cc], corr_asl[cc] = stt[k, 0], stt[k, 1], pvals[k]
+        for dst, src in ((corr_coef, stt[:, 0]), (corr_se, stt[:, 1]), (corr_asl, pvals)):
+            _ht.scatter_pairs(c, plan, dst, src, keep=good.any(axis=1))
+
+    for c in _ht.chunks_2d(st, plan, num_boot):
+        run_chunk(c)
     m['2d_ht'] = {'treatment': treatment, 'covariate': covariate, 'corr_coef': corr_coef, 'corr_se': corr_se, 'corr_asl': corr_asl}
     if treatment_for_gene is not None:
         m['2d_ht']['treatment_for_gene'] = treatment_for_gene                      # main.py:513-514
-    st.last_bootstrap2d = bs
-    st.last_chunk2d = (bounds[-2], bounds[-1]) if P_ else (0, 0)                   # diagnostics / tests: pair range of the last chunk
     if not inplace:
         return adata
 
@@ -1146,13 +852,10 @@ def ht_2d_vs_control(adata, control, num_boot=10000, num_cpus=1, fill_seed=0, ma
 
     Returns a DataFrame (gene_1, gene_2, group, corr_coef, corr_se, corr_pval), pair-major, one row per (requested pair,
     tested guide), and stores the arrays in ``uns['memento']['2d_ht_vs_control']``."""
-    if rng not in ('replay', 'fast'):
-        raise ValueError("rng must be 'replay' or 'fast'")
+    _ht.check_args(rng, resampling=resampling)
     m = adata.uns['memento']
     st = m['_hip']
     st.last_bootstrap2d = None                 # (free the previous call's replicate rows before this call allocates its own)
-    groups = m['groups']
-    ng = len(groups)
     tested, designs, (ctrl, others), meta = _vs_control_plan(m, control, treatment_col)
     if designs is None:
         # design k = {(guide k, +1), (control, -1)}; the last design is empty (a guide or the control is not good -> NaN test)
@@ -1160,50 +863,28 @@ def ht_2d_vs_control(adata, control, num_boot=10000, num_cpus=1, fill_seed=0, ma
         plain_grp = np.column_stack([others, np.full(len(others), ctrl)]).reshape(-1).astype(np.int32)
         plain_w = np.tile([1.0, -1.0], len(others))
     n_t = len(tested)
-    gq = np.array([m['group_q'][g] for g in groups])
-    idx1, idx2 = m['2d_moments']['gene_idx_1'], m['2d_moments']['gene_idx_2']
-    n_conv = idx1.shape[0]
-    first, members, c1, c2, true_corr, skip, bounds = _pair_plan(m, st, num_boot, max_rows)
-    P_ = len(first)
-    chain_key = np.arange(P_ * ng, dtype=np.int64)        # rng='fast': stream key of (pair k, group) = k * n_groups + group
-    live = ~skip.reshape(-1)
-    r1a, r1b, r0 = (np.zeros(P_ * ng) for _ in range(3))
-    u = np.random.random(3 * int(live.sum()))            # r = random(2) then r0 = random() per live (pair, group), in order
-    r1a[live], r1b[live], r0[live] = u[0::3], u[1::3], u[2::3]
-    out = {k: np.full((n_conv, n_t), np.nan) for k in ('corr_coef', 'corr_se', 'corr_asl')}
-    bs = None
-    for lo, hi in zip(bounds[:-1], bounds[1:]):
-        if hi <= lo:
-            continue
-        n_ch = hi - lo
-        del bs                   # release the previous chunk's tables and replicate rows first: the caching allocator hands them back
-        bs = engine.Bootstrap2D(st.cols, c1[lo:hi], c2[lo:hi], st.maxx, st.sf_bin, st.sf_table, gq, num_boot)
-        so = bs.order                                     # device pair order (sorted by left column)
-        sl = slice(lo * ng, hi * ng)
+    plan = _ht.pair_plan(m, st, num_boot, max_rows)
+    uniforms = _ht.hash_uniforms(~plan.skip.reshape(-1), 3)
+    out = {k: np.full((plan.n_conv, n_t), np.nan) for k in ('corr_coef', 'corr_se', 'corr_asl')}
 
-        def to_dev_order(a):
-            return a[sl].reshape(n_ch, ng)[so].reshape(-1)
-
-        bs.run(to_dev_order(skip.reshape(-1)), to_dev_order(r1a), to_dev_order(r1b), to_dev_order(r0),
-               to_dev_order(np.where(skip, np.nan, true_corr).reshape(-1)), fast=(rng == 'fast'), fast_seed=fill_seed,
-               pair_key=to_dev_order(chain_key))
-        good = bs.active.reshape(n_ch, ng)                # device order
-        test_pair = np.repeat(np.arange(n_ch), n_t)       # pair-major: a pair's control rows stay in L2 for its consecutive guides
+    def run_chunk(c):
+        good = _ht.run_chunk_2d(c, plan, uniforms, rng, fill_seed)                 # device order
+        test_pair = np.repeat(np.arange(c.n_ch), n_t)     # pair-major: a pair's control rows stay in L2 for its consecutive guides
         if designs is None:
             both = good[:, others] & good[:, [ctrl]]
             test_design = np.where(both, np.arange(n_t)[None, :], n_t).reshape(-1)
-            stt, rows = bs.contrast_design(test_pair, test_design, plain_ptr, plain_grp, plain_w)
+            stt, rows = c.bs.contrast_design(test_pair, test_design, plain_ptr, plain_grp, plain_w)
         else:
-            stt, rows = bs.contrast_design(test_pair, designs.tests(good), *designs.tables())
+            stt, rows = c.bs.contrast_design(test_pair, designs.tests(good), *designs.tables())
         pvals = _asl.asl_from_stats(stt, approx, rows, num_cpus, resampling)
-        for k in range(n_ch):
-            cc = members[lo + so[k]]
-            tt = slice(k * n_t, (k + 1) * n_t)
-            out['corr_coef'][cc], out['corr_se'][cc], out['corr_asl'][cc] = stt[tt, 0], stt[tt, 1], pvals[tt]
+        for key, src in (('corr_coef', stt[:, 0]), ('corr_se', stt[:, 1]), ('corr_asl', pvals)):
+            _ht.scatter_pairs(c, plan, out[key], src)
+
+    for c in _ht.chunks_2d(st, plan, num_boot):
+        run_chunk(c)
     out = {k: v.reshape(-1) for k, v in out.items()}
-    st.last_bootstrap2d = bs
-    st.last_chunk2d = (bounds[-2], bounds[-1]) if P_ else (0, 0)                   # diagnostics / tests: pair range of the last chunk
     m['2d_ht_vs_control'] = dict(out, **meta)
+    n_conv = plan.n_conv
     pairs = list(m['2d_moments']['gene_pairs'])
     df = pd.DataFrame({'gene_1': np.repeat([a for a, _ in pairs], n_t), 'gene_2': np.repeat([b for _, b in pairs], n_t),
                        'group': np.tile(tested, n_conv)})
