@@ -310,7 +310,7 @@ int mm_hist1d_sell(const uint32_t *d_ent, const int64_t *d_blk_base, const int32
                    const uint8_t *d_sf_bin, int32_t n_blocks, int32_t n_genes, const int32_t *d_gene_pairbase,
                    const int64_t *d_tab_ptr, const int32_t *d_xcap, uint32_t *d_tab, void *stream) {
   MM_ARG(d_ent && d_blk_base && d_slice_w && d_slice_ptr && d_item_ptr && d_perm && d_blk_cell0 && d_blk_group && d_sf_bin);
-  MM_ARG(d_gene_pairbase && d_tab_ptr && d_xcap && d_tab && n_blocks >= 0 && n_genes > 0);
+  MM_ARG(d_gene_pairbase && d_tab_ptr && d_xcap && d_tab && n_blocks >= 0 && n_genes > 0 && n_genes <= 65536);  // ip[]: 1024 slices
   if (n_blocks == 0) return MM_OK;
   int32_t n_slices = (n_genes + 63) / 64;
   int split = (4096 + n_blocks - 1) / n_blocks;
@@ -340,7 +340,7 @@ int mm_bins_order(const uint32_t *d_tab, const int64_t *d_tab_ptr, const int32_t
                   const int64_t *d_tile_ptr, const double *d_grp_ncells, double *d_pk, double *d_lq, double *d_v,
                   double *d_a, double *d_b, int32_t *d_status, void *stream) {
   MM_ARG(d_tab && d_tab_ptr && d_xcap && d_K && d_pair_list && d_sf_table && d_r1 && d_r0 && d_pair_slot && d_tile_ptr);
-  MM_ARG(d_grp_ncells && d_pk && d_lq && d_v && d_a && d_b && d_status && n_list >= 0 && n_sf_bins <= 256);
+  MM_ARG(d_grp_ncells && d_pk && d_lq && d_v && d_a && d_b && d_status && n_list >= 0 && n_groups > 0 && n_sf_bins > 0 && n_sf_bins <= 256);
   if (n_list == 0) return MM_OK;
   return launch_bins_order<8192>(big, n_list, stream, Bins1D{d_xcap, d_r1, {d_v}}, d_tab, d_tab_ptr, d_K, d_pair_list, n_list, n_groups,
                                  n_sf_bins, d_sf_table, d_r0, d_pair_slot, d_tile_ptr, d_grp_ncells, d_pk, d_lq, d_a, d_b, d_status);
@@ -352,7 +352,8 @@ int mm_bins_order2d(const uint32_t *d_tab, const int64_t *d_tab_ptr, const int32
                     const int64_t *d_pair_slot, const int64_t *d_tile_ptr, const double *d_grp_ncells, double *d_pk, double *d_lq,
                     double *d_v1, double *d_v2, double *d_a, double *d_b, int32_t *d_status, void *stream) {
   MM_ARG(d_tab && d_tab_ptr && d_xcap_i && d_xcap_j && d_K && d_pair_list && d_sf_table && d_r1a && d_r1b && d_r0 && d_pair_slot);
-  MM_ARG(d_tile_ptr && d_grp_ncells && d_pk && d_lq && d_v1 && d_v2 && d_a && d_b && d_status && n_list >= 0 && n_sf_bins <= 256);
+  MM_ARG(d_tile_ptr && d_grp_ncells && d_pk && d_lq && d_v1 && d_v2 && d_a && d_b && d_status && n_list >= 0 && n_groups > 0);
+  MM_ARG(n_sf_bins > 0 && n_sf_bins <= 256);
   if (n_list == 0) return MM_OK;
   // 20 B per bin: 80 KiB of LDS in the big instantiation
   return launch_bins_order<4096>(big, n_list, stream, Bins2D{d_xcap_i, d_xcap_j, d_r1a, d_r1b, {d_v1, d_v2}}, d_tab, d_tab_ptr, d_K,
