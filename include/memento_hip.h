@@ -88,7 +88,16 @@ int mm_csr_colsum(const int32_t *d_indices, const float *d_data, int64_t nnz, do
  * d_cell_order[n_sel]: original cell index of every selected cell, sorted by group;
  * d_blk_cell0[n_blocks+1]: block b covers cell_order[blk_cell0[b] .. blk_cell0[b+1]) (one group each).
  * Step 1 counts nnz per (block, gene) and validates the data (integer valued, 0 < x <= MM_MAX_COUNT;
- * d_status[0] != 0 afterwards means invalid data).  */
+ * d_status[0] != 0 afterwards means invalid data).
+ * Width: one set of count blocks holds n_genes <= 60000 (mm_sell_layout's per-block rank table in LDS; the K0 / K1 / K5 / K11
+ * kernels that index slices stop at 65536).  A caller with more genes PARTITIONS THE COLUMNS, as the Python engine does
+ * (engine.count_blocks): cut the gene axis into contiguous ranges of <= 60000 (the engine takes 59392 = 58 ranges of 1024), take
+ * each range out of the CSR with mm_csr_colcount + mm_csr_colsplit, ingest it into count blocks of its own on the SAME cell
+ * plan (d_cell_order / d_blk_cell0 depend only on the grouping), and launch the kernels that read count blocks once per range:
+ * mm_moments1d_sell / _reduce write that range's slice of the per-gene outputs; mm_hist1d_sell and mm_extract_cols take that
+ * range's slice of d_gene_pairbase / d_col_id and write into the ONE set of tables / columns, which are indexed by pair / column
+ * slot, not by gene.  mm_csr_colsplit drops entries whose column lies in no range: compare the ranges' entry counts with
+ * d_indptr to keep the column-index validation.  */
 int mm_sell_count(const int64_t *d_indptr, const int32_t *d_indices, const float *d_data, const int32_t *d_cell_order,
                   const int32_t *d_blk_cell0, int32_t n_blocks, int32_t n_genes, uint16_t *d_blk_cnt /* [nb][G] */,
                   int32_t *d_status, void *stream);
@@ -107,7 +116,7 @@ int mm_sell_scatter(const int64_t *d_indptr, const int32_t *d_indices, const flo
                     const int32_t *d_slice_ptr, const int64_t *d_blk_base, uint32_t *d_ent, void *stream);
 /* Range-partitioned form of steps 1 and 3 for rows with strictly ascending column indices (canonical CSR): the path the
  * Python driver takes; mm_sell_count / mm_sell_scatter above remain for unsorted rows.  The gene ids are cut into
- * n_ranges = ceil(G / MM_RANGE_GENES) ranges of MM_RANGE_GENES = 1024 consecutive ids (G <= 65536).
+ * n_ranges = ceil(G / MM_RANGE_GENES) ranges of MM_RANGE_GENES = 1024 consecutive ids (G <= 65536 per ingest; more genes: see above).
  * mm_sell_split_count, one pass over the column indices: d_rowsplit[k][r], k = 0..R = absolute position in d_indices / d_data at
  * which range k begins in selected row r (block order, n_sel rows; range-major so that a (block, range) workgroup reads contiguous
  * runs); d_status |= 2 if some row is not strictly ascending or has a column outside [0, G); and d_blk_cnt as mm_sell_count fills

@@ -18,6 +18,8 @@ from . import _lib
 BLOCK_CELLS = 8192
 MAX_COUNT = (1 << 19) - 1
 RANGE_GENES, MAX_RANGES = 1024, 64   # include/memento_hip.h: MM_RANGE_GENES, MM_MAX_RANGES (range-partitioned ingest)
+MAX_PART_GENES = 60_000              # genes ONE CountBlocks holds (mm_sell_layout's rank table; the other K0 / K1 / K5 kernels stop at 65,536)
+PART_GENES = 59_392                  # genes per part of a wider matrix (count_blocks): 58 ranges of 1024, a multiple of 64
 ORDER_SMALL_CAP = 1024
 ORDER_BIG_CAP = 8192
 ORDER_BIG_CAP_2D = 4096
@@ -233,12 +235,30 @@ def plan_blocks(group_id, n_groups, block_cells=BLOCK_CELLS):
             np.asarray(grp_blk0, dtype=np.int32), counts)
 
 
+def plan_parts(G, part_genes=PART_GENES):
+    """Gene ranges [(lo, hi), ...] of the count-block parts of a G-gene matrix: ascending, contiguous, covering [0, G), each at most
+    ``part_genes`` wide (every part but the last exactly that).  One part iff G <= part_genes."""
+    G, part_genes = int(G), int(part_genes)
+    if not 0 < part_genes <= MAX_PART_GENES:
+        raise ValueError(f"part_genes must be in 1..{MAX_PART_GENES}")
+    if G < 0:
+        raise ValueError("G must not be negative")
+    return [(lo, min(G, lo + part_genes)) for lo in range(0, max(1, G), part_genes)]
+
+
+_BAD_COUNTS = f"count matrix must hold positive integer counts <= {MAX_COUNT} with valid column indices"
+
+
 class CountBlocks:
-    """K0 result: the group-ordered SELL-64x4 count blocks living in HBM (see include/memento_hip.h)."""
+    """K0 result: the group-ordered SELL-64x4 count blocks living in HBM (see include/memento_hip.h).  One object holds at most
+    MAX_PART_GENES genes (LDS budgets of the K0 / K1 / K5 kernels); ``count_blocks`` builds wider matrices from several."""
 
     def __init__(self, csr, group_id, n_groups, timing=None):
         """``timing``: an optional dict that receives the HIP-event time (ms) of each of the three K0 launches
         (bench.py's CSR -> moments roofline; the launches are otherwise untimed)."""
+        if int(csr.shape[1]) > MAX_PART_GENES:
+            raise ValueError(f"one CountBlocks holds at most {MAX_PART_GENES} genes, got {int(csr.shape[1])}: "
+                             "build the blocks of a wider matrix with engine.count_blocks")
         torch = _torch()
         call = _lib.call if timing is None else (lambda name, *a: _timed_call(timing, name, *a))
         self.G = int(csr.shape[1])
@@ -256,14 +276,12 @@ class CountBlocks:
         blk_cnt_buf = zeros((nb * G + 2,), torch.int16)     # (the fused split + count merges 16-bit halves by 32-bit atomics)
         blk_cnt = blk_cnt_buf[:nb * G].view(nb, G)
         status = zeros((1,), torch.int32)
-        bad_data = ValueError(f"count matrix must hold positive integer counts <= {MAX_COUNT} with valid column indices")
+        bad_data = ValueError(_BAD_COUNTS)
         # Range-partitioned ingest (rows with ascending column indices: every canonical CSR): a workgroup owns (block, range of
         # 1024 consecutive gene ids), so a row contributes one contiguous segment to it and the per-gene state of the range lives
         # in LDS (csrc/ingest.hip).
         n_sel = len(self.cell_order)
-        R = -(-G // RANGE_GENES)
-        if R > MAX_RANGES:
-            raise ValueError(f"at most {MAX_RANGES * RANGE_GENES} genes per ingest")
+        R = -(-G // RANGE_GENES)          # (<= MAX_RANGES: G <= MAX_PART_GENES)
         rowsplit = empty((R + 1, max(1, n_sel)), torch.int64)     # [range][row]
         call("mm_sell_split_count", P(csr.indptr), P(csr.indices), P(self.d_cell_order), P(self.d_blk_cell0), nb, n_sel, G, R,
              P(rowsplit), P(blk_cnt_buf), P(status), s)
@@ -308,6 +326,14 @@ class CountBlocks:
         n = max(1, self.total_items) * 64
         self._slab = empty((n * 8,), torch.int32)          # 32-byte record per (item, lane): S1, S2, S3 (fp64), sum x, max x
 
+    part_lo = (0,)
+
+    @property
+    def parts(self):
+        """The gene parts the consumers loop over: this object, from gene 0 (a WideCountBlocks has several).  A property: stored on
+        the object it would be a reference cycle, and the device buffers would wait for the cycle collector."""
+        return (self,)
+
     @property
     def ent_bytes(self):
         return self.total_rows * 1024
@@ -338,17 +364,70 @@ class CountBlocks:
         return host(out_S), host(out_sx, np.uint64), host(out_mx, np.uint32)
 
 
-def _timed_call(timing, name, *args):
-    """_lib.call bracketed by HIP events on the launch stream (last argument); elapsed ms -> timing[name]."""
+class WideCountBlocks:
+    """Count blocks of a matrix with more genes than one CountBlocks holds: one CountBlocks per gene range of ``plan_parts``, all on
+    the same cell plan (plan_blocks depends only on the grouping).  Offers what the consumers of count blocks read -- the common cell
+    plan, ``blk_cnt`` / ``moments`` over the whole gene axis, and ``parts`` / ``part_lo`` for the kernels that read the entries:
+    Bootstrap1D and GeneColumns launch once per part with that part's slice of their gene -> output map, into the one output."""
+
+    def __init__(self, parts, part_lo, G):
+        self.parts, self.part_lo, self.G = tuple(parts), tuple(int(lo) for lo in part_lo), int(G)
+        p0 = self.parts[0]
+        for name in ("n_groups", "n_blocks", "cell_order", "blk_cell0", "blk_group", "grp_blk0", "grp_ncells",
+                     "d_cell_order", "d_blk_cell0", "d_blk_group", "d_grp_blk0"):
+            setattr(self, name, getattr(p0, name))
+        self.blk_cnt = np.concatenate([p.blk_cnt for p in self.parts], axis=1)      # [nb][G]
+        self.nnz_sel = sum(p.nnz_sel for p in self.parts)
+        self.ranged = all(p.ranged for p in self.parts)
+
+    def moments(self, inv_sf_cells):
+        """K1+K2 of every part, concatenated along the gene axis: S (3, n_groups, G), sumx (n_groups, G), maxx (n_groups, G)."""
+        res = [p.moments(inv_sf_cells) for p in self.parts]
+        return tuple(np.concatenate([r[i] for r in res], axis=-1) for i in range(3))
+
+
+def count_blocks(csr, group_id, n_groups, timing=None, part_genes=None):
+    """The count blocks of ``csr`` whatever its width: a CountBlocks when the genes fit one part (the same object and launches as the
+    direct constructor), else a WideCountBlocks of one CountBlocks per gene range, each ingested from a column split of ``csr`` that
+    is released before the next is cut (extra memory: one part's indices + data).  ``timing`` also receives the HIP-event time of
+    the splits under 'colsplit'.  ``part_genes``: by default a matrix that fits one CountBlocks (<= MAX_PART_GENES genes) stays one part,
+    as it always was, and a wider one is cut into parts of PART_GENES; a value (<= MAX_PART_GENES) cuts parts of exactly that width --
+    it exists for tests that need several parts at small shapes."""
+    G = int(csr.shape[1])
+    ranges = plan_parts(G, part_genes if part_genes is not None else PART_GENES if G > MAX_PART_GENES else MAX_PART_GENES)
+    if len(ranges) == 1:
+        return CountBlocks(csr, group_id, n_groups, timing=timing)
+    parts = []
+    for lo, hi in ranges:
+        sub = csr.colsplit(lo, hi) if timing is None else _timed(timing, "colsplit", _stream(), lambda: csr.colsplit(lo, hi))
+        parts.append(CountBlocks(sub, group_id, n_groups, timing=timing))
+        del sub
+    wide = WideCountBlocks(parts, [lo for lo, _ in ranges], csr.shape[1])
+    # colsplit drops an entry whose column lies in no part, so an invalid column index never reaches a part's ingest check: every
+    # stored entry of the selected cells must have arrived in some part
+    indptr = host(csr.indptr)
+    if int((indptr[wide.cell_order.astype(np.int64) + 1] - indptr[wide.cell_order]).sum()) != wide.nnz_sel:
+        raise ValueError(_BAD_COUNTS)
+    return wide
+
+
+def _timed(timing, key, stream, fn):
+    """fn() bracketed by HIP events on ``stream``; elapsed ms is added to timing[key].  Returns fn's result."""
     t = c_void_p()
     ms = ctypes.c_float()
     _lib.call("mm_timer_create", ctypes.byref(t))
-    _lib.call("mm_timer_begin", t, args[-1])
-    _lib.call(name, *args)
-    _lib.call("mm_timer_end", t, args[-1])
+    _lib.call("mm_timer_begin", t, stream)
+    res = fn()
+    _lib.call("mm_timer_end", t, stream)
     _lib.call("mm_timer_elapsed_ms", t, ctypes.byref(ms))
     _lib.call("mm_timer_destroy", t)
-    timing[name] = timing.get(name, 0.0) + float(ms.value)
+    timing[key] = timing.get(key, 0.0) + float(ms.value)
+    return res
+
+
+def _timed_call(timing, name, *args):
+    """_lib.call bracketed by HIP events on the launch stream (last argument); elapsed ms -> timing[name]."""
+    _timed(timing, name, args[-1], lambda: _lib.call(name, *args))
 
 
 def _tiles_from_lanes(lanes, n_act):
@@ -690,9 +769,11 @@ class Bootstrap1D:
         self.d_xcap, self.d_tab_ptr = dev(xcap), dev(tab_ptr[:-1])
         self.tab = zeros((max(1, int(tab_ptr[-1])),), torch.int32)
         d_pairbase = dev(pairbase)  # NB: every device operand must stay referenced until after the call
-        _lib.call("mm_hist1d_sell", P(b.ent), P(b.blk_base), P(b.slice_w), P(b.slice_ptr), P(b.item_ptr), P(b.perm),
-                  P(b.d_blk_cell0), P(b.d_blk_group), P(d_bins), b.n_blocks, b.G, P(d_pairbase), P(self.d_tab_ptr),
-                  P(self.d_xcap), P(self.tab), s)
+        for p, lo in zip(b.parts, b.part_lo):      # one launch per gene part, each with its slice of the map, all into the one table
+            if (pairbase[lo:lo + p.G] >= 0).any():
+                _lib.call("mm_hist1d_sell", P(p.ent), P(p.blk_base), P(p.slice_w), P(p.slice_ptr), P(p.item_ptr), P(p.perm),
+                          P(p.d_blk_cell0), P(p.d_blk_group), P(d_bins), p.n_blocks, p.G, P(d_pairbase[lo:lo + p.G]), P(self.d_tab_ptr),
+                          P(self.d_xcap), P(self.tab), s)
         self.d_K = empty((self.n_pairs,), torch.int32)
         d_gbc = dev(self.grp_bin_cells)
         _lib.call("mm_bins_count", P(self.tab), P(self.d_tab_ptr), P(self.d_xcap), self.n_pairs, self.ng, self.n_bins,
@@ -1057,8 +1138,10 @@ class GeneColumns:
         col_id[self.genes] = np.arange(M, dtype=np.int32)
         d_col_id = dev(col_id)
         self.cols = zeros((max(1, total),), torch.int32)
-        _lib.call("mm_extract_cols", P(blocks.ent), P(blocks.blk_base), P(blocks.slice_w), P(blocks.slice_ptr), P(blocks.item_ptr),
-                  P(blocks.perm), nb, blocks.G, P(d_col_id), M, P(self.col_ptr), P(self.cols), _stream())
+        for p, lo in zip(blocks.parts, blocks.part_lo):      # one launch per gene part, each with its slice of the map, all into the one store
+            if M == 0 or (col_id[lo:lo + p.G] >= 0).any():       # (no column at all: the C-ABI refuses the launch)
+                _lib.call("mm_extract_cols", P(p.ent), P(p.blk_base), P(p.slice_w), P(p.slice_ptr), P(p.item_ptr),
+                          P(p.perm), nb, p.G, P(d_col_id[lo:lo + p.G]), M, P(self.col_ptr), P(self.cols), _stream())
         self.slot_of_gene = {int(g): i for i, g in enumerate(self.genes)}
 
 

@@ -185,7 +185,7 @@ def setup_memento(adata, q_column, inplace=True, filter_mean_thresh=0.07, trim_p
         assert size_factor.shape == (N,)
         adata.obs['memento_size_factor'] = size_factor
         m['least_variable_genes'] = []
-        blocks_all = engine.CountBlocks(st.csr, np.zeros(N, dtype=np.int32), 1)
+        blocks_all = engine.count_blocks(st.csr, np.zeros(N, dtype=np.int32), 1)
         S, _, _ = blocks_all.moments(1.0 / size_factor)
         m['all_1d_moments'] = list(_moments_from_sums(S[:, 0], N, m['all_q']))
         if estimator_type == 'mean_only':
@@ -194,7 +194,7 @@ def setup_memento(adata, q_column, inplace=True, filter_mean_thresh=0.07, trim_p
     naive = st.csr.rowsum()                                                   # estimator.py:64-69
     if comm is not None:
         naive = comm.allreduce_sum(naive)
-    blocks_all = engine.CountBlocks(st.csr, np.zeros(N, dtype=np.int32), 1)
+    blocks_all = engine.count_blocks(st.csr, np.zeros(N, dtype=np.int32), 1)
     with np.errstate(divide="ignore"):
         S, sumx, _ = blocks_all.moments(1.0 / naive)
     all_m, all_v = _moments_from_sums(S[:, 0], N, m['all_q'])                 # main.py:62-66
@@ -245,7 +245,7 @@ def create_groups(adata, label_columns, label_delimiter='^', inplace=True):
     m['q'] = adata.obs[m['q_column']].values
     st = m['_hip']
     st.group_id = codes.astype(np.int32)
-    st.blocks = engine.CountBlocks(st.csr, st.group_id, len(uniques))
+    st.blocks = engine.count_blocks(st.csr, st.group_id, len(uniques))
     G = adata.shape[1]
     m['group_cells'] = {g: _GroupCellsView(st.blocks.grp_ncells[i], G) for i, g in enumerate(m['groups'])}
     qsum = np.bincount(codes, weights=m['q'], minlength=len(uniques))

@@ -107,7 +107,7 @@ def extract_parameters(data, q=0.1, min_mean=0.001):
     csr = data if isinstance(data, engine.DeviceCSR) else engine.DeviceCSR(data)
     n = csr.shape[0]
     rowsum = csr.rowsum()
-    blocks = engine.CountBlocks(csr, np.zeros(n, dtype=np.int32), 1)
+    blocks = engine.count_blocks(csr, np.zeros(n, dtype=np.int32), 1)
     with np.errstate(divide="ignore"):
         S, sumx, _ = blocks.moments(1.0 / rowsum)
     x_mean = S[0, 0] / n
