@@ -392,6 +392,21 @@ int mm_contrast_design1_rows(const double *d_y, int64_t ld, int32_t num_boot, in
                              const int32_t *d_test_design, const int32_t *d_design_ptr, const int32_t *d_design_grp,
                              const double *d_design_w, int64_t n_tests, double *d_out, void *stream);
 
+/* ---- order statistics of replicate rows (percentile intervals of the coefficients) -------------------------------
+ * For every row of d_rows [n_rows][ld]: the replicate columns 1..num_boot (column 0, the observed value, and the padding
+ * from num_boot + 1 on are not read), NaNs dropped; d_n_valid[row] = n, the number of columns kept, and
+ *   d_out[row][k] = np.nanquantile(row[1 : num_boot + 1], probs[k])   (numpy's default method, 'linear'):
+ * with x_(0) <= ... <= x_(n-1) the kept values, h = probs[k] * (n - 1), a = x_(floor h), b = x_(min(floor h + 1, n - 1)) and
+ * t = h - floor h, the result is a + (b - a) * t for t < 0.5 and b - (b - a) * (1 - t) otherwise (numpy's _lerp, unfused);
+ * t == 0 or a == b gives a itself (the same number wherever the formula is finite; an order statistic that is +-inf comes
+ * out as +-inf, where the formula has inf - inf).  n == 0 gives NaN.  +-inf are ordinary values at the ends of the order;
+ * which of -0.0 and +0.0 comes out is not specified (numpy's sort does not order them either).
+ * probs: HOST array of n_probs values in [0, 1], 1 <= n_probs <= 8.  Needs num_boot >= 1 and ld >= num_boot + 1; n_rows == 0
+ * is a no-op.  The selection is an exact radix select on the row in place (8 reads of the row, nothing stored): ties and rows
+ * of any length are handled by the same path. */
+int mm_row_quantiles(const double *d_rows, int64_t n_rows, int64_t ld, int32_t num_boot, const double *probs, int32_t n_probs,
+                     double *d_out /* [n_rows][n_probs] */, int32_t *d_n_valid /* [n_rows] */, void *stream);
+
 /* ==== 2D (gene pairs) ===========================================================================
  * K11 step 1: copy the columns of the n_cols genes with d_col_id[gene] = m >= 0 out of the SELL blocks into a
  * gene-contiguous store: entries of (block b, column m) at d_out[col_ptr[b*(n_cols+1)+m] .. col_ptr[b*(n_cols+1)+m+1])

@@ -108,6 +108,7 @@ _SIGS = {
     "mm_std_normal": ([c_uint64, c_int64, c_void_p, c_void_p], ctypes.c_int),
     "mm_contract_stats": ([c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_int32,
                            c_void_p, c_void_p, c_void_p], ctypes.c_int),
+    "mm_row_quantiles": ([c_void_p, c_int64, c_int64, c_int32, ctypes.POINTER(c_double), c_int32, c_void_p, c_void_p, c_void_p], ctypes.c_int),
 }
 
 EXPORTS = ["mm_last_error"] + list(_SIGS)

@@ -527,7 +527,141 @@ __global__ __launch_bounds__(256) void k_contrast_design1_rows(const double *__r
   }
 }
 
+// ------------------------------------------------------------------------------------------------
+// Order statistics of a replicate row (percentile intervals of the coefficients): np.nanquantile(row[1 : B + 1], probs),
+// method 'linear', for up to RQ_MAX_PROBS probabilities per launch.  One workgroup per row.  Every double maps to a uint64 key
+// of the same order (negatives: all bits flipped; others: sign bit flipped) and the two order statistics of every probability
+// are found by an MSB-first radix select, 8 bits per pass: a pass builds one 256-bin LDS histogram per distinct key prefix
+// among the wanted ranks (ranks inside one run of equal keys share their prefix, and so their histogram, to the end) over the
+// keys that carry that prefix; a scan of the histogram gives the rank's next digit and its rank among the keys that share it.
+// The first pass has the empty prefix, so its histogram also counts the non-NaN columns.  The row is read from global memory
+// in every pass (8 reads of a row that stays in L2), so nothing depends on the row length: no LDS-resident variant.
+#define RQ_THREADS 256
+#define RQ_MAX_PROBS 8
+#define RQ_MAX_RANKS (2 * RQ_MAX_PROBS)
+struct rq_probs { double p[RQ_MAX_PROBS]; };
+
+__device__ __forceinline__ uint64_t rq_key(double x) {
+  uint64_t b = (uint64_t)__double_as_longlong(x);
+  return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
+__device__ __forceinline__ double rq_value(uint64_t k) {
+  return __longlong_as_double((long long)((k >> 63) ? (k & 0x7FFFFFFFFFFFFFFFull) : ~k));
+}
+
+__global__ __launch_bounds__(RQ_THREADS) void k_row_quantiles(const double *__restrict__ rows, int64_t ld, int32_t num_boot, rq_probs probs,
+                                                              int32_t n_probs, double *__restrict__ out, int32_t *__restrict__ n_valid) {
+  __shared__ uint32_t hist[RQ_MAX_RANKS][256];
+  __shared__ uint64_t pre[RQ_MAX_RANKS];      // per wanted rank: the key digits found so far
+  __shared__ uint32_t rnk[RQ_MAX_RANKS];      //                  its rank among the keys that share them
+  __shared__ int slot[RQ_MAX_RANKS];          //                  the histogram of its prefix
+  __shared__ uint64_t gpre[RQ_MAX_RANKS];     // per histogram: the prefix it counts
+  __shared__ int n_hist_s;
+  __shared__ uint32_t wave_n[RQ_THREADS / 64];
+  const int tid = threadIdx.x;
+  const int n_ranks = 2 * n_probs;
+  const double *x = rows + (int64_t)blockIdx.x * ld + 1;     // replicate columns 1..num_boot
+  int n_hist = 1;
+  uint32_t n = 0;
+  for (int pass = 0; pass < 8; pass++) {
+    const int shift = 56 - 8 * pass;
+    for (int i = tid; i < n_hist * 256; i += RQ_THREADS) (&hist[0][0])[i] = 0;
+    __syncthreads();
+    for (int c = tid; c < num_boot; c += RQ_THREADS) {
+      double v = x[c];
+      if (v != v) continue;
+      uint64_t k = rq_key(v);
+      uint32_t digit = (uint32_t)(k >> shift) & 255u;
+      if (pass == 0) {
+        atomicAdd(&hist[0][digit], 1u);
+      } else {
+        uint64_t hi = k >> (shift + 8);
+        for (int g = 0; g < n_hist; g++)
+          if (gpre[g] == hi) {      // the prefixes are distinct: at most one histogram takes the key
+            atomicAdd(&hist[g][digit], 1u);
+            break;
+          }
+      }
+    }
+    __syncthreads();
+    if (pass == 0) {
+      uint32_t cnt = hist[0][tid];
+      for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off, 64);
+      if ((tid & 63) == 0) wave_n[tid >> 6] = cnt;
+      __syncthreads();
+      n = wave_n[0] + wave_n[1] + wave_n[2] + wave_n[3];
+      if (n == 0) {
+        if (tid < n_probs) out[(int64_t)blockIdx.x * n_probs + tid] = NAN;
+        if (tid == 0) n_valid[blockIdx.x] = 0;
+        return;
+      }
+      if (tid < n_ranks) {
+        double h = (double)(n - 1) * probs.p[tid >> 1];
+        uint32_t lo = (uint32_t)floor(h);
+        lo = lo < n - 1 ? lo : n - 1;
+        uint32_t hi = lo + 1 < n - 1 ? lo + 1 : n - 1;
+        rnk[tid] = (tid & 1) ? hi : lo;
+        pre[tid] = 0;
+        slot[tid] = 0;
+      }
+      __syncthreads();
+    }
+    if (tid < n_ranks) {
+      const uint32_t *hg = hist[slot[tid]];
+      uint32_t r = rnk[tid], cum = 0, digit = 255;
+      for (uint32_t d = 0; d < 256; d++) {
+        uint32_t cnt = hg[d];
+        if (r < cum + cnt) { digit = d; break; }
+        cum += cnt;
+      }
+      rnk[tid] = r - cum;
+      pre[tid] = (pre[tid] << 8) | digit;
+    }
+    __syncthreads();
+    if (tid == 0) {      // one histogram per distinct prefix for the next pass
+      int nh = 0;
+      for (int j = 0; j < n_ranks; j++) {
+        int g = 0;
+        while (g < nh && gpre[g] != pre[j]) g++;
+        if (g == nh) gpre[nh++] = pre[j];
+        slot[j] = g;
+      }
+      n_hist_s = nh;
+    }
+    __syncthreads();
+    n_hist = n_hist_s;
+  }
+  if (tid < n_probs) {
+    // numpy's 'linear' method: virtual index h = (n - 1) p, weight t = h - floor(h), then _lerp(a, b, t).  t == 0 and a == b
+    // return a itself, which is _lerp's value wherever that is finite and keeps +-inf where _lerp has inf - inf.
+    double h = (double)(n - 1) * probs.p[tid];
+    double t = h - floor(h);
+    double a = rq_value(pre[2 * tid]), b = rq_value(pre[2 * tid + 1]);
+    double d = b - a, q;
+    if (t == 0.0 || a == b) q = a;
+    else if (t < 0.5) q = a + d * t;
+    else q = b - d * (1.0 - t);
+    out[(int64_t)blockIdx.x * n_probs + tid] = q;
+  }
+  if (tid == 0) n_valid[blockIdx.x] = (int32_t)n;
+}
+
 extern "C" {
+
+int mm_row_quantiles(const double *d_rows, int64_t n_rows, int64_t ld, int32_t num_boot, const double *probs, int32_t n_probs,
+                     double *d_out, int32_t *d_n_valid, void *stream) {
+  MM_ARG(n_rows >= 0 && n_rows < 2147483647LL && num_boot >= 1 && ld >= (int64_t)num_boot + 1);
+  MM_ARG(probs && n_probs >= 1 && n_probs <= RQ_MAX_PROBS);
+  rq_probs pr;
+  for (int k = 0; k < RQ_MAX_PROBS; k++) pr.p[k] = k < n_probs ? probs[k] : 0.0;
+  for (int k = 0; k < n_probs; k++) MM_ARG(pr.p[k] >= 0.0 && pr.p[k] <= 1.0);   // (NaN fails both comparisons)
+  if (n_rows == 0) return MM_OK;
+  MM_ARG(d_rows && d_out && d_n_valid);
+  hipLaunchKernelGGL(k_row_quantiles, dim3((unsigned)n_rows), dim3(RQ_THREADS), 0, (hipStream_t)stream, d_rows, ld, num_boot, pr, n_probs,
+                     d_out, d_n_valid);
+  MM_LAUNCH_CHECK();
+  return MM_OK;
+}
 
 int mm_contract_stats(const double *d_ym, const double *d_yv, int64_t ld, int32_t num_boot, int32_t n_groups,
                       const int32_t *d_test_gene, const double *d_W, const uint8_t *d_good, int64_t n_tests, int32_t which,

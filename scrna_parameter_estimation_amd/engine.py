@@ -999,7 +999,8 @@ class Bootstrap1D:
 
     def contrast(self, test_gene, test_grp, ctrl, good):
         """Two-group contrasts against the control group ``ctrl`` (mm_contrast_stats): returns (stats_mean, stats_var)
-        host arrays [n_tests][8]; ``rows(which, idx)`` gives the coefficient rows of selected tests on demand."""
+        host arrays [n_tests][8]; ``rows(which, idx)`` gives the coefficient rows of selected tests on demand: a host array, or
+        with ``to_host=False`` a device tensor [len(idx)][ld] (a view of the scratch tensor ``out`` when one is passed)."""
         torch = _torch()
         n_tests = len(test_gene)
         st_m = empty((max(1, n_tests), 8), torch.float64)
@@ -1009,13 +1010,13 @@ class Bootstrap1D:
         _lib.call("mm_contrast_stats", P(self.ym), P(self.yv), self.ld, self.B, self.ng, int(ctrl), P(d_tg), P(d_gr), P(d_good), n_tests,
                   P(st_m), P(st_v), _stream())
 
-        def rows(which, idx):
+        def rows(which, idx, to_host=True, out=None):
             idx = np.asarray(idx, dtype=np.int64)
-            out = empty((max(1, len(idx)), self.ld), torch.float64)
+            out = _rows_out(out, len(idx), self.ld)
             a, b = dev(np.asarray(test_gene, dtype=np.int32)[idx]), dev(np.asarray(test_grp, dtype=np.int32)[idx])
             _lib.call("mm_contrast_rows", P(self.ym), P(self.yv), self.ld, self.B, self.ng, int(ctrl), P(a), P(b), len(idx), int(which),
                       P(out), _stream())
-            return host(out)[: len(idx)]
+            return host(out)[: len(idx)] if to_host else out[: len(idx)]
 
         return host(st_m)[:n_tests], host(st_v)[:n_tests], rows
 
@@ -1031,13 +1032,13 @@ class Bootstrap1D:
         _lib.call("mm_contrast_design_stats", P(self.ym), P(self.yv), self.ld, self.B, self.ng, *map(P, d_tab), n_tests, P(st_m), P(st_v),
                   _stream())
 
-        def rows(which, idx):
+        def rows(which, idx, to_host=True, out=None):
             idx = np.asarray(idx, dtype=np.int64)
-            out = empty((max(1, len(idx)), self.ld), torch.float64)
+            out = _rows_out(out, len(idx), self.ld)
             a, b = dev(test_gene[idx]), dev(test_design[idx])
             _lib.call("mm_contrast_design_rows", P(self.ym), P(self.yv), self.ld, self.B, self.ng, P(a), P(b), *map(P, d_tab[2:]), len(idx),
                       int(which), P(out), _stream())
-            return host(out)[: len(idx)]
+            return host(out)[: len(idx)] if to_host else out[: len(idx)]
 
         return host(st_m)[:n_tests], host(st_v)[:n_tests], rows
 
@@ -1052,6 +1053,33 @@ class Bootstrap1D:
         device.  ``col_map``/``n_valid`` (from ``valid_cols``): surviving replicate columns, None = all of them."""
         return _contract_resampled(self.yv if which else self.ym, self.ld, self.B, self.ng, self.n_tested, test_gene, tt, good, gene_mask,
                                    M, Nc, rep, bcol, seed, col_map, n_valid)
+
+
+def _rows_out(out, n, ld):
+    """Where a ``rows`` closure writes ``n`` coefficient rows: a fresh tensor, or the caller's scratch ``out`` [>= n][ld] (fp64,
+    contiguous), reused from call to call."""
+    torch = _torch()
+    if out is None:
+        return empty((max(1, n), ld), torch.float64)
+    if out.dtype != torch.float64 or out.dim() != 2 or out.shape[1] != ld or out.shape[0] < max(1, n) or not out.is_contiguous():
+        raise ValueError(f"rows: out must be a contiguous fp64 tensor [>= {max(1, n)}][{ld}]")
+    return out
+
+
+def row_quantiles(rows, ld, num_boot, probs):
+    """np.nanquantile(row[1:num_boot + 1], probs) of every row of an [n_rows][ld] fp64 device tensor (mm_row_quantiles: an exact
+    radix select per row; column 0 and the padding are not read).  Returns (q device tensor [n_rows][n_probs], n_valid host
+    [n_rows] = the non-NaN columns of every row)."""
+    torch = _torch()
+    probs = np.ascontiguousarray(probs, dtype=np.float64).reshape(-1)
+    if rows.dtype != torch.float64 or not rows.is_cuda or not rows.is_contiguous() or rows.numel() % ld:
+        raise ValueError("row_quantiles: rows must be a contiguous fp64 device tensor of [n_rows][ld]")
+    n_rows = rows.numel() // ld
+    q = empty((max(1, n_rows), max(1, len(probs))), torch.float64)
+    n_valid = empty((max(1, n_rows),), torch.int32)
+    _lib.call("mm_row_quantiles", P(rows), n_rows, int(ld), int(num_boot), probs.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), len(probs),
+              P(q), P(n_valid), _stream())
+    return q[:n_rows], host(n_valid)[:n_rows]
 
 
 def _design_tables(test_row, test_design, design_ptr, design_grp, design_w, n_rows, ng):
@@ -1349,18 +1377,18 @@ class Bootstrap2D:
         """Guide-vs-control contrasts on the correlation rows (mm_contrast_design1_stats): test t applies the sparse weight row
         ``design_grp/design_w[design_ptr[d]:design_ptr[d + 1]]``, d = ``test_design[t]``, to the replicate rows of pair
         ``test_pair[t]`` (device pair order, ``self.order``).  Returns (stats host [n_tests][8], ``rows(idx)`` giving the
-        coefficient rows of selected tests on demand)."""
+        coefficient rows of selected tests on demand; ``to_host`` / ``out`` as in ``Bootstrap1D.contrast``)."""
         torch = _torch()
         test_pair, test_design, d_tab = _design_tables(test_pair, test_design, design_ptr, design_grp, design_w, self.n_pairs, self.ng)
         n_tests = len(test_pair)
         stats = empty((max(1, n_tests), 8), torch.float64)
         _lib.call("mm_contrast_design1_stats", P(self.yc), self.ld, self.B, self.ng, *map(P, d_tab), n_tests, P(stats), _stream())
 
-        def rows(idx):
+        def rows(idx, to_host=True, out=None):
             idx = np.asarray(idx, dtype=np.int64)
-            out = empty((max(1, len(idx)), self.ld), torch.float64)
+            out = _rows_out(out, len(idx), self.ld)
             a, b = dev(test_pair[idx]), dev(test_design[idx])
             _lib.call("mm_contrast_design1_rows", P(self.yc), self.ld, self.B, self.ng, P(a), P(b), *map(P, d_tab[2:]), len(idx), P(out), _stream())
-            return host(out)[: len(idx)]
+            return host(out)[: len(idx)] if to_host else out[: len(idx)]
 
         return host(stats)[:n_tests], rows

@@ -28,6 +28,52 @@ def check_args(rng, strict=False, **kwargs):
     return kwargs['resampling'], bool(kwargs.get('resample_rep', False)), bool(kwargs.get('approx', False))
 
 
+def ci_probs(ci):
+    """The ``ci`` keyword of the four drivers: None -> None (no interval); a level 0 < ci < 1 -> the two probabilities
+    ((1 - ci) / 2, (1 + ci) / 2) of the percentile interval; anything else raises ValueError.  Pure: runs before any device work."""
+    if ci is None:
+        return None
+    if isinstance(ci, (bool, np.bool_)) or not isinstance(ci, (int, float, np.integer, np.floating)) or not 0 < float(ci) < 1:
+        raise ValueError(f"ci must be None or a confidence level strictly between 0 and 1, not {ci!r}")
+    ci = float(ci)
+    return (1 - ci) / 2, (1 + ci) / 2
+
+
+# scratch for the coefficient rows of ``sliced_intervals``: not tuned, it only has to be small next to the replicate planes
+CI_SCRATCH_BYTES = 1 << 30
+
+
+def row_intervals(coef_rows, ld, num_boot, probs, coef0):
+    """Percentile intervals [test][2] (host) of coefficient rows that are resident (``coef_rows``: device [test][ld]): the
+    ``probs`` quantiles of the replicate columns 1..num_boot, dropped (NaN) columns excluded -- the columns the standard error
+    is taken over.  A test without a coefficient (``coef0`` NaN) has a NaN interval."""
+    q, _ = engine.row_quantiles(coef_rows, ld, num_boot, probs)
+    ci = engine.host(q).copy()
+    ci[np.isnan(coef0)] = np.nan
+    return ci
+
+
+def sliced_intervals(rows, ld, num_boot, probs, coef0, scratch_bytes=None):
+    """``row_intervals`` for tests whose coefficient rows are not stored: ``rows(idx, to_host=False, out=scratch)`` produces
+    them (``contrast`` / ``contrast_design`` of Bootstrap1D / Bootstrap2D), a slice of tests at a time, into ONE scratch tensor of
+    at most ``scratch_bytes`` (default ``CI_SCRATCH_BYTES``; never less than one row).  Every test's interval comes from its own
+    row alone, so the slicing changes no number.  Tests without a coefficient are not produced at all."""
+    if scratch_bytes is None:
+        scratch_bytes = CI_SCRATCH_BYTES
+    coef0 = np.asarray(coef0)
+    ci = np.full((len(coef0), 2), np.nan)
+    live = np.flatnonzero(~np.isnan(coef0))
+    if not len(live):
+        return ci
+    per = int(min(len(live), max(1, int(scratch_bytes) // (8 * ld))))
+    scratch = engine.empty((per, ld), engine._torch().float64)
+    for lo in range(0, len(live), per):
+        idx = live[lo:lo + per]
+        q, _ = engine.row_quantiles(rows(idx, to_host=False, out=scratch), ld, num_boot, probs)
+        ci[idx] = engine.host(q)
+    return ci
+
+
 def moments_view(m):
     """What a 1D test reads from ``uns['memento']``: the groups, their q and cell counts, the true moments [group][gene] and the
     mean-variance fit."""

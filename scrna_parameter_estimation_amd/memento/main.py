@@ -382,7 +382,7 @@ def _var_names(adata):
 
 
 def ht_1d_moments(adata, covariate, treatment, treatment_for_gene=None, inplace=True, num_boot=10000, verbose=1, num_cpus=1,
-                  rng='replay', strict=False, fill_seed=0, max_rows=None, **kwargs):
+                  rng='replay', strict=False, fill_seed=0, max_rows=None, ci=None, **kwargs):
     """Bootstrap hypothesis test of mean / residual-variance differences (reference: memento/main.py:341-415).
 
     ``rng='replay'``: the multinomial resampling replays numpy's ``Generator(PCG64(5))`` stream draw for
@@ -395,13 +395,23 @@ def ht_1d_moments(adata, covariate, treatment, treatment_for_gene=None, inplace=
     ``strict=True`` additionally replays the reference's ``_fill`` draws from the global stream in gene order
     (exactly reproducible against the reference at ``num_cpus=1``; sequential, meant for validation);
     with ``strict=False`` invalid replicates are re-filled on the device with a counter-based RNG.
+    ``ci``: a level 0 < ci < 1 adds the percentile interval of every coefficient, the (1 - ci) / 2 and (1 + ci) / 2 quantiles
+    (np.nanquantile, 'linear') of the replicate coefficients the standard error is taken over (columns 1..num_boot, dropped
+    columns excluded, not centred): ``uns['memento']['1d_ht']['mean_ci']`` / ``['var_ci']`` [test][2] and ``['ci']``, the level;
+    ``get_1d_ht_result`` then has ``de_ci_lo, de_ci_hi, dv_ci_lo, dv_ci_hi``.  A NaN coefficient has a NaN interval.  Not gathered
+    across ranks (NotImplementedError on a gene-sharded run).  ``ci=None`` (default): nothing is added and nothing more runs.
     kwargs: ``resampling`` (required, as in the reference), ``approx``, ``resample_rep``.
     """
     resampling, resample_rep, approx = _ht.check_args(rng, strict, **kwargs)
+    probs = _ht.ci_probs(ci)
     if not inplace:
         adata = adata.copy()
     m = adata.uns['memento']
     st = m['_hip']
+    comm = getattr(st, 'comm', None)
+    sharded = comm is not None and comm.world > 1
+    if sharded and probs is not None:
+        raise NotImplementedError("ci= on a gene-sharded run: the intervals are not gathered across ranks")
     mv = _ht.moments_view(m)
     ng = mv.ng
     names = _var_names(adata)
@@ -411,8 +421,6 @@ def ht_1d_moments(adata, covariate, treatment, treatment_for_gene=None, inplace=
     gene_cols = _ht.gene_columns(treatment, treatment_for_gene, names[:G_all])
     if st.sf_bin is None:
         raise NotImplementedError("more than 255 size-factor bins")
-    comm = getattr(st, 'comm', None)
-    sharded = comm is not None and comm.world > 1
     shard_stream = gene_pos = None
     if sharded:
         # The reference scatters every gene's result back from ONE sequential np.random stream (main.py:399-404, bootstrap.py:62-65):
@@ -500,6 +508,8 @@ def ht_1d_moments(adata, covariate, treatment, treatment_for_gene=None, inplace=
             fin = _asl.asl_from_stats(stt, approx, lambda idx, coef=coef: engine.host(coef[engine.dev(np.asarray(idx, dtype=np.int64))]),
                                       num_cpus, resampling, defer=True)
             c0[no_group], se[no_group] = np.nan, np.nan                                                   # hypothesis_test.py:203-204
+            if probs is not None:
+                out[tag + '_ci'] = _ht.row_intervals(coef[:len(test_gene)], bs.ld, num_boot, probs, c0)
             out[tag + '_coef'], out[tag + '_se'], out[tag + '_asl'] = c0, se, (fin, no_group)
         for tag in ('mean', 'var'):
             fin, no_group = out[tag + '_asl']
@@ -526,6 +536,10 @@ def ht_1d_moments(adata, covariate, treatment, treatment_for_gene=None, inplace=
     keys = ('mean_coef', 'mean_se', 'mean_asl', 'var_coef', 'var_se', 'var_asl')
     out = {k: (np.concatenate([p_[k] for p_ in parts]) if parts else np.zeros(0)) for k in keys}
     m['1d_ht'] = {}
+    if probs is not None:
+        for k in ('mean_ci', 'var_ci'):
+            m['1d_ht'][k] = np.concatenate([p_[k] for p_ in parts]) if parts else np.zeros((0, 2))
+        m['1d_ht']['ci'] = float(ci)
     if sharded:
         # gene-sharded run: scatter-back of the reference (main.py:399-412) across ranks -- every rank ends with the flat result
         # vectors of ALL genes in the unsharded run's order, plus the gene names they belong to
@@ -569,7 +583,7 @@ def _vs_control_plan(m, control, treatment_col):
 
 
 def ht_1d_vs_control(adata, control, num_boot=10000, num_cpus=1, rng='replay', fill_seed=0, max_rows=None, approx=False,
-                     resampling='bootstrap', *, treatment_col=None):
+                     resampling='bootstrap', *, treatment_col=None, ci=None):
     """Perturb-seq style batch test: every group against one shared ``control`` group (a label of
     ``adata.uns['memento']['groups']`` or its index), for all kept genes, in one call.
 
@@ -593,9 +607,14 @@ def ht_1d_vs_control(adata, control, num_boot=10000, num_cpus=1, rng='replay', f
     streams and, with ``rng='fast'``, the bootstrap streams are keyed by (``fill_seed``, gene, group) with the gene numbered over
     the whole call, so the chunking changes no number; in a one-chunk call the key is the chain's row.
 
+    ``ci`` as in ``ht_1d_moments``: the percentile interval of every coefficient.  The coefficient rows are not stored here: they
+    are produced for a slice of tests at a time into one bounded scratch tensor (``_ht.sliced_intervals``), which changes no
+    number.  Adds the columns ``de_ci_lo, de_ci_hi, dv_ci_lo, dv_ci_hi`` and ``mean_ci`` / ``var_ci`` [test][2] and ``ci`` to ``uns``.
+
     Returns a DataFrame (gene, group, de_coef, de_se, de_pval, dv_coef, dv_se, dv_pval) and stores the arrays in
     ``uns['memento']['1d_ht_vs_control']``."""
     _ht.check_args(rng, resampling=resampling)
+    probs = _ht.ci_probs(ci)
     m = adata.uns['memento']
     st = m['_hip']
     tested, designs, (ctrl, others), meta = _vs_control_plan(m, control, treatment_col)
@@ -608,6 +627,8 @@ def ht_1d_vs_control(adata, control, num_boot=10000, num_cpus=1, rng='replay', f
                                                                  # slower in a fresh one -- mapping fresh device memory costs ~30 ms per GB)
     chunk = max(1, int(max_rows) // max(1, ng))
     cols = {k: [] for k in ('mean_coef', 'mean_se', 'mean_asl', 'var_coef', 'var_se', 'var_asl')}
+    if probs is not None:
+        cols.update(mean_ci=[], var_ci=[])
     st.last_bootstrap = st.last_good = None    # (see ht_1d_moments: free the previous call's replicate rows first)
 
     def run_chunk(c):
@@ -630,14 +651,19 @@ def ht_1d_vs_control(adata, control, num_boot=10000, num_cpus=1, rng='replay', f
             cols[tag + '_coef'].append(stt[:, 0])
             cols[tag + '_se'].append(stt[:, 1])
             cols[tag + '_asl'].append(p)
+            if probs is not None:
+                cols[tag + '_ci'].append(_ht.sliced_intervals(functools.partial(rows, which), bs.ld, num_boot, probs, stt[:, 0]))
 
     for c in _ht.chunks_1d(st, mv, num_boot, chunk):
         run_chunk(c)
-    out = {k: (np.concatenate(v) if v else np.zeros(0)) for k, v in cols.items()}
+    out = {k: (np.concatenate(v) if v else np.zeros((0, 2) if k.endswith('_ci') else 0)) for k, v in cols.items()}
     m['1d_ht_vs_control'] = dict(out, **meta)
     df = pd.DataFrame({'gene': np.repeat(names, len(tested)), 'group': np.tile(tested, G_all)})
     df['de_coef'], df['de_se'], df['de_pval'] = out['mean_coef'], out['mean_se'], out['mean_asl']
     df['dv_coef'], df['dv_se'], df['dv_pval'] = out['var_coef'], out['var_se'], out['var_asl']
+    if probs is not None:
+        m['1d_ht_vs_control']['ci'] = float(ci)
+        _ci_columns(df, ('de', out['mean_ci']), ('dv', out['var_ci']))
     return df
 
 
@@ -763,7 +789,7 @@ def _replay_pair_draws(c, plan, uniforms, trt, tcol, per_gene, num_boot):
 
 
 def ht_2d_moments(adata, covariate, treatment, treatment_for_gene=None, inplace=True, num_boot=10000, verbose=3, num_cpus=1,
-                  max_rows=None, fill_seed=0, strict=False, rng='replay', **kwargs):
+                  max_rows=None, fill_seed=0, strict=False, rng='replay', ci=None, **kwargs):
     """Bootstrap hypothesis test of correlation differences (reference: memento/main.py:418-520,
     hypothesis_test._ht_2d :303-364).  Same replay semantics as ht_1d_moments.
     ``rng='fast'``: same samplers and replicate arithmetic, but every (pair, group, replicate) has its own counter-derived
@@ -778,12 +804,18 @@ def ht_2d_moments(adata, covariate, treatment, treatment_for_gene=None, inplace=
     draw-identical.  Without resample_rep the 2D path consumes the global stream exactly like the reference either way.
     ``treatment_for_gene`` as the reference BEHAVES (main.py:492): a pair's treatment columns are looked up under
     ``frozenset({name of the pair's first gene})`` -- the key is built from idx_1 twice -- and one number per pair is stored,
-    so the list must hold exactly one column (the reference raises ValueError on more); pinned by fixture ``api_tfg2d``."""
+    so the list must hold exactly one column (the reference raises ValueError on more); pinned by fixture ``api_tfg2d``.
+    ``ci`` as in ``ht_1d_moments``: ``uns['memento']['2d_ht']['corr_ci']`` [pair][2] (NaN for skipped pairs) and ``['ci']``;
+    ``get_2d_ht_result`` then has ``corr_ci_lo, corr_ci_hi``."""
     resampling, resample_rep, approx = _ht.check_args(rng, strict, **kwargs)
+    probs = _ht.ci_probs(ci)
     if not inplace:
         adata = adata.copy()
     m = adata.uns['memento']
     st = m['_hip']
+    comm = getattr(st, 'comm', None)
+    if probs is not None and comm is not None and comm.world > 1:
+        raise NotImplementedError("ci= on a run over several ranks: the intervals are not gathered across ranks")
     st.last_bootstrap2d = None                 # (free the previous call's replicate rows before this call allocates its own)
     Nc_list = np.array([m['group_cells'][g].shape[0] for g in m['groups']], dtype=np.float64)
     cov = np.asarray(covariate.values, dtype=np.float64)
@@ -801,6 +833,7 @@ def ht_2d_moments(adata, covariate, treatment, treatment_for_gene=None, inplace=
     replay_rr = resample_rep and strict                   # the choice draws interleave with the hash uniforms, pair by pair
     uniforms = np.zeros((3, plan.P_ * plan.ng)) if replay_rr else _ht.hash_uniforms(~plan.skip.reshape(-1), 3)
     corr_coef, corr_se, corr_asl = (np.full(plan.n_conv, np.nan) for _ in range(3))
+    corr_ci = np.full((plan.n_conv, 2), np.nan) if probs is not None else None
 
     def run_chunk(c):
         bs = c.bs
@@ -820,10 +853,15 @@ def ht_2d_moments(adata, covariate, treatment, treatment_for_gene=None, inplace=
         pvals = _asl.asl_from_stats(stt, approx, lambda idx: engine.host(coef[engine.dev(np.asarray(idx, dtype=np.int64))]), num_cpus, resampling)
         for dst, src in ((corr_coef, stt[:, 0]), (corr_se, stt[:, 1]), (corr_asl, pvals)):
             _ht.scatter_pairs(c, plan, dst, src, keep=good.any(axis=1))
+        if probs is not None:
+            _ht.scatter_pairs(c, plan, corr_ci, _ht.row_intervals(coef[:len(d.test_row)], bs.ld, num_boot, probs, stt[:, 0]),
+                              keep=good.any(axis=1))
 
     for c in _ht.chunks_2d(st, plan, num_boot):
         run_chunk(c)
     m['2d_ht'] = {'treatment': treatment, 'covariate': covariate, 'corr_coef': corr_coef, 'corr_se': corr_se, 'corr_asl': corr_asl}
+    if probs is not None:
+        m['2d_ht']['corr_ci'], m['2d_ht']['ci'] = corr_ci, float(ci)
     if treatment_for_gene is not None:
         m['2d_ht']['treatment_for_gene'] = treatment_for_gene                      # main.py:513-514
     if not inplace:
@@ -831,7 +869,7 @@ def ht_2d_moments(adata, covariate, treatment, treatment_for_gene=None, inplace=
 
 
 def ht_2d_vs_control(adata, control, num_boot=10000, num_cpus=1, fill_seed=0, max_rows=None, approx=False, resampling='bootstrap',
-                     rng='replay', *, treatment_col=None):
+                     rng='replay', *, treatment_col=None, ci=None):
     """Perturb-seq style batch test of differential COEXPRESSION: the correlation of every pair of ``compute_2d_moments`` in
     every group against one shared ``control``, in one call.  ``control`` / ``treatment_col`` mean what they mean in
     ``ht_1d_vs_control``: without ``treatment_col`` a group label (or index) every other group is tested against; with it the
@@ -850,9 +888,12 @@ def ht_2d_vs_control(adata, control, num_boot=10000, num_cpus=1, fill_seed=0, ma
     is NaN.  ``rng='replay'|'fast'`` as in ``ht_2d_moments``: ``'fast'`` draws every (pair, group, replicate) from its own
     stream seeded by ``fill_seed`` (mm_boot2d_fast), with the same bins, ``corr_coef`` and NaN pattern as ``'replay'``.
 
+    ``ci`` as in ``ht_1d_vs_control``: adds the columns ``corr_ci_lo, corr_ci_hi`` and ``corr_ci`` [test][2] and ``ci`` to ``uns``.
+
     Returns a DataFrame (gene_1, gene_2, group, corr_coef, corr_se, corr_pval), pair-major, one row per (requested pair,
     tested guide), and stores the arrays in ``uns['memento']['2d_ht_vs_control']``."""
     _ht.check_args(rng, resampling=resampling)
+    probs = _ht.ci_probs(ci)
     m = adata.uns['memento']
     st = m['_hip']
     st.last_bootstrap2d = None                 # (free the previous call's replicate rows before this call allocates its own)
@@ -866,6 +907,7 @@ def ht_2d_vs_control(adata, control, num_boot=10000, num_cpus=1, fill_seed=0, ma
     plan = _ht.pair_plan(m, st, num_boot, max_rows)
     uniforms = _ht.hash_uniforms(~plan.skip.reshape(-1), 3)
     out = {k: np.full((plan.n_conv, n_t), np.nan) for k in ('corr_coef', 'corr_se', 'corr_asl')}
+    corr_ci = np.full((plan.n_conv, n_t * 2), np.nan) if probs is not None else None
 
     def run_chunk(c):
         good = _ht.run_chunk_2d(c, plan, uniforms, rng, fill_seed)                 # device order
@@ -879,22 +921,35 @@ def ht_2d_vs_control(adata, control, num_boot=10000, num_cpus=1, fill_seed=0, ma
         pvals = _asl.asl_from_stats(stt, approx, rows, num_cpus, resampling)
         for key, src in (('corr_coef', stt[:, 0]), ('corr_se', stt[:, 1]), ('corr_asl', pvals)):
             _ht.scatter_pairs(c, plan, out[key], src)
+        if probs is not None:
+            _ht.scatter_pairs(c, plan, corr_ci, _ht.sliced_intervals(rows, c.bs.ld, num_boot, probs, stt[:, 0]))
 
     for c in _ht.chunks_2d(st, plan, num_boot):
         run_chunk(c)
     out = {k: v.reshape(-1) for k, v in out.items()}
     m['2d_ht_vs_control'] = dict(out, **meta)
+    if probs is not None:
+        m['2d_ht_vs_control'].update(corr_ci=corr_ci.reshape(-1, 2), ci=float(ci))
     n_conv = plan.n_conv
     pairs = list(m['2d_moments']['gene_pairs'])
     df = pd.DataFrame({'gene_1': np.repeat([a for a, _ in pairs], n_t), 'gene_2': np.repeat([b for _, b in pairs], n_t),
                        'group': np.tile(tested, n_conv)})
     df['corr_coef'], df['corr_se'], df['corr_pval'] = out['corr_coef'], out['corr_se'], out['corr_asl']
+    if probs is not None:
+        _ci_columns(df, ('corr', m['2d_ht_vs_control']['corr_ci']))
     return df
 
 
 # ----------------------------------------------------------------------------------------------
 # getters
 # ----------------------------------------------------------------------------------------------
+
+
+def _ci_columns(df, *named):
+    """Append ``<name>_ci_lo`` / ``<name>_ci_hi`` to a result table for every (name, interval array [test][2])."""
+    for name, ci in named:
+        ci = np.asarray(ci).reshape(-1, 2)
+        df[name + '_ci_lo'], df[name + '_ci_hi'] = ci[:, 0], ci[:, 1]
 
 
 def get_1d_moments(adata, groupby=None):
@@ -944,6 +999,8 @@ def get_1d_ht_result(adata):
     df = pd.DataFrame(pairs, columns=['gene', 'tx'])
     df['de_coef'], df['de_se'], df['de_pval'] = ht['mean_coef'], ht['mean_se'], ht['mean_asl']
     df['dv_coef'], df['dv_se'], df['dv_pval'] = ht['var_coef'], ht['var_se'], ht['var_asl']
+    if 'mean_ci' in ht and 'var_ci' in ht:      # ht_1d_moments(ci=...)
+        _ci_columns(df, ('de', ht['mean_ci']), ('dv', ht['var_ci']))
     return df
 
 
@@ -990,4 +1047,6 @@ def get_2d_ht_result(adata):
     m = adata.uns['memento']
     df = pd.DataFrame(m['2d_moments']['gene_pairs'], columns=['gene_1', 'gene_2'])
     df['corr_coef'], df['corr_se'], df['corr_pval'] = m['2d_ht']['corr_coef'], m['2d_ht']['corr_se'], m['2d_ht']['corr_asl']
+    if 'corr_ci' in m['2d_ht']:                 # ht_2d_moments(ci=...)
+        _ci_columns(df, ('corr', m['2d_ht']['corr_ci']))
     return df
