@@ -392,6 +392,27 @@ int mm_contrast_design1_rows(const double *d_y, int64_t ld, int32_t num_boot, in
                              const int32_t *d_test_design, const int32_t *d_design_ptr, const int32_t *d_design_grp,
                              const double *d_design_w, int64_t n_tests, double *d_out, void *stream);
 
+/* ---- joint test of a block of treatment columns (ht_1d_joint) ------------------------------------------------------
+ * test t applies the r = design_rank[d] linear forms of design d = test_design[t] to every replicate column of gene
+ * test_gene[t]: L [r][n_d] row-major at d_design_L + design_lofs[d], over the n_d groups
+ * design_grp[design_ptr[d] .. design_ptr[d + 1]) (memento/design.py: joint_rows), and reduces
+ *   Q_0 = ||L y_0||^2  and, for the replicate columns c = 1..num_boot,  Q*_c = ||L y_c - L y_0||^2  (the centred bootstrap null)
+ * for the mean and the variability plane in one launch.  The record, 8 doubles per test and plane (NOT the layout of
+ * mm_contract_stats):
+ *   [0] Q_0   [1] population sd of Q* over the valid columns   [2] n_valid   [3] n_extreme = #{ Q*_c > Q_0 } (strict)
+ *   [4] mean of Q*   [5] all_equal: 1 when every valid Q*_c is exactly 0   [6] max of Q*   [7] r
+ * ([1], [4], [6] are NaN and [5] is 0 when n_valid == 0).  Column c is valid only if every listed group is finite there in
+ * BOTH planes.  An invalid column 0, an empty design and r = 0 give the NaN record of mm_contract_stats on both planes
+ * ([2], [3], [5] zero, the rest NaN).  A form sums its groups in ascending p, Q sums its forms in ascending k, unfused; L is
+ * staged in LDS when r * n_d <= 4096 doubles and read through the cache otherwise, with the same arithmetic.  Nothing
+ * per-replicate is stored.  The tables are trusted -- validate them on the host: every design needs
+ * 0 <= r <= n_d <= n_groups, group indices in [0, n_groups), r * n_d doubles at design_lofs[d], and every test a gene slot of
+ * the planes.  Needs n_groups <= 2048 (z_0 of both planes and the staged L share 64 KB of LDS). */
+int mm_joint_stats(const double *d_ym, const double *d_yv, int64_t ld, int32_t num_boot, int32_t n_groups,
+                   const int32_t *d_test_gene, const int32_t *d_test_design, const int32_t *d_design_ptr,
+                   const int32_t *d_design_rank, const int64_t *d_design_lofs, const int32_t *d_design_grp,
+                   const double *d_design_L, int64_t n_tests, double *d_stats_mean, double *d_stats_var, void *stream);
+
 /* ---- order statistics of replicate rows (percentile intervals of the coefficients) -------------------------------
  * For every row of d_rows [n_rows][ld]: the replicate columns 1..num_boot (column 0, the observed value, and the padding
  * from num_boot + 1 on are not read), NaNs dropped; d_n_valid[row] = n, the number of columns kept, and

@@ -528,6 +528,205 @@ __global__ __launch_bounds__(256) void k_contrast_design1_rows(const double *__r
 }
 
 // ------------------------------------------------------------------------------------------------
+// Joint test of a block of treatment columns (ht_1d_joint): test t applies the r linear forms of design d = test_design[t] --
+// L [r][n_d] row-major at design_L + design_lofs[d], over the n_d groups design_grp[design_ptr[d] .. design_ptr[d + 1]) -- to
+// every replicate column of gene test_gene[t] and reduces the quadratic statistic
+//   Q_0 = ||L y_0||^2,   Q*_c = ||L y_c - L y_0||^2  (c >= 1: the centred bootstrap null),
+// on the mean and the variability plane at once.  THE JOINT RECORD, 8 doubles per test and plane:
+//   [0] Q_0   [1] population sd of Q* over the valid columns 1..B   [2] n_valid   [3] n_extreme = #{ Q*_c > Q_0 }
+//   [4] mean of Q*   [5] all_equal: 1 when every valid Q*_c is exactly 0   [6] max of Q*   [7] r
+// Column c is valid only if every listed group is finite there in BOTH planes (hypothesis_test.py:249-251); an invalid
+// column 0, an empty design and r = 0 give the NaN record on both planes.  z_0 = L y_0 is formed first and kept in LDS.  A form
+// sums p ascending, Q sums k ascending, and column 0 goes through the same routine as the others: a replicate column equal to
+// column 0 has Q* == 0 exactly.  L is staged in LDS when r * n_d <= JOINT_LDS_DOUBLES (32 KB: a choice that leaves four
+// workgroups per CU, not a measurement) and comes through the cache otherwise; both paths do the same arithmetic in the same
+// order.  Two passes that recompute Q* (count / sum / max, then squared deviations and the extreme count): nothing
+// per-replicate is stored.  Up to JOINT_REG_GROUPS groups a thread keeps its column's operands in registers (one read of the
+// planes per pass; instantiated for JOINT_REG_SMALL and for JOINT_REG_GROUPS); beyond, the rows are read again for every form and come back
+// from L1 / L2.
+#define JOINT_LDS_DOUBLES 4096
+#define JOINT_REG_GROUPS 32
+#define JOINT_REG_SMALL 8      // the narrower tier: 84 VGPRs against 182, 2.5x the wider one's speed on designs it holds (profiles/joint_stats.txt)
+
+struct joint_design {
+  const double *ym, *yv;      // the planes, offset to the gene's first row
+  const int32_t *grp;         // [nd]
+  int64_t ld;
+  int nd, r;
+};
+
+// forms k of column c on both planes: each L element and each operand offset is read once
+template <class LP>
+__device__ __forceinline__ void joint_form(const joint_design &D, LP Lk, int c, double &am, double &av) {
+  am = 0.0;
+  av = 0.0;
+  for (int p = 0; p < D.nd; p++) {
+    int64_t o = (int64_t)D.grp[p] * D.ld + c;
+    double l = Lk[p];
+    am += l * D.ym[o];
+    av += l * D.yv[o];
+  }
+}
+
+__device__ __forceinline__ bool joint_valid(const joint_design &D, int c) {
+  bool ok = true;
+  for (int p = 0; p < D.nd; p++) {
+    int64_t o = (int64_t)D.grp[p] * D.ld + c;
+    ok = ok && isfinite(D.ym[o]) && isfinite(D.yv[o]);
+  }
+  return ok;
+}
+
+// Q* of column c on both planes into q; returns whether the column is valid.  NDR == 0: any n_d, the operands are read again for
+// every form and come back from L1 / L2.  NDR > 0 (n_d <= NDR): the column's operands are read ONCE into registers, which also
+// decides its validity, and the forms run on registers and the LDS copy of L.  The arithmetic and its order are those of
+// joint_form either way.  LP: ``const double *`` into LDS (staged) or into global memory; z0m / z0v [r] in LDS.
+template <int NDR, class LP>
+__device__ __forceinline__ bool joint_q(const joint_design &D, LP L, const double *z0m, const double *z0v, int c, double (&q)[2]) {
+  q[0] = q[1] = 0.0;
+  if constexpr (NDR == 0) {
+    if (!joint_valid(D, c)) return false;
+    for (int k = 0; k < D.r; k++) {
+      double am, av;
+      joint_form(D, L + (int64_t)k * D.nd, c, am, av);
+      double dm = am - z0m[k], dv = av - z0v[k];
+      q[0] += dm * dm;
+      q[1] += dv * dv;
+    }
+  } else {
+    double a[NDR], b[NDR];
+    bool ok = true;
+#pragma unroll
+    for (int p = 0; p < NDR; p++) {
+      a[p] = b[p] = 0.0;
+      if (p < D.nd) {
+        int64_t o = (int64_t)D.grp[p] * D.ld + c;
+        a[p] = D.ym[o];
+        b[p] = D.yv[o];
+        ok = ok && isfinite(a[p]) && isfinite(b[p]);
+      }
+    }
+    if (!ok) return false;
+    for (int k = 0; k < D.r; k++) {
+      LP Lk = L + (int64_t)k * D.nd;
+      double am = 0.0, av = 0.0;
+#pragma unroll
+      for (int p = 0; p < NDR; p++) {
+        if (p < D.nd) {
+          double l = Lk[p];
+          am += l * a[p];
+          av += l * b[p];
+        }
+      }
+      double dm = am - z0m[k], dv = av - z0v[k];
+      q[0] += dm * dm;
+      q[1] += dv * dv;
+    }
+  }
+  return true;
+}
+
+// Called by all threads of the workgroup.
+template <int NDR, class LP>
+__device__ __forceinline__ void joint_records(const joint_design &D, LP L, double *z0m, double *z0v, int num_boot, double *stm,
+                                              double *stv, double *red) {
+  for (int k = threadIdx.x; k < D.r; k += K9_THREADS) {
+    double am, av;
+    joint_form(D, L + (int64_t)k * D.nd, 0, am, av);
+    z0m[k] = am;
+    z0v[k] = av;
+  }
+  __syncthreads();
+  double q0[2] = {0.0, 0.0};
+  for (int k = 0; k < D.r; k++) {
+    q0[0] += z0m[k] * z0m[k];
+    q0[1] += z0v[k] * z0v[k];
+  }
+  double q[2], sum[2] = {0.0, 0.0}, hi[2] = {-INFINITY, -INFINITY}, cnt = 0.0;
+  for (int c = 1 + threadIdx.x; c <= num_boot; c += K9_THREADS) {
+    if (!joint_q<NDR>(D, L, z0m, z0v, c, q)) continue;
+    for (int k = 0; k < 2; k++) { sum[k] += q[k]; hi[k] = fmax(hi[k], q[k]); }
+    cnt += 1.0;
+  }
+  double n = wg_sum(cnt, red), mean[2], sq[2] = {0.0, 0.0}, ext[2] = {0.0, 0.0};
+  for (int k = 0; k < 2; k++) {
+    sum[k] = wg_sum(sum[k], red);
+    hi[k] = wg_max(hi[k], red);
+    mean[k] = n > 0 ? sum[k] / n : NAN;
+  }
+  for (int c = 1 + threadIdx.x; c <= num_boot; c += K9_THREADS) {
+    if (!joint_q<NDR>(D, L, z0m, z0v, c, q)) continue;
+    for (int k = 0; k < 2; k++) {
+      double d = q[k] - mean[k];
+      sq[k] += d * d;
+      if (q[k] > q0[k]) ext[k] += 1.0;
+    }
+  }
+  for (int k = 0; k < 2; k++) { sq[k] = wg_sum(sq[k], red); ext[k] = wg_sum(ext[k], red); }
+  if (threadIdx.x == 0) {
+    for (int k = 0; k < 2; k++) {
+      double *s = k ? stv : stm;
+      s[0] = q0[k];
+      s[1] = n > 0 ? sqrt(sq[k] / n) : NAN;
+      s[2] = n;
+      s[3] = ext[k];
+      s[4] = mean[k];
+      s[5] = (n > 0 && hi[k] == 0.0) ? 1.0 : 0.0;
+      s[6] = n > 0 ? hi[k] : NAN;
+      s[7] = (double)D.r;
+    }
+  }
+}
+
+// NDR: 0, or a bound on n_groups (and so on every n_d) that lets a column's operands live in registers (joint_q)
+template <int NDR>
+__global__ __launch_bounds__(K9_THREADS) void k_joint_stats(const double *__restrict__ ym, const double *__restrict__ yv, int64_t ld,
+                                                            int32_t num_boot, int32_t n_groups, int32_t stage_cap,
+                                                            const int32_t *__restrict__ test_gene, const int32_t *__restrict__ test_design,
+                                                            const int32_t *__restrict__ design_ptr, const int32_t *__restrict__ design_rank,
+                                                            const int64_t *__restrict__ design_lofs, const int32_t *__restrict__ design_grp,
+                                                            const double *__restrict__ design_L, double *__restrict__ stats_m,
+                                                            double *__restrict__ stats_v) {
+  extern __shared__ double sm[];
+  double *z0m = sm, *z0v = sm + n_groups, *Ls = sm + 2 * (int64_t)n_groups;   // [n_groups], [n_groups], [stage_cap]
+  __shared__ double red[K9_THREADS / 64];
+  int64_t t = blockIdx.x;
+  int gene = test_gene[t], d = test_design[t];
+  int p0 = design_ptr[d], p1 = design_ptr[d + 1];
+  double *stm = stats_m + t * 8, *stv = stats_v + t * 8;
+  joint_design D;
+  D.nd = p1 - p0;
+  D.r = design_rank[d];
+  if (D.nd <= 0 || D.r <= 0 || D.r > n_groups || (NDR > 0 && D.nd > NDR)) {
+    write_nan_record(stm);
+    write_nan_record(stv);
+    return;
+  }
+  D.ld = ld;
+  D.grp = design_grp + p0;
+  D.ym = ym + (int64_t)gene * n_groups * ld;
+  D.yv = yv + (int64_t)gene * n_groups * ld;
+  const double *Lg = design_L + design_lofs[d];
+  const int n_l = D.r * D.nd;                       // <= n_groups^2 < 2^31 (checked by the caller)
+  const bool staged = n_l <= stage_cap;
+  if (staged)
+    for (int i = threadIdx.x; i < n_l; i += K9_THREADS) Ls[i] = Lg[i];
+  double ok0 = 1.0;                                 // column 0: every listed group finite in both planes?
+  for (int p = threadIdx.x; p < D.nd; p += K9_THREADS) {
+    int64_t o = (int64_t)D.grp[p] * ld;
+    if (!(isfinite(D.ym[o]) && isfinite(D.yv[o]))) ok0 = 0.0;
+  }
+  ok0 = wg_min(ok0, red);                           // (its barriers also publish Ls)
+  if (ok0 == 0.0) {
+    write_nan_record(stm);
+    write_nan_record(stv);
+    return;
+  }
+  if (staged) joint_records<NDR>(D, (const double *)Ls, z0m, z0v, num_boot, stm, stv, red);
+  else joint_records<NDR>(D, Lg, z0m, z0v, num_boot, stm, stv, red);
+}
+
+// ------------------------------------------------------------------------------------------------
 // Order statistics of a replicate row (percentile intervals of the coefficients): np.nanquantile(row[1 : B + 1], probs),
 // method 'linear', for up to RQ_MAX_PROBS probabilities per launch.  One workgroup per row.  Every double maps to a uint64 key
 // of the same order (negatives: all bits flipped; others: sign bit flipped) and the two order statistics of every probability
@@ -762,6 +961,26 @@ int mm_contrast_design_rows(const double *d_ym, const double *d_yv, int64_t ld, 
   if (n_tests == 0) return MM_OK;
   hipLaunchKernelGGL(k_contrast_design_rows, dim3((unsigned)n_tests), dim3(256), 0, (hipStream_t)stream, d_ym, d_yv, ld, num_boot, n_groups,
                      d_test_gene, d_test_design, d_design_ptr, d_design_grp, d_design_w, which, d_out);
+  MM_LAUNCH_CHECK();
+  return MM_OK;
+}
+
+int mm_joint_stats(const double *d_ym, const double *d_yv, int64_t ld, int32_t num_boot, int32_t n_groups,
+                   const int32_t *d_test_gene, const int32_t *d_test_design, const int32_t *d_design_ptr,
+                   const int32_t *d_design_rank, const int64_t *d_design_lofs, const int32_t *d_design_grp,
+                   const double *d_design_L, int64_t n_tests, double *d_stats_mean, double *d_stats_var, void *stream) {
+  MM_ARG(d_ym && d_yv && d_test_gene && d_test_design && d_design_ptr && d_design_rank && d_design_lofs && d_design_grp && d_design_L);
+  MM_ARG(d_stats_mean && d_stats_var);
+  MM_ARG(n_tests >= 0 && n_tests < 2147483647LL && n_groups > 0 && num_boot > 0 && ld >= (int64_t)num_boot + 1);
+  // a design has r <= n_d <= n_groups: z_0 of both planes takes 2 x n_groups doubles, the staged L at most JOINT_LDS_DOUBLES
+  int64_t cap = (int64_t)n_groups * n_groups < JOINT_LDS_DOUBLES ? (int64_t)n_groups * n_groups : JOINT_LDS_DOUBLES;
+  size_t shm = ((size_t)n_groups * 2 + (size_t)cap) * 8;
+  MM_ARG(shm <= 64 * 1024);
+  if (n_tests == 0) return MM_OK;
+  auto kernel = n_groups <= JOINT_REG_SMALL ? k_joint_stats<JOINT_REG_SMALL> : n_groups <= JOINT_REG_GROUPS ? k_joint_stats<JOINT_REG_GROUPS> : k_joint_stats<0>;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)n_tests), dim3(K9_THREADS), shm, (hipStream_t)stream, d_ym, d_yv, ld, num_boot, n_groups,
+                     (int32_t)cap, d_test_gene, d_test_design, d_design_ptr, d_design_rank, d_design_lofs, d_design_grp, d_design_L,
+                     d_stats_mean, d_stats_var);
   MM_LAUNCH_CHECK();
   return MM_OK;
 }

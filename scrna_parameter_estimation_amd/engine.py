@@ -1042,6 +1042,19 @@ class Bootstrap1D:
 
         return host(st_m)[:n_tests], host(st_v)[:n_tests], rows
 
+    def joint(self, test_gene, tables):
+        """Joint tests of a treatment block (mm_joint_stats): test t applies the linear forms of design ``tables.test_design[t]``
+        (``memento._ht.joint_tables``: ``design_ptr``, ``design_rank``, ``design_lofs``, ``design_grp``, ``design_L``) to the
+        replicate rows of gene ``test_gene[t]``.  Returns (stats_mean, stats_var) host arrays [n_tests][8], the joint record of
+        include/memento_hip.h."""
+        torch = _torch()
+        test_gene, d_tab = _joint_tables(test_gene, tables, self.n_tested, self.ng)
+        n_tests = len(test_gene)
+        st_m = empty((max(1, n_tests), 8), torch.float64)
+        st_v = empty((max(1, n_tests), 8), torch.float64)
+        _lib.call("mm_joint_stats", P(self.ym), P(self.yv), self.ld, self.B, self.ng, *map(P, d_tab), n_tests, P(st_m), P(st_v), _stream())
+        return host(st_m)[:n_tests], host(st_v)[:n_tests]
+
     def valid_cols(self, good):
         """hypothesis_test.py:249-251 on the device: (col_map device tensor [n_tested][B+1], n_valid host [n_tested]) --
         the replicate columns in which every good group is finite in both the mean and the variability rows."""
@@ -1107,6 +1120,40 @@ def _design_tables(test_row, test_design, design_ptr, design_grp, design_w, n_ro
         return dev(a if len(a) else np.zeros(1, a.dtype))
 
     return test_row, test_design, (up(test_row), up(test_design), dev(design_ptr), up(design_grp), up(design_w))
+
+
+def _joint_tables(test_gene, tables, n_rows, ng):
+    """The tables of mm_joint_stats (``Bootstrap1D.joint``), coerced, checked (the kernel trusts them) and uploaded, empty arrays
+    padded to one element: every design has 0 <= rank <= n_d <= ``ng`` groups, all in [0, ng), and rank x n_d doubles of
+    ``design_L`` at its offset; every test names a gene slot < ``n_rows`` and a design.  Returns test_gene as an int32 host array
+    and the device tensors (test_gene, test_design, design_ptr, design_rank, design_lofs, design_grp, design_L), the order in
+    which the kernel takes them."""
+    test_gene = np.asarray(test_gene, dtype=np.int32)
+    test_design = np.asarray(tables.test_design, dtype=np.int32)
+    design_ptr = np.asarray(tables.design_ptr, dtype=np.int32)
+    design_rank = np.asarray(tables.design_rank, dtype=np.int32)
+    design_lofs = np.asarray(tables.design_lofs, dtype=np.int64)
+    design_grp = np.asarray(tables.design_grp, dtype=np.int32)
+    design_L = np.asarray(tables.design_L, dtype=np.float64).reshape(-1)
+    n_tests, n_designs = len(test_gene), len(design_ptr) - 1
+    if len(test_design) != n_tests or n_designs < 0 or len(design_rank) != n_designs or len(design_lofs) != n_designs:
+        raise ValueError("joint: inconsistent table sizes")
+    if design_ptr[0] != 0 or design_ptr[-1] != len(design_grp) or (np.diff(design_ptr) < 0).any():
+        raise ValueError("joint: design_ptr is not a CSR pointer over design_grp")
+    if len(design_grp) and (design_grp.min() < 0 or design_grp.max() >= ng):
+        raise ValueError("joint: group index out of range")
+    n_d = np.diff(design_ptr).astype(np.int64)
+    if (n_d > ng).any() or (design_rank < 0).any() or (design_rank > n_d).any():
+        raise ValueError("joint: a design needs 0 <= rank <= its number of groups <= n_groups")
+    if n_designs and ((design_lofs < 0).any() or (design_lofs + design_rank * n_d > len(design_L)).any()):
+        raise ValueError("joint: design_lofs / design_rank run past design_L")
+    if n_tests and (test_gene.min() < 0 or test_gene.max() >= n_rows or test_design.min() < 0 or test_design.max() >= n_designs):
+        raise ValueError("joint: test index out of range")
+
+    def up(a):
+        return dev(a if len(a) else np.zeros(1, a.dtype))
+
+    return test_gene, (up(test_gene), up(test_design), dev(design_ptr), up(design_rank), up(design_lofs), up(design_grp), up(design_L))
 
 
 def _valid_cols(ym, yv, ld, B, ng, good, n_genes):

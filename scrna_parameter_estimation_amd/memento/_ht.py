@@ -204,6 +204,37 @@ def pair_design_tables(good, tcol, per_gene, cov, trt, Nc, resampled=False):
     return design_tables(good, cols, cov, trt, Nc, resampled, rr_cols=cols if per_gene else [None] * len(cols), first_only=True)
 
 
+def joint_tables(good, cov, trt, Nc):
+    """The designs of the joint test (``design.joint_rows``) of a chunk: row ``k`` of ``good`` [rows][groups] (a gene) is tested
+    once, on its good groups; one design per distinct good mask, shared by the rows that have it.
+
+    -> ``test_design`` [row] and the CSR-like tables the kernel takes (``Bootstrap1D.joint``): ``design_ptr`` [design + 1] into
+    ``design_grp`` (every good group of the mask, ascending), ``design_rank`` [design], ``design_lofs`` [design] (int64 offset
+    into ``design_L``) and ``design_L`` (row-major rank x n_d per design: the columns of L on the good groups)."""
+    good = np.asarray(good, dtype=bool)
+    cache = {}
+    test_design = np.zeros(good.shape[0], dtype=np.int32)
+    ptr, rank, lofs, grp, Ls, n_l = [0], [], [], [], [], 0
+    for k in range(good.shape[0]):
+        key = good[k].tobytes()
+        d = cache.get(key)
+        if d is None:
+            d = cache[key] = len(rank)
+            idx = np.flatnonzero(good[k])
+            L = _design.joint_rows(cov, trt, Nc, good[k])[:, idx]
+            grp.append(idx)
+            ptr.append(ptr[-1] + len(idx))
+            rank.append(L.shape[0])
+            lofs.append(n_l)
+            Ls.append(L.reshape(-1))
+            n_l += L.size
+        test_design[k] = d
+    return SimpleNamespace(
+        test_design=test_design, design_ptr=np.asarray(ptr, dtype=np.int32), design_rank=np.asarray(rank, dtype=np.int32),
+        design_lofs=np.asarray(lofs, dtype=np.int64), design_grp=np.concatenate(grp).astype(np.int32) if grp else np.zeros(0, np.int32),
+        design_L=np.concatenate(Ls).astype(np.float64) if Ls else np.zeros(0))
+
+
 def surviving_cols(bs, good, num_boot):
     """The replicate columns that survive hypothesis_test.py:249-251 / :372-373 (``bs.valid_cols``); (None, None) when nothing
     was dropped (the usual case): identity map."""

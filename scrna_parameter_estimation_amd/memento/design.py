@@ -4,6 +4,7 @@ Everything ``_regress_1d`` / ``_regress_2d`` do before ``_compute_asl`` is LINEA
 replicate vector (/root/reference/memento/hypothesis_test.py:262-271, :290-291, :218-228), so for a given
 set of valid groups it is a fixed matrix ``W`` (T x n_groups):  coef[t, b] = sum_j W[t, j] * y[j, b].
 The HIP kernel mm_contract_stats applies it; this module only builds W (tiny dense algebra, numpy).
+``joint_rows`` builds, in the same way, the block of linear forms of the joint test of several treatment columns (mm_joint_stats).
 """
 
 import numpy as np
@@ -80,6 +81,44 @@ def residual_parts(cov, trt, Nc, good):
     pred = c @ coef + (t_off - c_off @ coef)
     tt[:, idx] = (t - pred).T
     return M, tt
+
+
+# singular values of the weighted residualised treatment block at or below RANK_TOL * max(1, s_max) are zero (joint_rows)
+RANK_TOL = 1e-10
+
+
+def joint_rows(cov, trt, Nc, good):
+    """The design of the joint test of a treatment BLOCK (``ht_1d_joint``): L (r x n_groups, zero on groups that are not
+    ``good``) with the statistic Q(y) = ||L y||^2 -- the weighted sum of squares of the covariate-adjusted response that the
+    treatment columns explain together.
+
+    With w = Nc / sum(Nc) on the good groups, D = diag(w), M the residual maker of the weighted fit on [1, cov] (the pinv hat
+    matrix of ``weight_rows``) and the thin SVD  D^1/2 M trt = U S V':  r = #{s > RANK_TOL * max(1, s_max)} and
+    L = U[:, :r]' D^1/2 M.  L [1, cov] = 0 and L D^-1 L' = I_r; Q depends on the column SPACE of the residualised block only
+    (which dummy is dropped, or all dummies given: the same Q); for one column L = +-sqrt(ss) * weight_rows, so Q = ss * coef^2.
+    Shape (0, n_groups) -- nothing to test -- when no group is good, when the residualised block is numerically zero (the
+    treatment lies in the span of [1, cov]) and when the treatment is all ones on the good groups."""
+    cov = np.asarray(cov, dtype=np.float64)
+    trt = np.asarray(trt, dtype=np.float64)
+    Nc = np.asarray(Nc, dtype=np.float64)
+    good = np.asarray(good, dtype=bool)
+    idx = np.flatnonzero(good)
+    n, ng = len(idx), len(good)
+    if n == 0 or trt.shape[1] == 0:
+        return np.zeros((0, ng))
+    c, t, w = cov[idx], trt[idx], Nc[idx]
+    if (t == 1).mean() == 1:
+        return np.zeros((0, ng))
+    Xa = np.column_stack([np.ones(n), c])
+    sw = np.sqrt(w)
+    H = Xa @ (np.linalg.pinv(Xa * sw[:, None]) * sw[None, :])
+    M = np.eye(n) - H
+    sd = np.sqrt(w / w.sum())
+    U, s, _ = np.linalg.svd(sd[:, None] * (M @ t), full_matrices=False)
+    r = int((s > RANK_TOL * max(1.0, s.max())).sum())
+    L = np.zeros((r, ng))
+    L[:, idx] = U[:, :r].T @ (sd[:, None] * M)
+    return L
 
 
 # residualised-treatment sums of squares at or below this are "no stratum holds both arms" (exact zero up to round-off; the

@@ -667,6 +667,133 @@ def ht_1d_vs_control(adata, control, num_boot=10000, num_cpus=1, rng='replay', f
     return df
 
 
+def _label_dummies(m, columns):
+    """Main-effect dummies (first level dropped) of the label columns ``columns`` of ``create_groups``: [group][...] and names."""
+    label_columns = list(m['label_columns'])
+    labels = np.asarray([g.split(m['label_delimiter'])[1:] for g in m['groups']], dtype=object).astype(str)
+    parts, names = [np.ones((len(labels), 0))], []
+    for c in columns:
+        if c not in label_columns:
+            raise ValueError(f"{c!r} is not one of the label columns {label_columns}")
+        dm = pd.get_dummies(pd.Series(labels[:, label_columns.index(c)]), drop_first=True)
+        parts.append(dm.values.astype(np.float64))
+        names.extend(f"{c}={v}" for v in dm.columns)
+    return np.concatenate(parts, axis=1), names
+
+
+def _joint_block(m, block, what):
+    """``treatment`` / ``covariate`` of ``ht_1d_joint`` -> ([group][column] fp64, column names): an array or DataFrame in the group
+    order of ``uns['memento']['groups']``, the name of a label column (treatment) or a list of such names (covariate), or None."""
+    ng = len(m['groups'])
+    if block is None:
+        return np.ones((ng, 0)), []
+    if isinstance(block, str):
+        return _label_dummies(m, [block])
+    if isinstance(block, (list, tuple)) and all(isinstance(c, str) for c in block):
+        return _label_dummies(m, block)
+    names = [str(c) for c in block.columns] if isinstance(block, pd.DataFrame) else None
+    a = np.asarray(block.values if isinstance(block, pd.DataFrame) else block, dtype=np.float64)
+    a = a.reshape(len(a), -1)
+    if a.shape[0] != ng:
+        raise ValueError(f"{what} has {a.shape[0]} rows, there are {ng} groups")
+    return a, names if names is not None else [f"{what}_{j}" for j in range(a.shape[1])]
+
+
+def joint_pvalues(stt, approx=False):
+    """P-values of joint records [test][8] (``Bootstrap1D.joint``).  ``approx=False``: (1 + n_extreme) / (1 + n_valid), never
+    below 1 / (n_valid + 1).  ``approx=True``: the Satterthwaite fit Q* ~ a chi2_nu from the mean m and the population sd s of
+    the valid Q*: a = s^2 / (2 m), nu = 2 m^2 / s^2, p = chi2.sf(Q_0 / a, nu).  NaN where there is no test (NaN record), no valid
+    replicate or every valid Q* is exactly 0 (the replicates all equal the observed column)."""
+    stt = np.asarray(stt, dtype=np.float64)
+    q0, s, n, ext, mean, all_equal = (stt[:, k] for k in range(6))
+    dead = np.isnan(q0) | (n < 1) | (all_equal == 1)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        if approx:
+            p = stats.chi2.sf(q0 / (s ** 2 / (2 * mean)), 2 * mean ** 2 / s ** 2)
+        else:
+            p = (1 + ext) / (1 + n)
+    return np.where(dead, np.nan, p)
+
+
+def ht_1d_joint(adata, treatment, covariate=None, num_boot=10000, rng='replay', fill_seed=0, max_rows=None, approx=False):
+    """Joint bootstrap test of several treatment columns: does the gene differ AT ALL across the levels of a factor (cell types,
+    doses, time points, donors), in mean (``de``) or in variability (``dv``), after the covariates?  One test per kept gene
+    instead of one p-value per dummy column, and the answer does not depend on how the factor is coded.
+
+    ``treatment``: array or DataFrame [groups][T] in the group order of ``uns['memento']['groups']``, or the NAME of a label
+    column of ``create_groups``: the block is then that column's one-hot dummies with the first level dropped.  ``covariate``:
+    array or DataFrame [groups][C], a list of label-column names (main-effect dummies, first level dropped) or None; the
+    intercept is always there.
+
+    On a gene's good groups, with w = Nc / sum(Nc) and D = diag(w), M the residual maker of the weighted fit on
+    [1, covariate] and the thin SVD D^1/2 M treatment = U S V' of rank r (``design.joint_rows``), the statistic of a replicate
+    plane y is Q(y) = ||L y||^2, L = U[:, :r]' D^1/2 M: the weighted sum of squares of the covariate-adjusted log moment that the
+    block explains.  It depends on the column space of the block only (which dummy is dropped, or all dummies given: the same
+    Q) and for one column it is ss * coef^2 of the marginal test of ``ht_1d_moments``.  The null is the centred bootstrap,
+    Q*_c = ||L y_c - L y_0||^2 over the valid replicate columns c >= 1, and
+    p = (1 + #{Q*_c > Q_0}) / (1 + n_valid): never below 1 / (n_valid + 1) (no tail fit here).  ``approx=True`` gives smaller
+    p-values for screens, from the Satterthwaite fit Q* ~ a chi2_nu to the mean and the sd of the Q* (``joint_pvalues``).
+    The statistic is not studentised: the Nc weights already roughly equalise the group variances.
+
+    The bootstrap is that of the other ``ht_*`` calls: ``rng``, ``fill_seed`` and ``max_rows`` as in ``ht_1d_vs_control``, the
+    hash uniforms from the global ``np.random`` stream, refill and ``rng='fast'`` streams keyed as in ``ht_1d_moments`` with the
+    gene numbered over the whole call -- chunking changes no number, and the same ``np.random`` seed and ``max_rows`` give the
+    replicate planes of ``ht_1d_moments``.  Not available on a gene-sharded run (NotImplementedError).
+
+    Returns a DataFrame (gene, df, de_stat, de_pval, dv_stat, dv_pval), df = r; a gene without a design (no good group, or no
+    treatment left after the covariates on its good groups) has df 0 and NaN otherwise.  The arrays go to
+    ``uns['memento']['1d_ht_joint']``: ``mean_stat``, ``mean_asl``, ``var_stat``, ``var_asl``, ``df``, ``n_valid`` and the
+    ``treatment`` / ``covariate`` column names."""
+    _ht.check_args(rng, resampling='bootstrap')
+    m = adata.uns['memento']
+    st = m['_hip']
+    comm = getattr(st, 'comm', None)
+    if comm is not None and comm.world > 1:
+        raise NotImplementedError("ht_1d_joint on a gene-sharded run: the results are not gathered across ranks")
+    trt, trt_names = _joint_block(m, treatment, 'treatment')
+    cov, cov_names = _joint_block(m, covariate, 'covariate')
+    mv = _ht.moments_view(m)
+    ng = mv.ng
+    names = _var_names(adata)
+    G_all = len(st.gene_idx)
+    if st.sf_bin is None:
+        raise NotImplementedError("more than 255 size-factor bins")
+    if max_rows is None:
+        max_rows = engine.auto_max_rows(num_boot + 1, arrays=2)
+    chunk = max(1, int(max_rows) // max(1, ng))
+    # stream keys as in ht_1d_moments: the refill by the gene's position in the unfiltered gene order, rng='fast' by its position
+    # among the kept genes
+    fill_pos = (np.asarray(st.shard, dtype=np.int64)[st.gene_idx] if getattr(st, 'shard', None) is not None
+                else np.asarray(st.gene_idx, dtype=np.int64))
+    cols = {k: [] for k in ('mean_stat', 'mean_asl', 'var_stat', 'var_asl', 'df', 'n_valid')}
+    st.last_bootstrap = st.last_good = None    # (see ht_1d_moments: free the previous call's replicate rows first)
+
+    def run_chunk(c):
+        g0, g1, G, bs, skip = c.g0, c.g1, c.G, c.bs, c.skip
+        r1, r0 = _ht.hash_uniforms(~skip, 2)
+        keys = (fill_pos[g0:g1, None] * ng + np.arange(ng)[None, :]).reshape(-1)
+        chain_keys = np.arange(g0 * ng, g1 * ng, dtype=np.int64)
+        n_inv = bs.run(skip, r1, r0, mv.fit, fill_mode=0, fill_seed=fill_seed, fast=(rng == 'fast'), mean_only=mv.mean_only,
+                       fill_keys=keys, chain_keys=chain_keys)
+        good = ((~skip) & (bs.K >= 2) & ~(n_inv < 0).any(axis=1)).reshape(G, ng)
+        st.last_good = good
+        tables = _ht.joint_tables(good, cov, trt, mv.Nc_list)
+        st.last_joint_tables = tables          # (diagnostics / tests: the designs of the last gene chunk)
+        st_m, st_v = bs.joint(np.arange(G), tables)
+        for tag, stt in (('mean', st_m), ('var', st_v)):
+            cols[tag + '_stat'].append(stt[:, 0])
+            cols[tag + '_asl'].append(joint_pvalues(stt, approx))
+        cols['df'].append(tables.design_rank[tables.test_design].astype(np.int64))
+        cols['n_valid'].append(st_m[:, 2].astype(np.int64))
+
+    for c in _ht.chunks_1d(st, mv, num_boot, chunk):
+        run_chunk(c)
+    out = {k: (np.concatenate(v) if v else np.zeros(0, dtype=np.int64 if k in ('df', 'n_valid') else np.float64)) for k, v in cols.items()}
+    m['1d_ht_joint'] = dict(out, treatment=trt_names, covariate=cov_names)
+    return pd.DataFrame({'gene': names[:G_all], 'df': out['df'], 'de_stat': out['mean_stat'], 'de_pval': out['mean_asl'],
+                         'dv_stat': out['var_stat'], 'dv_pval': out['var_asl']})
+
+
 # ----------------------------------------------------------------------------------------------
 # 2D: compute_2d_moments / ht_2d_moments / get_corr_matrix
 # ----------------------------------------------------------------------------------------------
