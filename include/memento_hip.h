@@ -412,6 +412,19 @@ int mm_joint_stats(const double *d_ym, const double *d_yv, int64_t ld, int32_t n
                    const int32_t *d_test_gene, const int32_t *d_test_design, const int32_t *d_design_ptr,
                    const int32_t *d_design_rank, const int64_t *d_design_lofs, const int32_t *d_design_grp,
                    const double *d_design_L, int64_t n_tests, double *d_stats_mean, double *d_stats_var, void *stream);
+/* The same test on ONE response plane (the replicate correlations of Bootstrap2D, ht_2d_joint): test t applies design
+ * test_design[t] to the rows of row block test_row[t] of d_y [row block][group][ld] (a row block is a pair, in device pair
+ * order) and writes ONE joint record, d_stats [n_tests][8], in the layout above:
+ *   [0] Q_0   [1] population sd of Q*   [2] n_valid   [3] n_extreme   [4] mean of Q*   [5] all_equal   [6] max of Q*   [7] r
+ * Column c is valid only if every listed group is finite there; an unlisted group is never read.  An invalid column 0, an
+ * empty design and r = 0 give the NaN record.  The design tables, the arithmetic and its order, the staging of L and the
+ * trust in the tables are those of mm_joint_stats: the record equals, bit for bit, the mean-plane record of mm_joint_stats
+ * given the plane as both d_ym and d_yv, at one read of every operand and one evaluation of every form.  Needs
+ * n_groups <= 4096 (z_0 and the staged L share 64 KB of LDS). */
+int mm_joint1_stats(const double *d_y, int64_t ld, int32_t num_boot, int32_t n_groups, const int32_t *d_test_row,
+                    const int32_t *d_test_design, const int32_t *d_design_ptr, const int32_t *d_design_rank,
+                    const int64_t *d_design_lofs, const int32_t *d_design_grp, const double *d_design_L, int64_t n_tests,
+                    double *d_stats, void *stream);
 
 /* ---- order statistics of replicate rows (percentile intervals of the coefficients) -------------------------------
  * For every row of d_rows [n_rows][ld]: the replicate columns 1..num_boot (column 0, the observed value, and the padding

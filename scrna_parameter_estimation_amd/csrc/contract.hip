@@ -543,139 +543,204 @@ __global__ __launch_bounds__(256) void k_contrast_design1_rows(const double *__r
 // order.  Two passes that recompute Q* (count / sum / max, then squared deviations and the extreme count): nothing
 // per-replicate is stored.  Up to JOINT_REG_GROUPS groups a thread keeps its column's operands in registers (one read of the
 // planes per pass; instantiated for JOINT_REG_SMALL and for JOINT_REG_GROUPS); beyond, the rows are read again for every form and come back
-// from L1 / L2.
+// from L1 / L2.  The routines take the number of planes NP as a template parameter: k_joint_stats is NP = 2, k_joint1_stats (the
+// correlation plane of ht_2d_joint) NP = 1.
 #define JOINT_LDS_DOUBLES 4096
 #define JOINT_REG_GROUPS 32
-#define JOINT_REG_SMALL 8      // the narrower tier: 84 VGPRs against 182, 2.5x the wider one's speed on designs it holds (profiles/joint_stats.txt)
+#define JOINT_REG_SMALL 8      // the narrower tier: 86 VGPRs against 184, 2.5x the wider one's speed on designs it holds (profiles/joint_stats.txt, profiles/joint1_stats.txt)
 
+// The NP response planes of a test (NP = 2: ym, yv of Bootstrap1D; NP = 1: the correlation rows of Bootstrap2D, mm_joint1_stats)
+template <int NP>
 struct joint_design {
-  const double *ym, *yv;      // the planes, offset to the gene's first row
+  const double *y[NP];        // the planes, offset to the test's first row
   const int32_t *grp;         // [nd]
   int64_t ld;
   int nd, r;
 };
 
-// forms k of column c on both planes: each L element and each operand offset is read once
-template <class LP>
-__device__ __forceinline__ void joint_form(const joint_design &D, LP Lk, int c, double &am, double &av) {
-  am = 0.0;
-  av = 0.0;
+// form k of column c on every plane: each L element and each operand offset is read once
+template <int NP, class LP>
+__device__ __forceinline__ void joint_form(const joint_design<NP> &D, LP Lk, int c, double (&a)[NP]) {
+#pragma unroll
+  for (int j = 0; j < NP; j++) a[j] = 0.0;
   for (int p = 0; p < D.nd; p++) {
     int64_t o = (int64_t)D.grp[p] * D.ld + c;
     double l = Lk[p];
-    am += l * D.ym[o];
-    av += l * D.yv[o];
+#pragma unroll
+    for (int j = 0; j < NP; j++) a[j] += l * D.y[j][o];
   }
 }
 
-__device__ __forceinline__ bool joint_valid(const joint_design &D, int c) {
+template <int NP>
+__device__ __forceinline__ bool joint_valid(const joint_design<NP> &D, int c) {
   bool ok = true;
   for (int p = 0; p < D.nd; p++) {
     int64_t o = (int64_t)D.grp[p] * D.ld + c;
-    ok = ok && isfinite(D.ym[o]) && isfinite(D.yv[o]);
+#pragma unroll
+    for (int j = 0; j < NP; j++) ok = ok && isfinite(D.y[j][o]);
   }
   return ok;
 }
 
-// Q* of column c on both planes into q; returns whether the column is valid.  NDR == 0: any n_d, the operands are read again for
+// Q* of column c on every plane into q; returns whether the column is valid.  NDR == 0: any n_d, the operands are read again for
 // every form and come back from L1 / L2.  NDR > 0 (n_d <= NDR): the column's operands are read ONCE into registers, which also
 // decides its validity, and the forms run on registers and the LDS copy of L.  The arithmetic and its order are those of
-// joint_form either way.  LP: ``const double *`` into LDS (staged) or into global memory; z0m / z0v [r] in LDS.
-template <int NDR, class LP>
-__device__ __forceinline__ bool joint_q(const joint_design &D, LP L, const double *z0m, const double *z0v, int c, double (&q)[2]) {
-  q[0] = q[1] = 0.0;
+// joint_form either way.  LP: ``const double *`` into LDS (staged) or into global memory; z0 [NP][zs] in LDS, r <= zs.
+template <int NDR, int NP, class LP>
+__device__ __forceinline__ bool joint_q(const joint_design<NP> &D, LP L, const double *z0, int zs, int c, double (&q)[NP]) {
+#pragma unroll
+  for (int j = 0; j < NP; j++) q[j] = 0.0;
   if constexpr (NDR == 0) {
     if (!joint_valid(D, c)) return false;
     for (int k = 0; k < D.r; k++) {
-      double am, av;
-      joint_form(D, L + (int64_t)k * D.nd, c, am, av);
-      double dm = am - z0m[k], dv = av - z0v[k];
-      q[0] += dm * dm;
-      q[1] += dv * dv;
+      double a[NP];
+      joint_form(D, L + (int64_t)k * D.nd, c, a);
+#pragma unroll
+      for (int j = 0; j < NP; j++) {
+        double d = a[j] - z0[j * zs + k];
+        q[j] += d * d;
+      }
     }
   } else {
-    double a[NDR], b[NDR];
+    double a[NP][NDR];
     bool ok = true;
 #pragma unroll
     for (int p = 0; p < NDR; p++) {
-      a[p] = b[p] = 0.0;
+#pragma unroll
+      for (int j = 0; j < NP; j++) a[j][p] = 0.0;
       if (p < D.nd) {
         int64_t o = (int64_t)D.grp[p] * D.ld + c;
-        a[p] = D.ym[o];
-        b[p] = D.yv[o];
-        ok = ok && isfinite(a[p]) && isfinite(b[p]);
+#pragma unroll
+        for (int j = 0; j < NP; j++) a[j][p] = D.y[j][o];      // every plane's load is issued before the first value is looked at
+#pragma unroll
+        for (int j = 0; j < NP; j++) ok = ok && isfinite(a[j][p]);
       }
     }
     if (!ok) return false;
     for (int k = 0; k < D.r; k++) {
       LP Lk = L + (int64_t)k * D.nd;
-      double am = 0.0, av = 0.0;
+      double s[NP];
+#pragma unroll
+      for (int j = 0; j < NP; j++) s[j] = 0.0;
 #pragma unroll
       for (int p = 0; p < NDR; p++) {
         if (p < D.nd) {
           double l = Lk[p];
-          am += l * a[p];
-          av += l * b[p];
+#pragma unroll
+          for (int j = 0; j < NP; j++) s[j] += l * a[j][p];
         }
       }
-      double dm = am - z0m[k], dv = av - z0v[k];
-      q[0] += dm * dm;
-      q[1] += dv * dv;
+#pragma unroll
+      for (int j = 0; j < NP; j++) {
+        double d = s[j] - z0[j * zs + k];
+        q[j] += d * d;
+      }
     }
   }
   return true;
 }
 
-// Called by all threads of the workgroup.
-template <int NDR, class LP>
-__device__ __forceinline__ void joint_records(const joint_design &D, LP L, double *z0m, double *z0v, int num_boot, double *stm,
-                                              double *stv, double *red) {
+// Called by all threads of the workgroup.  z0: LDS scratch [NP][zs]; st[j]: the record of plane j.
+template <int NDR, int NP, class LP>
+__device__ __forceinline__ void joint_records(const joint_design<NP> &D, LP L, double *z0, int zs, int num_boot, double *const (&st)[NP],
+                                              double *red) {
   for (int k = threadIdx.x; k < D.r; k += K9_THREADS) {
-    double am, av;
-    joint_form(D, L + (int64_t)k * D.nd, 0, am, av);
-    z0m[k] = am;
-    z0v[k] = av;
+    double a[NP];
+    joint_form(D, L + (int64_t)k * D.nd, 0, a);
+#pragma unroll
+    for (int j = 0; j < NP; j++) z0[j * zs + k] = a[j];
   }
   __syncthreads();
-  double q0[2] = {0.0, 0.0};
+  double q0[NP], q[NP], sum[NP], hi[NP], cnt = 0.0;
+#pragma unroll
+  for (int j = 0; j < NP; j++) { q0[j] = 0.0; sum[j] = 0.0; hi[j] = -INFINITY; }
   for (int k = 0; k < D.r; k++) {
-    q0[0] += z0m[k] * z0m[k];
-    q0[1] += z0v[k] * z0v[k];
+#pragma unroll
+    for (int j = 0; j < NP; j++) q0[j] += z0[j * zs + k] * z0[j * zs + k];
   }
-  double q[2], sum[2] = {0.0, 0.0}, hi[2] = {-INFINITY, -INFINITY}, cnt = 0.0;
   for (int c = 1 + threadIdx.x; c <= num_boot; c += K9_THREADS) {
-    if (!joint_q<NDR>(D, L, z0m, z0v, c, q)) continue;
-    for (int k = 0; k < 2; k++) { sum[k] += q[k]; hi[k] = fmax(hi[k], q[k]); }
+    if (!joint_q<NDR>(D, L, z0, zs, c, q)) continue;
+#pragma unroll
+    for (int j = 0; j < NP; j++) { sum[j] += q[j]; hi[j] = fmax(hi[j], q[j]); }
     cnt += 1.0;
   }
-  double n = wg_sum(cnt, red), mean[2], sq[2] = {0.0, 0.0}, ext[2] = {0.0, 0.0};
-  for (int k = 0; k < 2; k++) {
-    sum[k] = wg_sum(sum[k], red);
-    hi[k] = wg_max(hi[k], red);
-    mean[k] = n > 0 ? sum[k] / n : NAN;
+  double n = wg_sum(cnt, red), mean[NP], sq[NP], ext[NP];
+#pragma unroll
+  for (int j = 0; j < NP; j++) {
+    sum[j] = wg_sum(sum[j], red);
+    hi[j] = wg_max(hi[j], red);
+    mean[j] = n > 0 ? sum[j] / n : NAN;
+    sq[j] = 0.0;
+    ext[j] = 0.0;
   }
   for (int c = 1 + threadIdx.x; c <= num_boot; c += K9_THREADS) {
-    if (!joint_q<NDR>(D, L, z0m, z0v, c, q)) continue;
-    for (int k = 0; k < 2; k++) {
-      double d = q[k] - mean[k];
-      sq[k] += d * d;
-      if (q[k] > q0[k]) ext[k] += 1.0;
+    if (!joint_q<NDR>(D, L, z0, zs, c, q)) continue;
+#pragma unroll
+    for (int j = 0; j < NP; j++) {
+      double d = q[j] - mean[j];
+      sq[j] += d * d;
+      if (q[j] > q0[j]) ext[j] += 1.0;
     }
   }
-  for (int k = 0; k < 2; k++) { sq[k] = wg_sum(sq[k], red); ext[k] = wg_sum(ext[k], red); }
+#pragma unroll
+  for (int j = 0; j < NP; j++) { sq[j] = wg_sum(sq[j], red); ext[j] = wg_sum(ext[j], red); }
   if (threadIdx.x == 0) {
-    for (int k = 0; k < 2; k++) {
-      double *s = k ? stv : stm;
-      s[0] = q0[k];
-      s[1] = n > 0 ? sqrt(sq[k] / n) : NAN;
+#pragma unroll
+    for (int j = 0; j < NP; j++) {
+      double *s = st[j];
+      s[0] = q0[j];
+      s[1] = n > 0 ? sqrt(sq[j] / n) : NAN;
       s[2] = n;
-      s[3] = ext[k];
-      s[4] = mean[k];
-      s[5] = (n > 0 && hi[k] == 0.0) ? 1.0 : 0.0;
-      s[6] = n > 0 ? hi[k] : NAN;
+      s[3] = ext[j];
+      s[4] = mean[j];
+      s[5] = (n > 0 && hi[j] == 0.0) ? 1.0 : 0.0;
+      s[6] = n > 0 ? hi[j] : NAN;
       s[7] = (double)D.r;
     }
   }
+}
+
+// One workgroup = one test, on NP planes: the designs, the NaN records, the staging of L and the column-0 check that the
+// two kernels below share.  y[j]: plane j; st[j]: record j of this test; sm: LDS [NP * n_groups + stage_cap].
+template <int NDR, int NP>
+__device__ __forceinline__ void joint_test(const double *const (&y)[NP], int64_t ld, int32_t num_boot, int32_t n_groups, int32_t stage_cap,
+                                           int row, int d, const int32_t *__restrict__ design_ptr, const int32_t *__restrict__ design_rank,
+                                           const int64_t *__restrict__ design_lofs, const int32_t *__restrict__ design_grp,
+                                           const double *__restrict__ design_L, double *const (&st)[NP], double *sm, double *red) {
+  double *z0 = sm, *Ls = sm + NP * (int64_t)n_groups;      // [NP][n_groups], [stage_cap]
+  int p0 = design_ptr[d], p1 = design_ptr[d + 1];
+  joint_design<NP> D;
+  D.nd = p1 - p0;
+  D.r = design_rank[d];
+  if (D.nd <= 0 || D.r <= 0 || D.r > n_groups || (NDR > 0 && D.nd > NDR)) {
+#pragma unroll
+    for (int j = 0; j < NP; j++) write_nan_record(st[j]);
+    return;
+  }
+  D.ld = ld;
+  D.grp = design_grp + p0;
+#pragma unroll
+  for (int j = 0; j < NP; j++) D.y[j] = y[j] + (int64_t)row * n_groups * ld;
+  const double *Lg = design_L + design_lofs[d];
+  const int n_l = D.r * D.nd;                       // <= n_groups^2 < 2^31 (checked by the caller)
+  const bool staged = n_l <= stage_cap;
+  if (staged)
+    for (int i = threadIdx.x; i < n_l; i += K9_THREADS) Ls[i] = Lg[i];
+  double ok0 = 1.0;                                 // column 0: every listed group finite in every plane?
+  for (int p = threadIdx.x; p < D.nd; p += K9_THREADS) {
+    int64_t o = (int64_t)D.grp[p] * ld;
+#pragma unroll
+    for (int j = 0; j < NP; j++)
+      if (!isfinite(D.y[j][o])) ok0 = 0.0;
+  }
+  ok0 = wg_min(ok0, red);                           // (its barriers also publish Ls)
+  if (ok0 == 0.0) {
+#pragma unroll
+    for (int j = 0; j < NP; j++) write_nan_record(st[j]);
+    return;
+  }
+  if (staged) joint_records<NDR>(D, (const double *)Ls, z0, n_groups, num_boot, st, red);
+  else joint_records<NDR>(D, Lg, z0, n_groups, num_boot, st, red);
 }
 
 // NDR: 0, or a bound on n_groups (and so on every n_d) that lets a column's operands live in registers (joint_q)
@@ -688,42 +753,33 @@ __global__ __launch_bounds__(K9_THREADS) void k_joint_stats(const double *__rest
                                                             const double *__restrict__ design_L, double *__restrict__ stats_m,
                                                             double *__restrict__ stats_v) {
   extern __shared__ double sm[];
-  double *z0m = sm, *z0v = sm + n_groups, *Ls = sm + 2 * (int64_t)n_groups;   // [n_groups], [n_groups], [stage_cap]
   __shared__ double red[K9_THREADS / 64];
   int64_t t = blockIdx.x;
-  int gene = test_gene[t], d = test_design[t];
-  int p0 = design_ptr[d], p1 = design_ptr[d + 1];
-  double *stm = stats_m + t * 8, *stv = stats_v + t * 8;
-  joint_design D;
-  D.nd = p1 - p0;
-  D.r = design_rank[d];
-  if (D.nd <= 0 || D.r <= 0 || D.r > n_groups || (NDR > 0 && D.nd > NDR)) {
-    write_nan_record(stm);
-    write_nan_record(stv);
-    return;
-  }
-  D.ld = ld;
-  D.grp = design_grp + p0;
-  D.ym = ym + (int64_t)gene * n_groups * ld;
-  D.yv = yv + (int64_t)gene * n_groups * ld;
-  const double *Lg = design_L + design_lofs[d];
-  const int n_l = D.r * D.nd;                       // <= n_groups^2 < 2^31 (checked by the caller)
-  const bool staged = n_l <= stage_cap;
-  if (staged)
-    for (int i = threadIdx.x; i < n_l; i += K9_THREADS) Ls[i] = Lg[i];
-  double ok0 = 1.0;                                 // column 0: every listed group finite in both planes?
-  for (int p = threadIdx.x; p < D.nd; p += K9_THREADS) {
-    int64_t o = (int64_t)D.grp[p] * ld;
-    if (!(isfinite(D.ym[o]) && isfinite(D.yv[o]))) ok0 = 0.0;
-  }
-  ok0 = wg_min(ok0, red);                           // (its barriers also publish Ls)
-  if (ok0 == 0.0) {
-    write_nan_record(stm);
-    write_nan_record(stv);
-    return;
-  }
-  if (staged) joint_records<NDR>(D, (const double *)Ls, z0m, z0v, num_boot, stm, stv, red);
-  else joint_records<NDR>(D, Lg, z0m, z0v, num_boot, stm, stv, red);
+  const double *const y[2] = {ym, yv};
+  double *const st[2] = {stats_m + t * 8, stats_v + t * 8};
+  joint_test<NDR, 2>(y, ld, num_boot, n_groups, stage_cap, test_gene[t], test_design[t], design_ptr, design_rank, design_lofs, design_grp,
+                     design_L, st, sm, red);
+}
+
+// The joint test on ONE response plane (the replicate correlations of Bootstrap2D, ht_2d_joint): test t applies the forms of
+// design test_design[t] to the rows of pair test_row[t] and writes one joint record.  The routines, the arithmetic and its
+// order are those of k_joint_stats, instantiated for one plane: the record is, bit for bit, the mean-plane record of
+// k_joint_stats given the plane twice, but every operand is read once, every form evaluated once and -- in the register tiers --
+// one operand array is held, not two (profiles/joint1_stats.txt).
+template <int NDR>
+__global__ __launch_bounds__(K9_THREADS) void k_joint1_stats(const double *__restrict__ y, int64_t ld, int32_t num_boot, int32_t n_groups,
+                                                             int32_t stage_cap, const int32_t *__restrict__ test_row,
+                                                             const int32_t *__restrict__ test_design, const int32_t *__restrict__ design_ptr,
+                                                             const int32_t *__restrict__ design_rank, const int64_t *__restrict__ design_lofs,
+                                                             const int32_t *__restrict__ design_grp, const double *__restrict__ design_L,
+                                                             double *__restrict__ stats) {
+  extern __shared__ double sm[];
+  __shared__ double red[K9_THREADS / 64];
+  int64_t t = blockIdx.x;
+  const double *const yp[1] = {y};
+  double *const st[1] = {stats + t * 8};
+  joint_test<NDR, 1>(yp, ld, num_boot, n_groups, stage_cap, test_row[t], test_design[t], design_ptr, design_rank, design_lofs, design_grp,
+                     design_L, st, sm, red);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -981,6 +1037,24 @@ int mm_joint_stats(const double *d_ym, const double *d_yv, int64_t ld, int32_t n
   hipLaunchKernelGGL(kernel, dim3((unsigned)n_tests), dim3(K9_THREADS), shm, (hipStream_t)stream, d_ym, d_yv, ld, num_boot, n_groups,
                      (int32_t)cap, d_test_gene, d_test_design, d_design_ptr, d_design_rank, d_design_lofs, d_design_grp, d_design_L,
                      d_stats_mean, d_stats_var);
+  MM_LAUNCH_CHECK();
+  return MM_OK;
+}
+
+int mm_joint1_stats(const double *d_y, int64_t ld, int32_t num_boot, int32_t n_groups, const int32_t *d_test_row,
+                    const int32_t *d_test_design, const int32_t *d_design_ptr, const int32_t *d_design_rank,
+                    const int64_t *d_design_lofs, const int32_t *d_design_grp, const double *d_design_L, int64_t n_tests,
+                    double *d_stats, void *stream) {
+  MM_ARG(d_y && d_test_row && d_test_design && d_design_ptr && d_design_rank && d_design_lofs && d_design_grp && d_design_L && d_stats);
+  MM_ARG(n_tests >= 0 && n_tests < 2147483647LL && n_groups > 0 && num_boot > 0 && ld >= (int64_t)num_boot + 1);
+  // as mm_joint_stats, with z_0 of one plane: n_groups doubles, and the staged L at most JOINT_LDS_DOUBLES
+  int64_t cap = (int64_t)n_groups * n_groups < JOINT_LDS_DOUBLES ? (int64_t)n_groups * n_groups : JOINT_LDS_DOUBLES;
+  size_t shm = ((size_t)n_groups + (size_t)cap) * 8;
+  MM_ARG(shm <= 64 * 1024);
+  if (n_tests == 0) return MM_OK;
+  auto kernel = n_groups <= JOINT_REG_SMALL ? k_joint1_stats<JOINT_REG_SMALL> : n_groups <= JOINT_REG_GROUPS ? k_joint1_stats<JOINT_REG_GROUPS> : k_joint1_stats<0>;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)n_tests), dim3(K9_THREADS), shm, (hipStream_t)stream, d_y, ld, num_boot, n_groups, (int32_t)cap,
+                     d_test_row, d_test_design, d_design_ptr, d_design_rank, d_design_lofs, d_design_grp, d_design_L, d_stats);
   MM_LAUNCH_CHECK();
   return MM_OK;
 }

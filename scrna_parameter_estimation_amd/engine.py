@@ -1123,9 +1123,10 @@ def _design_tables(test_row, test_design, design_ptr, design_grp, design_w, n_ro
 
 
 def _joint_tables(test_gene, tables, n_rows, ng):
-    """The tables of mm_joint_stats (``Bootstrap1D.joint``), coerced, checked (the kernel trusts them) and uploaded, empty arrays
-    padded to one element: every design has 0 <= rank <= n_d <= ``ng`` groups, all in [0, ng), and rank x n_d doubles of
-    ``design_L`` at its offset; every test names a gene slot < ``n_rows`` and a design.  Returns test_gene as an int32 host array
+    """The tables of mm_joint_stats / mm_joint1_stats (``Bootstrap1D.joint``, ``Bootstrap2D.joint``), coerced, checked (the kernels
+    trust them) and uploaded, empty arrays padded to one element: every design has 0 <= rank <= n_d <= ``ng`` groups, all in
+    [0, ng), and rank x n_d doubles of ``design_L`` at its offset; every test names a row block (a gene slot or a pair)
+    < ``n_rows`` and a design.  Returns test_gene as an int32 host array
     and the device tensors (test_gene, test_design, design_ptr, design_rank, design_lofs, design_grp, design_L), the order in
     which the kernel takes them."""
     test_gene = np.asarray(test_gene, dtype=np.int32)
@@ -1439,3 +1440,15 @@ class Bootstrap2D:
             return host(out)[: len(idx)] if to_host else out[: len(idx)]
 
         return host(stats)[:n_tests], rows
+
+    def joint(self, test_pair, tables):
+        """Joint tests of a treatment block on the correlation rows (mm_joint1_stats): test t applies the linear forms of design
+        ``tables.test_design[t]`` (``memento._ht.joint_tables``, as for ``Bootstrap1D.joint``) to the replicate rows of pair
+        ``test_pair[t]`` (device pair order, ``self.order``).  Returns stats, a host array [n_tests][8]: the joint record of
+        include/memento_hip.h."""
+        torch = _torch()
+        test_pair, d_tab = _joint_tables(test_pair, tables, self.n_pairs, self.ng)
+        n_tests = len(test_pair)
+        stats = empty((max(1, n_tests), 8), torch.float64)
+        _lib.call("mm_joint1_stats", P(self.yc), self.ld, self.B, self.ng, *map(P, d_tab), n_tests, P(stats), _stream())
+        return host(stats)[:n_tests]

@@ -205,10 +205,10 @@ def pair_design_tables(good, tcol, per_gene, cov, trt, Nc, resampled=False):
 
 
 def joint_tables(good, cov, trt, Nc):
-    """The designs of the joint test (``design.joint_rows``) of a chunk: row ``k`` of ``good`` [rows][groups] (a gene) is tested
-    once, on its good groups; one design per distinct good mask, shared by the rows that have it.
+    """The designs of the joint test (``design.joint_rows``) of a chunk: row ``k`` of ``good`` [rows][groups] (a gene or a pair) is
+    tested once, on its good groups; one design per distinct good mask, shared by the rows that have it.
 
-    -> ``test_design`` [row] and the CSR-like tables the kernel takes (``Bootstrap1D.joint``): ``design_ptr`` [design + 1] into
+    -> ``test_design`` [row] and the CSR-like tables the kernels take (``Bootstrap1D.joint``, ``Bootstrap2D.joint``): ``design_ptr`` [design + 1] into
     ``design_grp`` (every good group of the mask, ascending), ``design_rank`` [design], ``design_lofs`` [design] (int64 offset
     into ``design_L``) and ``design_L`` (row-major rank x n_d per design: the columns of L on the good groups)."""
     good = np.asarray(good, dtype=bool)

@@ -1067,6 +1067,61 @@ def ht_2d_vs_control(adata, control, num_boot=10000, num_cpus=1, fill_seed=0, ma
     return df
 
 
+def ht_2d_joint(adata, treatment, covariate=None, num_boot=10000, rng='replay', fill_seed=0, max_rows=None, approx=False):
+    """Joint bootstrap test of several treatment columns on COEXPRESSION: does the correlation of a gene pair differ AT ALL
+    across the levels of a factor (cell types, doses, time points, donors), after the covariates?  One test per pair of
+    ``compute_2d_moments`` instead of one p-value per dummy column, and the answer does not depend on how the factor is coded.
+
+    ``treatment`` / ``covariate`` exactly as in ``ht_1d_joint``: an array or DataFrame [groups][columns] in the group order of
+    ``uns['memento']['groups']``, the name of a label column of ``create_groups`` (its dummies, first level dropped), a list of
+    such names, or None; the intercept is always there.
+
+    The statistic is the one of ``ht_1d_joint`` with y the RAW replicate correlations of the pair (no log, no Fisher
+    transform: the quantity ``ht_2d_moments`` regresses): on the pair's good groups L = ``design.joint_rows`` with the cell
+    counts ``ht_2d_moments`` gives its designs, Q_0 = ||L y_0||^2, the null Q*_c = ||L y_c - L y_0||^2 over the valid replicate
+    columns c >= 1 (mm_joint1_stats) and p from ``joint_pvalues``: (1 + #{Q*_c > Q_0}) / (1 + n_valid), or the Satterthwaite
+    fit with ``approx=True``.  For one treatment column Q_0 is ss * corr_coef^2 of the marginal test of ``ht_2d_moments``.
+
+    Pairs and the random stream are those of ``ht_2d_moments`` / ``ht_2d_vs_control``: unordered duplicates share the first
+    one's result, a self pair stays NaN with df 0, a (pair, group) with a NaN or +-1 correlation is skipped and the pair tested
+    on its remaining good groups with the rank that design has; three hash uniforms per live (pair, group) are taken from the
+    global ``np.random`` stream, pair-major, up front; ``rng='fast'`` streams are keyed by the pair's position among the
+    distinct tested pairs.  The same ``np.random`` seed and ``max_rows`` give the replicate rows of ``ht_2d_moments``, and
+    chunking changes no number under either generator.
+
+    Returns a DataFrame (gene_1, gene_2, df, corr_stat, corr_pval), one row per requested pair in the order of
+    ``compute_2d_moments``, df = r; a pair without a design (no good group, or no treatment left after the covariates on its
+    good groups) has df 0 and NaN otherwise.  The arrays go to ``uns['memento']['2d_ht_joint']``: ``corr_stat``, ``corr_asl``,
+    ``df``, ``n_valid`` and the ``treatment`` / ``covariate`` column names."""
+    _ht.check_args(rng, resampling='bootstrap')
+    m = adata.uns['memento']
+    st = m['_hip']
+    st.last_bootstrap2d = None                 # (free the previous call's replicate rows before this call allocates its own)
+    trt, trt_names = _joint_block(m, treatment, 'treatment')
+    cov, cov_names = _joint_block(m, covariate, 'covariate')
+    Nc_list = np.array([m['group_cells'][g].shape[0] for g in m['groups']], dtype=np.float64)
+    plan = _ht.pair_plan(m, st, num_boot, max_rows)
+    uniforms = _ht.hash_uniforms(~plan.skip.reshape(-1), 3)
+    out = {'corr_stat': np.full(plan.n_conv, np.nan), 'corr_asl': np.full(plan.n_conv, np.nan),
+           'df': np.zeros(plan.n_conv, dtype=np.int64), 'n_valid': np.zeros(plan.n_conv, dtype=np.int64)}
+
+    def run_chunk(c):
+        good = _ht.run_chunk_2d(c, plan, uniforms, rng, fill_seed)                 # device order
+        tables = _ht.joint_tables(good, cov, trt, Nc_list)
+        st.last_joint_tables = tables          # (diagnostics / tests: the designs of the last pair chunk)
+        stt = c.bs.joint(np.arange(c.n_ch), tables)
+        for key, src in (('corr_stat', stt[:, 0]), ('corr_asl', joint_pvalues(stt, approx)),
+                         ('df', tables.design_rank[tables.test_design].astype(np.int64)), ('n_valid', stt[:, 2].astype(np.int64))):
+            _ht.scatter_pairs(c, plan, out[key], src)
+
+    for c in _ht.chunks_2d(st, plan, num_boot):
+        run_chunk(c)
+    m['2d_ht_joint'] = dict(out, treatment=trt_names, covariate=cov_names)
+    pairs = list(m['2d_moments']['gene_pairs'])
+    return pd.DataFrame({'gene_1': [a for a, _ in pairs], 'gene_2': [b for _, b in pairs], 'df': out['df'],
+                         'corr_stat': out['corr_stat'], 'corr_pval': out['corr_asl']})
+
+
 # ----------------------------------------------------------------------------------------------
 # getters
 # ----------------------------------------------------------------------------------------------

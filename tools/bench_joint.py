@@ -9,7 +9,13 @@ Part 1, synthetic replicate planes (--genes x --groups rows of B + 1 normal valu
 HIP events around back-to-back launches after a warm-up, median of three passes.
 Part 2 (skipped with --no-call; --no-kernels skips part 1): a synthetic count matrix with --groups groups (levels x 4 replicates), one ht_1d_joint call timed by
 the host clock around a device synchronise, and mm_joint_stats alone on that call's last chunk and designs.
-usage: python tools/bench_joint.py [--genes 2000] [--groups 20] [--boot 10000] [--ranks 4,19] [--cells 100000] [--no-call] [--no-kernels]"""
+One-plane mode (--one-plane; nothing else runs): ONE synthetic plane of --genes row blocks (the pairs of ht_2d_joint) x --groups rows,
+the designs of part 1, and for every rank
+  * mm_joint1_stats on the plane: one record per test;
+  * mm_joint_stats given that plane as both of its planes -- the only way to run the test without the one-plane kernel: the baseline.
+Timed as in part 1.  n_groups chooses the instantiation: <8> up to 8 groups, <32> up to 32, <0> beyond.
+usage: python tools/bench_joint.py [--genes 2000] [--groups 20] [--boot 10000] [--ranks 4,19] [--cells 100000] [--no-call] [--no-kernels]
+                                   [--one-plane]"""
 import ctypes, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, pandas as pd, torch, scipy.sparse as sp
@@ -92,6 +98,32 @@ def kernels(genes, groups, B, ranks):
     del bs
 
 
+def one_plane(pairs, groups, B, ranks):
+    ld = B + 1
+    gen = torch.Generator(device="cuda").manual_seed(1)
+    y = torch.tanh(0.6 * torch.randn((pairs * groups, ld), dtype=torch.float64, device="cuda", generator=gen))
+    two = object.__new__(engine.Bootstrap1D)
+    two.ym, two.yv, two.ld, two.B, two.ng, two.n_tested = y, y, ld, B, groups, pairs
+    Nc = np.random.default_rng(2).integers(200, 3000, size=groups).astype(np.float64)
+    good = np.ones((pairs, groups), dtype=bool)
+    tier = 8 if groups <= 8 else 32 if groups <= 32 else 0
+    print(f"plane: {pairs} pairs x {groups} groups x {ld} columns, {y.numel() * 8 / 1e9:.2f} GB; instantiation <{tier}>", flush=True)
+    for r in ranks:
+        levels = np.arange(groups) % (r + 1)
+        trt = np.stack([(levels == v).astype(np.float64) for v in range(1, r + 1)], axis=1)
+        tables = _ht.joint_tables(good, np.ones((groups, 0)), trt, Nc)
+        assert list(tables.design_rank) == [r]
+        test_pair, d_tab = engine._joint_tables(np.arange(pairs), tables, pairs, groups)
+        stats = engine.empty((pairs, 8), torch.float64)
+        args = [engine.P(y), ld, B, groups, *map(engine.P, d_tab), pairs, engine.P(stats), engine._stream()]
+        t_one, p_one = _events(lambda: _lib.call("mm_joint1_stats", *args), reps=5)
+        launch, keep = _joint_launch(two, np.arange(pairs), tables)
+        t_two, p_two = _events(launch, reps=5)
+        print(f"r = {r}: mm_joint1_stats {t_one:.3f} ms (passes {[round(x, 3) for x in p_one]}), {2 * y.numel() * 8 / t_one / 1e9:.2f} TB/s over its two "
+              f"passes; mm_joint_stats with the plane twice {t_two:.3f} ms (passes {[round(x, 3) for x in p_two]}); ratio {t_two / t_one:.2f}", flush=True)
+        del keep, launch, stats, d_tab
+
+
 def one_call(cells, genes, groups, B):
     import bench
 
@@ -129,6 +161,8 @@ def main():
     cells = _opt("--cells", 100_000)
     no_call, no_kernels = "--no-call" in sys.argv, "--no-kernels" in sys.argv
     engine._lib.load(require_gpu=True)
+    if "--one-plane" in sys.argv:
+        return one_plane(genes, groups, B, ranks)
     if not no_kernels:
         kernels(genes, groups, B, ranks)
     if not no_call:
