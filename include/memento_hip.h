@@ -349,25 +349,18 @@ int mm_cross_resampled(const double *d_yt, int64_t ld, int32_t num_boot, int32_t
                        const int32_t *d_col_map, const int32_t *d_n_valid, uint64_t seed, int64_t n_tests, double *d_coef,
                        double *d_stats, void *stream);
 
-/* ---- two-group contrasts against a shared control (Perturb-seq batching) ---------------------
- * test t: coef_b = y[test_gene[t], test_grp[t]][b] - y[test_gene[t], ctrl][b] -- what _regress_1d computes for the two
- * groups {control, guide} with a binary treatment (hypothesis_test.py:269-291); the control's bootstrap is shared by all
- * guides instead of being recomputed per guide as in the reference's per-guide loop.  stats layout as mm_contract_stats,
- * for the mean and the variability response in one launch; nothing per-replicate is stored.  A column counts only if all four
- * operands (guide and control, mean and variability) are finite; if column 0 does not, coef0 is NaN on both planes. */
-int mm_contrast_stats(const double *d_ym, const double *d_yv, int64_t ld, int32_t num_boot, int32_t n_groups, int32_t ctrl,
-                      const int32_t *d_test_gene, const int32_t *d_test_grp, const uint8_t *d_good, int64_t n_tests,
-                      double *d_stats_mean, double *d_stats_var, void *stream);
-/* coefficient rows [n_tests][ld] of selected contrasts (NaN where a replicate column is dropped) for the tail fits */
-int mm_contrast_rows(const double *d_ym, const double *d_yv, int64_t ld, int32_t num_boot, int32_t n_groups, int32_t ctrl,
-                     const int32_t *d_test_gene, const int32_t *d_test_grp, int64_t n_tests, int32_t which, double *d_out,
-                     void *stream);
-/* ---- guide-vs-control contrasts with covariates (replicate / well / dose strata) ------------------------------
+/* ---- guide-vs-control contrasts: sparse weight rows over the replicate groups ------------------------------------
  * test t: coef_c = sum_p design_w[p] * y[test_gene[t], design_grp[p]][c] over p in [design_ptr[d], design_ptr[d + 1]),
  * d = test_design[t] -- the per-guide weighted regression of _regress_1d (hypothesis_test.py:242-300) on the guide's and
  * the control's stratum groups, folded into one sparse weight row per design (memento/design.py).  Column c counts only
- * if the mean and the variability rows of every listed group are finite there.  An empty design gives a NaN test.
- * stats layout as mm_contrast_stats, mean and variability response in one launch. */
+ * if the mean and the variability rows of every listed group are finite there; if column 0 does not, coef0 is NaN on both
+ * planes.  An empty design gives a NaN test.  stats layout as mm_contract_stats, for the mean and the variability response in
+ * one launch; nothing per-replicate is stored.
+ * The plain two-group test against a shared control (Perturb-seq batching) is the two-entry design
+ * {(guide, +1.0), (control, -1.0)}: coef_b = y[gene, guide][b] - y[gene, control][b] -- what _regress_1d computes for the two
+ * groups {control, guide} with a binary treatment (hypothesis_test.py:269-291); the control's bootstrap is shared by all guides
+ * instead of being recomputed per guide as in the reference's per-guide loop.  The sums are unfused and start from 0.0, so
+ * the coefficient is that difference bit for bit, an exact zero always being +0.0 (engine._contrast builds these tables). */
 int mm_contrast_design_stats(const double *d_ym, const double *d_yv, int64_t ld, int32_t num_boot, int32_t n_groups,
                              const int32_t *d_test_gene, const int32_t *d_test_design, const int32_t *d_design_ptr,
                              const int32_t *d_design_grp, const double *d_design_w, int64_t n_tests, double *d_stats_mean,
@@ -383,7 +376,7 @@ int mm_contrast_design_rows(const double *d_ym, const double *d_yv, int64_t ld, 
  * d_test_row[t], coef_c = sum_p d_design_w[p] * y[d_test_row[t] * n_groups + d_design_grp[p]][c].  A plain two-group
  * test is the design {(guide, +1), (control, -1)}; an empty design gives a NaN test.  Column c counts only if every
  * listed group is finite there.  The index tables are trusted: validate them on the host.  d_stats [n_tests][8], layout
- * as mm_contrast_stats. */
+ * as mm_contract_stats. */
 int mm_contrast_design1_stats(const double *d_y, int64_t ld, int32_t num_boot, int32_t n_groups, const int32_t *d_test_row,
                               const int32_t *d_test_design, const int32_t *d_design_ptr, const int32_t *d_design_grp,
                               const double *d_design_w, int64_t n_tests, double *d_stats, void *stream);

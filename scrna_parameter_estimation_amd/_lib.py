@@ -76,10 +76,6 @@ _SIGS = {
                                                                       c_int32, c_void_p], ctypes.c_int),
     "mm_boot_fill_log": ([c_void_p, c_void_p, c_int64, c_int64, c_int32, ctypes.POINTER(c_double), c_int32, c_uint64,
                           c_void_p, c_void_p, c_void_p], ctypes.c_int),
-    "mm_contrast_stats": ([c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
-                           c_void_p], ctypes.c_int),
-    "mm_contrast_rows": ([c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p],
-                         ctypes.c_int),
     "mm_contrast_design_stats": ([c_void_p, c_void_p, c_int64, c_int32, c_int32] + [c_void_p] * 5 + [c_int64, c_void_p, c_void_p, c_void_p],
                                  ctypes.c_int),
     "mm_contrast_design_rows": ([c_void_p, c_void_p, c_int64, c_int32, c_int32] + [c_void_p] * 5 + [c_int64, c_int32, c_void_p, c_void_p],

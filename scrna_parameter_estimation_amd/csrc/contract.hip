@@ -356,63 +356,22 @@ __global__ __launch_bounds__(K9_THREADS) void k_cross_resampled(const double *__
 }
 
 // ------------------------------------------------------------------------------------------------
-// Two-group contrasts against a shared control (Perturb-seq style, BASELINE config 5): test t compares group
-// test_grp[t] with the control group of gene test_gene[t]:  coef_b = y[gene, grp][b] - y[gene, ctrl][b]
-// (the weighted slope of _cross_coef for two groups and a binary treatment, hypothesis_test.py:218-228, reduces to this
-// difference).  The control's bootstrap rows are computed once and shared by every guide.  Nothing per-replicate is
-// stored: both passes recompute the difference from the resident replicate rows.  One launch does mean and variance.
-__global__ __launch_bounds__(K9_THREADS) void k_contrast_stats(const double *__restrict__ ym, const double *__restrict__ yv,
-                                                               int64_t ld, int32_t num_boot, int32_t n_groups, int32_t ctrl,
-                                                               const int32_t *__restrict__ test_gene, const int32_t *__restrict__ test_grp,
-                                                               const uint8_t *__restrict__ good, double *__restrict__ stats_m,
-                                                               double *__restrict__ stats_v) {
-  __shared__ double red[K9_THREADS / 64];
-  int64_t t = blockIdx.x;
-  int gene = test_gene[t], grp = test_grp[t];
-  double *const st[2] = {stats_m + t * 8, stats_v + t * 8};
-  const uint8_t *gd = good + (int64_t)gene * n_groups;
-  if (!gd[grp] || !gd[ctrl]) {
-    write_nan_record(st[0]);
-    write_nan_record(st[1]);
-    return;
-  }
-  const double *ma = ym + ((int64_t)gene * n_groups + grp) * ld, *mc = ym + ((int64_t)gene * n_groups + ctrl) * ld;
-  const double *va = yv + ((int64_t)gene * n_groups + grp) * ld, *vc = yv + ((int64_t)gene * n_groups + ctrl) * ld;
-  auto coef_at = [&](int c, double(&v)[2]) {
-    double a = ma[c], b = mc[c], p = va[c], q = vc[c];
-    bool ok = isfinite(a) && isfinite(b) && isfinite(p) && isfinite(q);
-    v[0] = ok ? a - b : NAN;   // as k_contrast_rows: an invalid column 0 gives coef0 = NaN on both planes
-    v[1] = ok ? p - q : NAN;
-    return ok;
-  };
-  fill_records<2, false>(coef_at, num_boot + 1, nullptr, st, red);
-}
-
-// coefficient rows of selected contrasts (for the host-side tail fits of the few tests that need them)
-__global__ __launch_bounds__(256) void k_contrast_rows(const double *__restrict__ ym, const double *__restrict__ yv, int64_t ld,
-                                                       int32_t num_boot, int32_t n_groups, int32_t ctrl,
-                                                       const int32_t *__restrict__ test_gene, const int32_t *__restrict__ test_grp,
-                                                       int32_t which, double *__restrict__ out) {
-  int64_t t = blockIdx.x;
-  int gene = test_gene[t], grp = test_grp[t];
-  const double *ma = ym + ((int64_t)gene * n_groups + grp) * ld, *mc = ym + ((int64_t)gene * n_groups + ctrl) * ld;
-  const double *va = yv + ((int64_t)gene * n_groups + grp) * ld, *vc = yv + ((int64_t)gene * n_groups + ctrl) * ld;
-  for (int c = threadIdx.x; c <= num_boot; c += 256) {
-    double a = ma[c], b = mc[c], p = va[c], q = vc[c];
-    bool ok = isfinite(a) && isfinite(b) && isfinite(p) && isfinite(q);
-    out[t * ld + c] = ok ? (which ? p - q : a - b) : NAN;
-  }
-}
-
-// ------------------------------------------------------------------------------------------------
-// Guide-vs-control contrasts with covariates (replicate / well / dose strata): test t applies the sparse weight row of
-// design test_design[t] -- the per-guide weighted regression of _regress_1d (hypothesis_test.py:242-300) on the guide's and
-// the control's stratum groups, folded into weights by memento/design.py -- to the resident replicate rows of gene
-// test_gene[t]:  coef_c = sum_p design_w[p] * y[gene, design_grp[p]][c]  for p in [design_ptr[d], design_ptr[d + 1]).
-// Column c is valid only if the mean AND the variability rows of every listed group are finite there (:249-251; groups with
-// a ~0 weight included).  An empty design (no good guide or control group, or no stratum holding both arms) gives the NaN
-// record.  One workgroup per test; the coefficient is recomputed in the second pass instead of being
-// stored (a test reads 2 x |groups| rows; the control rows are shared by the gene's consecutive tests through L2 / MALL).
+// Guide-vs-control contrasts (ht_1d_vs_control, ht_2d_vs_control): test t applies the sparse weight row of design
+// d = test_design[t] to the replicate rows of row block test_row[t] (a gene slot, or a pair of Bootstrap2D) on NP response planes:
+//   coef_c = sum_p design_w[p] * y[test_row[t] * n_groups + design_grp[p]][c]  for p in [design_ptr[d], design_ptr[d + 1]).
+// With covariates (replicate / well / dose strata) the row is the per-guide weighted regression of _regress_1d
+// (hypothesis_test.py:242-300) on the guide's and the control's stratum groups, folded into weights by memento/design.py.  The
+// plain two-group test against a shared control (BASELINE config 5; the weighted slope of _cross_coef for two groups and a binary
+// treatment, hypothesis_test.py:218-228) is the design {(guide, +1), (control, -1)}: the library is built with -ffp-contract=off,
+// so design_coef forms (0.0 + 1.0 * a) + (-1.0 * b), which is a - b bit for bit except that an exact zero is always +0.0 -- and no
+// count, flag or comparison of the record sees the sign of a zero.  The control's bootstrap rows are computed once and shared by
+// every guide.
+// Column c is valid only if every listed group is finite there in EVERY plane (:249-251, :372-373; groups with a ~0 weight
+// included): one verdict for all planes.  An empty design (no good guide or control group, or no stratum holding both arms) gives
+// the NaN record.  One workgroup per test; the coefficient is recomputed in the second pass instead of being stored (a test reads
+// 2 x |design| rows; the control rows are shared by a row block's consecutive tests through L2 / MALL).  The routines take the
+// number of planes NP as a template parameter: k_contrast_design_* is NP = 2 (ym, yv of Bootstrap1D), k_contrast_design1_* NP = 1
+// (the replicate correlations of Bootstrap2D), which reads every byte once, tests it once and writes one record.
 // design_coef<NP>: the coefficient of column c on NP response planes at once (each operand offset and weight read once);
 // returns whether the column is valid and leaves NaN in v where it is not.
 template <int NP>
@@ -434,6 +393,35 @@ __device__ __forceinline__ bool design_coef(const double *const (&y)[NP], int64_
   return good;
 }
 
+// One workgroup = one test, on NP planes.  y[k]: plane k; st[k]: record k of this test.
+template <int NP>
+__device__ __forceinline__ void design_test(const double *const (&y)[NP], int64_t ld, int32_t num_boot, int32_t n_groups, int row, int d,
+                                            const int32_t *__restrict__ design_ptr, const int32_t *__restrict__ design_grp,
+                                            const double *__restrict__ design_w, double *const (&st)[NP], double *red) {
+  int p0 = design_ptr[d], p1 = design_ptr[d + 1];
+  if (p1 <= p0) {
+    for (int k = 0; k < NP; k++) write_nan_record(st[k]);
+    return;
+  }
+  int64_t row_base = (int64_t)row * n_groups;
+  auto coef_at = [&](int c, double(&v)[NP]) { return design_coef<NP>(y, ld, row_base, design_grp, design_w, p0, p1, c, v); };
+  fill_records<NP, false>(coef_at, num_boot + 1, nullptr, st, red);
+}
+
+// The coefficient row of one test on plane ``which`` (for the host-side tail fits); NaN in the columns that are not valid
+template <int NP>
+__device__ __forceinline__ void design_rows(const double *const (&y)[NP], int64_t ld, int32_t num_boot, int32_t n_groups, int row, int d,
+                                            const int32_t *__restrict__ design_ptr, const int32_t *__restrict__ design_grp,
+                                            const double *__restrict__ design_w, int32_t which, double *__restrict__ out_row) {
+  int p0 = design_ptr[d], p1 = design_ptr[d + 1];
+  int64_t row_base = (int64_t)row * n_groups;
+  for (int c = threadIdx.x; c <= num_boot; c += 256) {
+    double v[NP];
+    bool ok = design_coef<NP>(y, ld, row_base, design_grp, design_w, p0, p1, c, v);
+    out_row[c] = (ok && p1 > p0) ? (which ? v[NP - 1] : v[0]) : NAN;
+  }
+}
+
 __global__ __launch_bounds__(K9_THREADS) void k_contrast_design_stats(const double *__restrict__ ym, const double *__restrict__ yv,
                                                                       int64_t ld, int32_t num_boot, int32_t n_groups,
                                                                       const int32_t *__restrict__ test_gene,
@@ -444,21 +432,11 @@ __global__ __launch_bounds__(K9_THREADS) void k_contrast_design_stats(const doub
                                                                       double *__restrict__ stats_v) {
   __shared__ double red[K9_THREADS / 64];
   int64_t t = blockIdx.x;
-  int gene = test_gene[t], d = test_design[t];
-  int p0 = design_ptr[d], p1 = design_ptr[d + 1];
-  double *const st[2] = {stats_m + t * 8, stats_v + t * 8};
-  if (p1 <= p0) {
-    write_nan_record(st[0]);
-    write_nan_record(st[1]);
-    return;
-  }
   const double *const y[2] = {ym, yv};
-  int64_t row_base = (int64_t)gene * n_groups;
-  auto coef_at = [&](int c, double(&v)[2]) { return design_coef<2>(y, ld, row_base, design_grp, design_w, p0, p1, c, v); };
-  fill_records<2, false>(coef_at, num_boot + 1, nullptr, st, red);
+  double *const st[2] = {stats_m + t * 8, stats_v + t * 8};
+  design_test<2>(y, ld, num_boot, n_groups, test_gene[t], test_design[t], design_ptr, design_grp, design_w, st, red);
 }
 
-// coefficient rows of selected design contrasts (for the host-side tail fits); NaN in the columns that are not valid
 __global__ __launch_bounds__(256) void k_contrast_design_rows(const double *__restrict__ ym, const double *__restrict__ yv, int64_t ld,
                                                               int32_t num_boot, int32_t n_groups, const int32_t *__restrict__ test_gene,
                                                               const int32_t *__restrict__ test_design,
@@ -467,26 +445,10 @@ __global__ __launch_bounds__(256) void k_contrast_design_rows(const double *__re
                                                               const double *__restrict__ design_w, int32_t which,
                                                               double *__restrict__ out) {
   int64_t t = blockIdx.x;
-  int gene = test_gene[t], d = test_design[t];
-  int p0 = design_ptr[d], p1 = design_ptr[d + 1];
-  int64_t row_base = (int64_t)gene * n_groups;
   const double *const y[2] = {ym, yv};
-  for (int c = threadIdx.x; c <= num_boot; c += 256) {
-    double v[2];
-    bool ok = design_coef<2>(y, ld, row_base, design_grp, design_w, p0, p1, c, v);
-    out[t * ld + c] = (ok && p1 > p0) ? (which ? v[1] : v[0]) : NAN;
-  }
+  design_rows<2>(y, ld, num_boot, n_groups, test_gene[t], test_design[t], design_ptr, design_grp, design_w, which, out + t * ld);
 }
 
-// ------------------------------------------------------------------------------------------------
-// Guide-vs-control contrasts on ONE response plane (the replicate correlations of Bootstrap2D, ht_2d_vs_control): test t
-// applies the sparse weight row of design test_design[t] to the rows of pair test_row[t]:
-//   coef_c = sum_p design_w[p] * y[test_row[t] * n_groups + design_grp[p]][c],  p in [design_ptr[d], design_ptr[d + 1]).
-// The plain two-group test is the design {(guide, +1), (control, -1)}; an empty design gives the NaN record.  Column c is
-// valid only if every listed group is finite there (_regress_2d, hypothesis_test.py:372-373).  Against running the plane
-// through k_contrast_design_stats as both ym and yv this reads every byte once, tests it once and writes one record.
-// Two passes that recompute the coefficient (nothing per-replicate is stored): a test reads 2 x |design| rows, and the
-// control rows of a pair are shared by its consecutive tests through L2 / MALL (tests are issued pair-major).
 __global__ __launch_bounds__(K9_THREADS) void k_contrast_design1_stats(const double *__restrict__ y, int64_t ld, int32_t num_boot,
                                                                        int32_t n_groups, const int32_t *__restrict__ test_row,
                                                                        const int32_t *__restrict__ test_design,
@@ -495,20 +457,11 @@ __global__ __launch_bounds__(K9_THREADS) void k_contrast_design1_stats(const dou
                                                                        const double *__restrict__ design_w, double *__restrict__ stats) {
   __shared__ double red[K9_THREADS / 64];
   int64_t t = blockIdx.x;
-  int d = test_design[t];
-  int p0 = design_ptr[d], p1 = design_ptr[d + 1];
-  double *const st[1] = {stats + t * 8};
-  if (p1 <= p0) {
-    write_nan_record(st[0]);
-    return;
-  }
   const double *const yp[1] = {y};
-  int64_t row_base = (int64_t)test_row[t] * n_groups;
-  auto coef_at = [&](int c, double(&v)[1]) { return design_coef<1>(yp, ld, row_base, design_grp, design_w, p0, p1, c, v); };
-  fill_records<1, false>(coef_at, num_boot + 1, nullptr, st, red);
+  double *const st[1] = {stats + t * 8};
+  design_test<1>(yp, ld, num_boot, n_groups, test_row[t], test_design[t], design_ptr, design_grp, design_w, st, red);
 }
 
-// coefficient rows of selected single-plane design contrasts (for the host-side tail fits); NaN in the columns that are not valid
 __global__ __launch_bounds__(256) void k_contrast_design1_rows(const double *__restrict__ y, int64_t ld, int32_t num_boot, int32_t n_groups,
                                                                const int32_t *__restrict__ test_row,
                                                                const int32_t *__restrict__ test_design,
@@ -516,15 +469,8 @@ __global__ __launch_bounds__(256) void k_contrast_design1_rows(const double *__r
                                                                const int32_t *__restrict__ design_grp,
                                                                const double *__restrict__ design_w, double *__restrict__ out) {
   int64_t t = blockIdx.x;
-  int d = test_design[t];
-  int p0 = design_ptr[d], p1 = design_ptr[d + 1];
-  int64_t row_base = (int64_t)test_row[t] * n_groups;
   const double *const yp[1] = {y};
-  for (int c = threadIdx.x; c <= num_boot; c += 256) {
-    double v[1];
-    bool ok = design_coef<1>(yp, ld, row_base, design_grp, design_w, p0, p1, c, v);
-    out[t * ld + c] = (ok && p1 > p0) ? v[0] : NAN;
-  }
+  design_rows<1>(yp, ld, num_boot, n_groups, test_row[t], test_design[t], design_ptr, design_grp, design_w, 0, out + t * ld);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -972,26 +918,12 @@ int mm_cross_resampled(const double *d_yt, int64_t ld, int32_t num_boot, int32_t
   return MM_OK;
 }
 
-int mm_contrast_stats(const double *d_ym, const double *d_yv, int64_t ld, int32_t num_boot, int32_t n_groups, int32_t ctrl,
-                      const int32_t *d_test_gene, const int32_t *d_test_grp, const uint8_t *d_good, int64_t n_tests,
-                      double *d_stats_mean, double *d_stats_var, void *stream) {
-  MM_ARG(d_ym && d_yv && d_test_gene && d_test_grp && d_good && d_stats_mean && d_stats_var);
-  MM_ARG(n_tests >= 0 && n_tests < 2147483647LL && n_groups > 0 && ctrl >= 0 && ctrl < n_groups && num_boot > 0 && ld >= (int64_t)num_boot + 1);
-  if (n_tests == 0) return MM_OK;
-  hipLaunchKernelGGL(k_contrast_stats, dim3((unsigned)n_tests), dim3(K9_THREADS), 0, (hipStream_t)stream, d_ym, d_yv, ld, num_boot, n_groups,
-                     ctrl, d_test_gene, d_test_grp, d_good, d_stats_mean, d_stats_var);
-  MM_LAUNCH_CHECK();
-  return MM_OK;
-}
-
-int mm_contrast_rows(const double *d_ym, const double *d_yv, int64_t ld, int32_t num_boot, int32_t n_groups, int32_t ctrl,
-                     const int32_t *d_test_gene, const int32_t *d_test_grp, int64_t n_tests, int32_t which, double *d_out,
-                     void *stream) {
-  MM_ARG(d_ym && d_yv && d_test_gene && d_test_grp && d_out && n_tests >= 0 && n_tests < 2147483647LL && (which == 0 || which == 1));
-  if (n_tests == 0) return MM_OK;
-  hipLaunchKernelGGL(k_contrast_rows, dim3((unsigned)n_tests), dim3(256), 0, (hipStream_t)stream, d_ym, d_yv, ld, num_boot, n_groups, ctrl,
-                     d_test_gene, d_test_grp, which, d_out);
-  MM_LAUNCH_CHECK();
+// The checks the four design-contrast entry points share (the index tables themselves are trusted: engine._design_tables)
+static int design_args(bool planes_and_outputs, int64_t ld, int32_t num_boot, int32_t n_groups, const int32_t *d_test_row,
+                       const int32_t *d_test_design, const int32_t *d_design_ptr, const int32_t *d_design_grp, const double *d_design_w,
+                       int64_t n_tests) {
+  MM_ARG(planes_and_outputs && d_test_row && d_test_design && d_design_ptr && d_design_grp && d_design_w);
+  MM_ARG(n_tests >= 0 && n_tests < 2147483647LL && n_groups > 0 && num_boot > 0 && ld >= (int64_t)num_boot + 1);
   return MM_OK;
 }
 
@@ -999,9 +931,9 @@ int mm_contrast_design_stats(const double *d_ym, const double *d_yv, int64_t ld,
                              const int32_t *d_test_gene, const int32_t *d_test_design, const int32_t *d_design_ptr,
                              const int32_t *d_design_grp, const double *d_design_w, int64_t n_tests, double *d_stats_mean,
                              double *d_stats_var, void *stream) {
-  MM_ARG(d_ym && d_yv && d_test_gene && d_test_design && d_design_ptr && d_design_grp && d_design_w && d_stats_mean && d_stats_var);
-  MM_ARG(n_tests >= 0 && n_tests < 2147483647LL && n_groups > 0 && num_boot > 0 && ld >= (int64_t)num_boot + 1);
-  if (n_tests == 0) return MM_OK;
+  int rc = design_args(d_ym && d_yv && d_stats_mean && d_stats_var, ld, num_boot, n_groups, d_test_gene, d_test_design, d_design_ptr,
+                       d_design_grp, d_design_w, n_tests);
+  if (rc != MM_OK || n_tests == 0) return rc;
   hipLaunchKernelGGL(k_contrast_design_stats, dim3((unsigned)n_tests), dim3(K9_THREADS), 0, (hipStream_t)stream, d_ym, d_yv, ld, num_boot,
                      n_groups, d_test_gene, d_test_design, d_design_ptr, d_design_grp, d_design_w, d_stats_mean, d_stats_var);
   MM_LAUNCH_CHECK();
@@ -1012,49 +944,12 @@ int mm_contrast_design_rows(const double *d_ym, const double *d_yv, int64_t ld, 
                             const int32_t *d_test_gene, const int32_t *d_test_design, const int32_t *d_design_ptr,
                             const int32_t *d_design_grp, const double *d_design_w, int64_t n_tests, int32_t which, double *d_out,
                             void *stream) {
-  MM_ARG(d_ym && d_yv && d_test_gene && d_test_design && d_design_ptr && d_design_grp && d_design_w && d_out);
-  MM_ARG(n_tests >= 0 && n_tests < 2147483647LL && n_groups > 0 && num_boot > 0 && ld >= (int64_t)num_boot + 1 && (which == 0 || which == 1));
-  if (n_tests == 0) return MM_OK;
+  MM_ARG(which == 0 || which == 1);
+  int rc = design_args(d_ym && d_yv && d_out, ld, num_boot, n_groups, d_test_gene, d_test_design, d_design_ptr, d_design_grp, d_design_w,
+                       n_tests);
+  if (rc != MM_OK || n_tests == 0) return rc;
   hipLaunchKernelGGL(k_contrast_design_rows, dim3((unsigned)n_tests), dim3(256), 0, (hipStream_t)stream, d_ym, d_yv, ld, num_boot, n_groups,
                      d_test_gene, d_test_design, d_design_ptr, d_design_grp, d_design_w, which, d_out);
-  MM_LAUNCH_CHECK();
-  return MM_OK;
-}
-
-int mm_joint_stats(const double *d_ym, const double *d_yv, int64_t ld, int32_t num_boot, int32_t n_groups,
-                   const int32_t *d_test_gene, const int32_t *d_test_design, const int32_t *d_design_ptr,
-                   const int32_t *d_design_rank, const int64_t *d_design_lofs, const int32_t *d_design_grp,
-                   const double *d_design_L, int64_t n_tests, double *d_stats_mean, double *d_stats_var, void *stream) {
-  MM_ARG(d_ym && d_yv && d_test_gene && d_test_design && d_design_ptr && d_design_rank && d_design_lofs && d_design_grp && d_design_L);
-  MM_ARG(d_stats_mean && d_stats_var);
-  MM_ARG(n_tests >= 0 && n_tests < 2147483647LL && n_groups > 0 && num_boot > 0 && ld >= (int64_t)num_boot + 1);
-  // a design has r <= n_d <= n_groups: z_0 of both planes takes 2 x n_groups doubles, the staged L at most JOINT_LDS_DOUBLES
-  int64_t cap = (int64_t)n_groups * n_groups < JOINT_LDS_DOUBLES ? (int64_t)n_groups * n_groups : JOINT_LDS_DOUBLES;
-  size_t shm = ((size_t)n_groups * 2 + (size_t)cap) * 8;
-  MM_ARG(shm <= 64 * 1024);
-  if (n_tests == 0) return MM_OK;
-  auto kernel = n_groups <= JOINT_REG_SMALL ? k_joint_stats<JOINT_REG_SMALL> : n_groups <= JOINT_REG_GROUPS ? k_joint_stats<JOINT_REG_GROUPS> : k_joint_stats<0>;
-  hipLaunchKernelGGL(kernel, dim3((unsigned)n_tests), dim3(K9_THREADS), shm, (hipStream_t)stream, d_ym, d_yv, ld, num_boot, n_groups,
-                     (int32_t)cap, d_test_gene, d_test_design, d_design_ptr, d_design_rank, d_design_lofs, d_design_grp, d_design_L,
-                     d_stats_mean, d_stats_var);
-  MM_LAUNCH_CHECK();
-  return MM_OK;
-}
-
-int mm_joint1_stats(const double *d_y, int64_t ld, int32_t num_boot, int32_t n_groups, const int32_t *d_test_row,
-                    const int32_t *d_test_design, const int32_t *d_design_ptr, const int32_t *d_design_rank,
-                    const int64_t *d_design_lofs, const int32_t *d_design_grp, const double *d_design_L, int64_t n_tests,
-                    double *d_stats, void *stream) {
-  MM_ARG(d_y && d_test_row && d_test_design && d_design_ptr && d_design_rank && d_design_lofs && d_design_grp && d_design_L && d_stats);
-  MM_ARG(n_tests >= 0 && n_tests < 2147483647LL && n_groups > 0 && num_boot > 0 && ld >= (int64_t)num_boot + 1);
-  // as mm_joint_stats, with z_0 of one plane: n_groups doubles, and the staged L at most JOINT_LDS_DOUBLES
-  int64_t cap = (int64_t)n_groups * n_groups < JOINT_LDS_DOUBLES ? (int64_t)n_groups * n_groups : JOINT_LDS_DOUBLES;
-  size_t shm = ((size_t)n_groups + (size_t)cap) * 8;
-  MM_ARG(shm <= 64 * 1024);
-  if (n_tests == 0) return MM_OK;
-  auto kernel = n_groups <= JOINT_REG_SMALL ? k_joint1_stats<JOINT_REG_SMALL> : n_groups <= JOINT_REG_GROUPS ? k_joint1_stats<JOINT_REG_GROUPS> : k_joint1_stats<0>;
-  hipLaunchKernelGGL(kernel, dim3((unsigned)n_tests), dim3(K9_THREADS), shm, (hipStream_t)stream, d_y, ld, num_boot, n_groups, (int32_t)cap,
-                     d_test_row, d_test_design, d_design_ptr, d_design_rank, d_design_lofs, d_design_grp, d_design_L, d_stats);
   MM_LAUNCH_CHECK();
   return MM_OK;
 }
@@ -1062,9 +957,8 @@ int mm_joint1_stats(const double *d_y, int64_t ld, int32_t num_boot, int32_t n_g
 int mm_contrast_design1_stats(const double *d_y, int64_t ld, int32_t num_boot, int32_t n_groups, const int32_t *d_test_row,
                               const int32_t *d_test_design, const int32_t *d_design_ptr, const int32_t *d_design_grp,
                               const double *d_design_w, int64_t n_tests, double *d_stats, void *stream) {
-  MM_ARG(d_y && d_test_row && d_test_design && d_design_ptr && d_design_grp && d_design_w && d_stats);
-  MM_ARG(n_tests >= 0 && n_tests < 2147483647LL && n_groups > 0 && num_boot > 0 && ld >= (int64_t)num_boot + 1);
-  if (n_tests == 0) return MM_OK;
+  int rc = design_args(d_y && d_stats, ld, num_boot, n_groups, d_test_row, d_test_design, d_design_ptr, d_design_grp, d_design_w, n_tests);
+  if (rc != MM_OK || n_tests == 0) return rc;
   hipLaunchKernelGGL(k_contrast_design1_stats, dim3((unsigned)n_tests), dim3(K9_THREADS), 0, (hipStream_t)stream, d_y, ld, num_boot, n_groups,
                      d_test_row, d_test_design, d_design_ptr, d_design_grp, d_design_w, d_stats);
   MM_LAUNCH_CHECK();
@@ -1074,11 +968,62 @@ int mm_contrast_design1_stats(const double *d_y, int64_t ld, int32_t num_boot, i
 int mm_contrast_design1_rows(const double *d_y, int64_t ld, int32_t num_boot, int32_t n_groups, const int32_t *d_test_row,
                              const int32_t *d_test_design, const int32_t *d_design_ptr, const int32_t *d_design_grp,
                              const double *d_design_w, int64_t n_tests, double *d_out, void *stream) {
-  MM_ARG(d_y && d_test_row && d_test_design && d_design_ptr && d_design_grp && d_design_w && d_out);
-  MM_ARG(n_tests >= 0 && n_tests < 2147483647LL && n_groups > 0 && num_boot > 0 && ld >= (int64_t)num_boot + 1);
-  if (n_tests == 0) return MM_OK;
+  int rc = design_args(d_y && d_out, ld, num_boot, n_groups, d_test_row, d_test_design, d_design_ptr, d_design_grp, d_design_w, n_tests);
+  if (rc != MM_OK || n_tests == 0) return rc;
   hipLaunchKernelGGL(k_contrast_design1_rows, dim3((unsigned)n_tests), dim3(256), 0, (hipStream_t)stream, d_y, ld, num_boot, n_groups,
                      d_test_row, d_test_design, d_design_ptr, d_design_grp, d_design_w, d_out);
+  MM_LAUNCH_CHECK();
+  return MM_OK;
+}
+
+// The checks and the launch shape mm_joint_stats (NP = 2) and mm_joint1_stats (NP = 1) share.  A design has r <= n_d <= n_groups:
+// z_0 takes NP x n_groups doubles of LDS, the staged L at most JOINT_LDS_DOUBLES (*cap); *tier: 0, 1, 2 = the kernel's NDR
+// JOINT_REG_SMALL, JOINT_REG_GROUPS, 0.
+static int joint_args(int n_planes, bool planes_and_outputs, int64_t ld, int32_t num_boot, int32_t n_groups, const int32_t *d_test_row,
+                      const int32_t *d_test_design, const int32_t *d_design_ptr, const int32_t *d_design_rank,
+                      const int64_t *d_design_lofs, const int32_t *d_design_grp, const double *d_design_L, int64_t n_tests, int32_t *cap,
+                      size_t *shm, int *tier) {
+  MM_ARG(planes_and_outputs && d_test_row && d_test_design && d_design_ptr && d_design_rank && d_design_lofs && d_design_grp && d_design_L);
+  MM_ARG(n_tests >= 0 && n_tests < 2147483647LL && n_groups > 0 && num_boot > 0 && ld >= (int64_t)num_boot + 1);
+  int64_t c = (int64_t)n_groups * n_groups < JOINT_LDS_DOUBLES ? (int64_t)n_groups * n_groups : JOINT_LDS_DOUBLES;
+  *cap = (int32_t)c;
+  *shm = ((size_t)n_groups * n_planes + (size_t)c) * 8;
+  MM_ARG(*shm <= 64 * 1024);
+  *tier = n_groups <= JOINT_REG_SMALL ? 0 : n_groups <= JOINT_REG_GROUPS ? 1 : 2;
+  return MM_OK;
+}
+
+int mm_joint_stats(const double *d_ym, const double *d_yv, int64_t ld, int32_t num_boot, int32_t n_groups,
+                   const int32_t *d_test_gene, const int32_t *d_test_design, const int32_t *d_design_ptr,
+                   const int32_t *d_design_rank, const int64_t *d_design_lofs, const int32_t *d_design_grp,
+                   const double *d_design_L, int64_t n_tests, double *d_stats_mean, double *d_stats_var, void *stream) {
+  int32_t cap;
+  size_t shm;
+  int tier;
+  int rc = joint_args(2, d_ym && d_yv && d_stats_mean && d_stats_var, ld, num_boot, n_groups, d_test_gene, d_test_design, d_design_ptr,
+                      d_design_rank, d_design_lofs, d_design_grp, d_design_L, n_tests, &cap, &shm, &tier);
+  if (rc != MM_OK || n_tests == 0) return rc;
+  auto kernel = tier == 0 ? k_joint_stats<JOINT_REG_SMALL> : tier == 1 ? k_joint_stats<JOINT_REG_GROUPS> : k_joint_stats<0>;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)n_tests), dim3(K9_THREADS), shm, (hipStream_t)stream, d_ym, d_yv, ld, num_boot, n_groups, cap,
+                     d_test_gene, d_test_design, d_design_ptr, d_design_rank, d_design_lofs, d_design_grp, d_design_L, d_stats_mean,
+                     d_stats_var);
+  MM_LAUNCH_CHECK();
+  return MM_OK;
+}
+
+int mm_joint1_stats(const double *d_y, int64_t ld, int32_t num_boot, int32_t n_groups, const int32_t *d_test_row,
+                    const int32_t *d_test_design, const int32_t *d_design_ptr, const int32_t *d_design_rank,
+                    const int64_t *d_design_lofs, const int32_t *d_design_grp, const double *d_design_L, int64_t n_tests,
+                    double *d_stats, void *stream) {
+  int32_t cap;
+  size_t shm;
+  int tier;
+  int rc = joint_args(1, d_y && d_stats, ld, num_boot, n_groups, d_test_row, d_test_design, d_design_ptr, d_design_rank, d_design_lofs,
+                      d_design_grp, d_design_L, n_tests, &cap, &shm, &tier);
+  if (rc != MM_OK || n_tests == 0) return rc;
+  auto kernel = tier == 0 ? k_joint1_stats<JOINT_REG_SMALL> : tier == 1 ? k_joint1_stats<JOINT_REG_GROUPS> : k_joint1_stats<0>;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)n_tests), dim3(K9_THREADS), shm, (hipStream_t)stream, d_y, ld, num_boot, n_groups, cap,
+                     d_test_row, d_test_design, d_design_ptr, d_design_rank, d_design_lofs, d_design_grp, d_design_L, d_stats);
   MM_LAUNCH_CHECK();
   return MM_OK;
 }

@@ -6,6 +6,7 @@ include/memento_hip.h.  Nothing in this module has a CPU fallback.
 """
 
 import ctypes
+import functools
 import os
 
 from ctypes import c_void_p
@@ -998,62 +999,27 @@ class Bootstrap1D:
         return coef, host(stats)[:n_tests]
 
     def contrast(self, test_gene, test_grp, ctrl, good):
-        """Two-group contrasts against the control group ``ctrl`` (mm_contrast_stats): returns (stats_mean, stats_var)
-        host arrays [n_tests][8]; ``rows(which, idx)`` gives the coefficient rows of selected tests on demand: a host array, or
-        with ``to_host=False`` a device tensor [len(idx)][ld] (a view of the scratch tensor ``out`` when one is passed)."""
-        torch = _torch()
-        n_tests = len(test_gene)
-        st_m = empty((max(1, n_tests), 8), torch.float64)
-        st_v = empty((max(1, n_tests), 8), torch.float64)
-        d_tg, d_gr = dev(np.asarray(test_gene, dtype=np.int32)), dev(np.asarray(test_grp, dtype=np.int32))
-        d_good = dev(np.asarray(good, dtype=np.uint8))
-        _lib.call("mm_contrast_stats", P(self.ym), P(self.yv), self.ld, self.B, self.ng, int(ctrl), P(d_tg), P(d_gr), P(d_good), n_tests,
-                  P(st_m), P(st_v), _stream())
-
-        def rows(which, idx, to_host=True, out=None):
-            idx = np.asarray(idx, dtype=np.int64)
-            out = _rows_out(out, len(idx), self.ld)
-            a, b = dev(np.asarray(test_gene, dtype=np.int32)[idx]), dev(np.asarray(test_grp, dtype=np.int32)[idx])
-            _lib.call("mm_contrast_rows", P(self.ym), P(self.yv), self.ld, self.B, self.ng, int(ctrl), P(a), P(b), len(idx), int(which),
-                      P(out), _stream())
-            return host(out)[: len(idx)] if to_host else out[: len(idx)]
-
-        return host(st_m)[:n_tests], host(st_v)[:n_tests], rows
+        """Two-group contrasts against the control group ``ctrl`` (``_contrast``: the designs {(group, +1), (ctrl, -1)} through
+        ``contrast_design``): returns (stats_mean, stats_var) host arrays [n_tests][8], the NaN record where ``good`` [gene][group]
+        lacks the test's group or the control; ``rows(which, idx)`` gives the coefficient rows of selected tests on demand: a host
+        array, or with ``to_host=False`` a device tensor [len(idx)][ld] (a view of the scratch tensor ``out`` when one is passed)."""
+        (st_m, st_v), rows = _contrast([self.ym, self.yv], self.ld, self.B, self.ng, self.n_tested, test_gene, test_grp, ctrl, good)
+        return st_m, st_v, rows
 
     def contrast_design(self, test_gene, test_design, design_ptr, design_grp, design_w):
         """Guide-vs-control contrasts with covariates (mm_contrast_design_stats): test t applies the sparse weight row
         ``design_grp/design_w[design_ptr[d]:design_ptr[d + 1]]``, d = ``test_design[t]``, to the replicate rows of gene
         ``test_gene[t]``.  Returns (stats_mean, stats_var) host arrays [n_tests][8] and ``rows(which, idx)``, as ``contrast``."""
-        torch = _torch()
-        test_gene, test_design, d_tab = _design_tables(test_gene, test_design, design_ptr, design_grp, design_w, self.n_tested, self.ng)
-        n_tests = len(test_gene)
-        st_m = empty((max(1, n_tests), 8), torch.float64)
-        st_v = empty((max(1, n_tests), 8), torch.float64)
-        _lib.call("mm_contrast_design_stats", P(self.ym), P(self.yv), self.ld, self.B, self.ng, *map(P, d_tab), n_tests, P(st_m), P(st_v),
-                  _stream())
-
-        def rows(which, idx, to_host=True, out=None):
-            idx = np.asarray(idx, dtype=np.int64)
-            out = _rows_out(out, len(idx), self.ld)
-            a, b = dev(test_gene[idx]), dev(test_design[idx])
-            _lib.call("mm_contrast_design_rows", P(self.ym), P(self.yv), self.ld, self.B, self.ng, P(a), P(b), *map(P, d_tab[2:]), len(idx),
-                      int(which), P(out), _stream())
-            return host(out)[: len(idx)] if to_host else out[: len(idx)]
-
-        return host(st_m)[:n_tests], host(st_v)[:n_tests], rows
+        (st_m, st_v), rows = _contrast_design([self.ym, self.yv], self.ld, self.B, self.ng, self.n_tested, test_gene, test_design, design_ptr,
+                                              design_grp, design_w)
+        return st_m, st_v, rows
 
     def joint(self, test_gene, tables):
         """Joint tests of a treatment block (mm_joint_stats): test t applies the linear forms of design ``tables.test_design[t]``
         (``memento._ht.joint_tables``: ``design_ptr``, ``design_rank``, ``design_lofs``, ``design_grp``, ``design_L``) to the
         replicate rows of gene ``test_gene[t]``.  Returns (stats_mean, stats_var) host arrays [n_tests][8], the joint record of
         include/memento_hip.h."""
-        torch = _torch()
-        test_gene, d_tab = _joint_tables(test_gene, tables, self.n_tested, self.ng)
-        n_tests = len(test_gene)
-        st_m = empty((max(1, n_tests), 8), torch.float64)
-        st_v = empty((max(1, n_tests), 8), torch.float64)
-        _lib.call("mm_joint_stats", P(self.ym), P(self.yv), self.ld, self.B, self.ng, *map(P, d_tab), n_tests, P(st_m), P(st_v), _stream())
-        return host(st_m)[:n_tests], host(st_v)[:n_tests]
+        return tuple(_joint([self.ym, self.yv], self.ld, self.B, self.ng, self.n_tested, test_gene, tables))
 
     def valid_cols(self, good):
         """hypothesis_test.py:249-251 on the device: (col_map device tensor [n_tested][B+1], n_valid host [n_tested]) --
@@ -1095,66 +1061,115 @@ def row_quantiles(rows, ld, num_boot, probs):
     return q[:n_rows], host(n_valid)[:n_rows]
 
 
-def _design_tables(test_row, test_design, design_ptr, design_grp, design_w, n_rows, ng):
-    """The tables of the design-contrast kernels (``contrast_design`` of Bootstrap1D / Bootstrap2D): test t applies design
-    ``test_design[t]`` -- the CSR row ``design_grp/design_w[design_ptr[d]:design_ptr[d + 1]]`` over the ``ng`` groups -- to
-    row block ``test_row[t]`` < ``n_rows`` (a gene slot or a pair).  Coerces and checks them (the kernels trust these indices)
-    and uploads them, empty arrays padded to one element.  Returns test_row and test_design as int32 host arrays and the
-    device tensors (test_row, test_design, design_ptr, design_grp, design_w), the order in which the kernels take them."""
-    test_row = np.asarray(test_row, dtype=np.int32)
-    test_design = np.asarray(test_design, dtype=np.int32)
-    design_ptr = np.asarray(design_ptr, dtype=np.int32)
-    design_grp = np.asarray(design_grp, dtype=np.int32)
-    design_w = np.asarray(design_w, dtype=np.float64)
+def _up(a):
+    return dev(a if len(a) else np.zeros(1, a.dtype))
+
+
+def _csr_tables(what, test_row, test_design, design_ptr, design_grp, n_rows, ng):
+    """What the design and the joint tables share, coerced to int32 host arrays and checked (the kernels trust these indices):
+    test t applies design ``test_design[t]`` -- the groups ``design_grp[design_ptr[d]:design_ptr[d + 1]]`` among the ``ng`` -- to row
+    block ``test_row[t]`` < ``n_rows`` (a gene slot or a pair).  ``what`` names the caller in the messages."""
+    test_row, test_design, design_ptr, design_grp = (np.asarray(a, dtype=np.int32) for a in (test_row, test_design, design_ptr, design_grp))
     n_tests, n_designs = len(test_row), len(design_ptr) - 1
-    if len(test_design) != n_tests or n_designs < 0 or len(design_w) != len(design_grp):
-        raise ValueError("contrast_design: inconsistent table sizes")
+    if len(test_design) != n_tests or n_designs < 0:
+        raise ValueError(f"{what}: inconsistent table sizes")
     if design_ptr[0] != 0 or design_ptr[-1] != len(design_grp) or (np.diff(design_ptr) < 0).any():
-        raise ValueError("contrast_design: design_ptr is not a CSR pointer over design_grp")
+        raise ValueError(f"{what}: design_ptr is not a CSR pointer over design_grp")
     if len(design_grp) and (design_grp.min() < 0 or design_grp.max() >= ng):
-        raise ValueError("contrast_design: group index out of range")
+        raise ValueError(f"{what}: group index out of range")
     if n_tests and (test_row.min() < 0 or test_row.max() >= n_rows or test_design.min() < 0 or test_design.max() >= n_designs):
-        raise ValueError("contrast_design: test index out of range")
+        raise ValueError(f"{what}: test index out of range")
+    return test_row, test_design, design_ptr, design_grp
 
-    def up(a):
-        return dev(a if len(a) else np.zeros(1, a.dtype))
 
-    return test_row, test_design, (up(test_row), up(test_design), dev(design_ptr), up(design_grp), up(design_w))
+def _design_tables(test_row, test_design, design_ptr, design_grp, design_w, n_rows, ng):
+    """The tables of the design-contrast kernels (``contrast_design`` of Bootstrap1D / Bootstrap2D): the CSR rows of
+    ``_csr_tables`` with one weight ``design_w`` per listed group, checked and uploaded, empty arrays padded to one element.
+    Returns test_row and test_design as int32 host arrays and the device tensors (test_row, test_design, design_ptr, design_grp,
+    design_w), the order in which the kernels take them."""
+    design_w = np.asarray(design_w, dtype=np.float64)
+    if len(design_w) != len(np.asarray(design_grp)):
+        raise ValueError("contrast_design: inconsistent table sizes")
+    test_row, test_design, design_ptr, design_grp = _csr_tables("contrast_design", test_row, test_design, design_ptr, design_grp, n_rows, ng)
+    return test_row, test_design, (_up(test_row), _up(test_design), dev(design_ptr), _up(design_grp), _up(design_w))
+
+
+def _contrast_design(planes, ld, B, ng, n_rows, test_row, test_design, design_ptr, design_grp, design_w, rows_design=None):
+    """``contrast_design`` of Bootstrap1D (``planes`` = [ym, yv]: mm_contrast_design_stats / _rows) and Bootstrap2D ([yc]:
+    mm_contrast_design1_stats / _rows).  Returns the records, one host array [n_tests][8] per plane, and
+    ``rows(which, idx, to_host=True, out=None)``: the coefficient rows of the tests ``idx`` on plane ``which``, under the designs
+    ``rows_design`` (checked by the caller) where given, not ``test_design``."""
+    torch = _torch()
+    one = "1" if len(planes) == 1 else ""
+    test_row, test_design, d_tab = _design_tables(test_row, test_design, design_ptr, design_grp, design_w, n_rows, ng)
+    if rows_design is None:
+        rows_design = test_design
+    n_tests = len(test_row)
+    stats = [empty((max(1, n_tests), 8), torch.float64) for _ in planes]
+    _lib.call(f"mm_contrast_design{one}_stats", *map(P, planes), ld, B, ng, *map(P, d_tab), n_tests, *map(P, stats), _stream())
+
+    def rows(which, idx, to_host=True, out=None):
+        idx = np.asarray(idx, dtype=np.int64)
+        out = _rows_out(out, len(idx), ld)
+        a, b = dev(test_row[idx]), dev(rows_design[idx])
+        _lib.call(f"mm_contrast_design{one}_rows", *map(P, planes), ld, B, ng, P(a), P(b), *map(P, d_tab[2:]), len(idx),
+                  *([] if one else [int(which)]), P(out), _stream())
+        return host(out)[: len(idx)] if to_host else out[: len(idx)]
+
+    return [host(s)[:n_tests] for s in stats], rows
+
+
+def _contrast(planes, ld, B, ng, n_rows, test_row, test_grp, ctrl, good):
+    """``contrast`` of Bootstrap1D / Bootstrap2D: the plain two-group tests of group ``test_grp[t]`` against group ``ctrl`` on row
+    block ``test_row[t]``, as design contrasts.  Design j = {(j, +1.0), (ctrl, -1.0)} for every group j, the guide term first, and
+    design ``ng`` is empty: a test takes design ``test_grp[t]`` where ``good`` [row block][group] has its group and the control, the
+    empty one (the NaN record) otherwise; its ``rows`` are those of design ``test_grp[t]`` either way.  Returns as
+    ``_contrast_design``."""
+    test_row, test_grp, ctrl = np.asarray(test_row, dtype=np.int32), np.asarray(test_grp, dtype=np.int32), int(ctrl)
+    good = np.asarray(good, dtype=bool).reshape(-1, ng)
+    if not 0 <= ctrl < ng or (len(test_grp) and (test_grp.min() < 0 or test_grp.max() >= ng)):
+        raise ValueError("contrast: group index out of range")
+    if len(test_grp) != len(test_row) or (len(test_row) and (test_row.min() < 0 or test_row.max() >= min(n_rows, len(good)))):
+        raise ValueError("contrast: test index out of range")
+    design_ptr = np.concatenate([2 * np.arange(ng + 1), [2 * ng]])
+    design_grp = np.column_stack([np.arange(ng), np.full(ng, ctrl)]).reshape(-1)
+    test_design = np.where(good[test_row, test_grp] & good[test_row, ctrl], test_grp, ng)
+    return _contrast_design(planes, ld, B, ng, n_rows, test_row, test_design, design_ptr, design_grp, np.tile([1.0, -1.0], ng),
+                            rows_design=test_grp)
 
 
 def _joint_tables(test_gene, tables, n_rows, ng):
     """The tables of mm_joint_stats / mm_joint1_stats (``Bootstrap1D.joint``, ``Bootstrap2D.joint``), coerced, checked (the kernels
-    trust them) and uploaded, empty arrays padded to one element: every design has 0 <= rank <= n_d <= ``ng`` groups, all in
-    [0, ng), and rank x n_d doubles of ``design_L`` at its offset; every test names a row block (a gene slot or a pair)
-    < ``n_rows`` and a design.  Returns test_gene as an int32 host array
+    trust them) and uploaded, empty arrays padded to one element: the CSR rows of ``_csr_tables``, and every design has
+    0 <= rank <= n_d <= ``ng`` groups and rank x n_d doubles of ``design_L`` at its offset.  Returns test_gene as an int32 host array
     and the device tensors (test_gene, test_design, design_ptr, design_rank, design_lofs, design_grp, design_L), the order in
     which the kernel takes them."""
-    test_gene = np.asarray(test_gene, dtype=np.int32)
-    test_design = np.asarray(tables.test_design, dtype=np.int32)
-    design_ptr = np.asarray(tables.design_ptr, dtype=np.int32)
     design_rank = np.asarray(tables.design_rank, dtype=np.int32)
     design_lofs = np.asarray(tables.design_lofs, dtype=np.int64)
-    design_grp = np.asarray(tables.design_grp, dtype=np.int32)
     design_L = np.asarray(tables.design_L, dtype=np.float64).reshape(-1)
-    n_tests, n_designs = len(test_gene), len(design_ptr) - 1
-    if len(test_design) != n_tests or n_designs < 0 or len(design_rank) != n_designs or len(design_lofs) != n_designs:
+    n_designs = len(np.asarray(tables.design_ptr)) - 1
+    if len(design_rank) != n_designs or len(design_lofs) != n_designs:
         raise ValueError("joint: inconsistent table sizes")
-    if design_ptr[0] != 0 or design_ptr[-1] != len(design_grp) or (np.diff(design_ptr) < 0).any():
-        raise ValueError("joint: design_ptr is not a CSR pointer over design_grp")
-    if len(design_grp) and (design_grp.min() < 0 or design_grp.max() >= ng):
-        raise ValueError("joint: group index out of range")
+    test_gene, test_design, design_ptr, design_grp = _csr_tables("joint", test_gene, tables.test_design, tables.design_ptr, tables.design_grp,
+                                                                 n_rows, ng)
     n_d = np.diff(design_ptr).astype(np.int64)
     if (n_d > ng).any() or (design_rank < 0).any() or (design_rank > n_d).any():
         raise ValueError("joint: a design needs 0 <= rank <= its number of groups <= n_groups")
     if n_designs and ((design_lofs < 0).any() or (design_lofs + design_rank * n_d > len(design_L)).any()):
         raise ValueError("joint: design_lofs / design_rank run past design_L")
-    if n_tests and (test_gene.min() < 0 or test_gene.max() >= n_rows or test_design.min() < 0 or test_design.max() >= n_designs):
-        raise ValueError("joint: test index out of range")
+    return test_gene, (_up(test_gene), _up(test_design), dev(design_ptr), _up(design_rank), _up(design_lofs), _up(design_grp), _up(design_L))
 
-    def up(a):
-        return dev(a if len(a) else np.zeros(1, a.dtype))
 
-    return test_gene, (up(test_gene), up(test_design), dev(design_ptr), up(design_rank), up(design_lofs), up(design_grp), up(design_L))
+def _joint(planes, ld, B, ng, n_rows, test_row, tables):
+    """``joint`` of Bootstrap1D (``planes`` = [ym, yv]: mm_joint_stats) and Bootstrap2D ([yc]: mm_joint1_stats): the joint records, one
+    host array [n_tests][8] per plane."""
+    torch = _torch()
+    test_row, d_tab = _joint_tables(test_row, tables, n_rows, ng)
+    n_tests = len(test_row)
+    stats = [empty((max(1, n_tests), 8), torch.float64) for _ in planes]
+    _lib.call("mm_joint1_stats" if len(planes) == 1 else "mm_joint_stats", *map(P, planes), ld, B, ng, *map(P, d_tab), n_tests,
+              *map(P, stats), _stream())
+    return [host(s)[:n_tests] for s in stats]
 
 
 def _valid_cols(ym, yv, ld, B, ng, good, n_genes):
@@ -1421,34 +1436,24 @@ class Bootstrap2D:
                   P(stats), _stream())
         return coef, host(stats)[:n_tests]
 
+    def contrast(self, test_pair, test_grp, ctrl, good):
+        """Two-group contrasts of the correlation rows against the control group ``ctrl``, as ``Bootstrap1D.contrast``
+        (``_contrast``) with ``good`` [pair][group] in device pair order.  Returns (stats, rows) as ``contrast_design``."""
+        (stats,), rows = _contrast([self.yc], self.ld, self.B, self.ng, self.n_pairs, test_pair, test_grp, ctrl, good)
+        return stats, functools.partial(rows, 0)
+
     def contrast_design(self, test_pair, test_design, design_ptr, design_grp, design_w):
         """Guide-vs-control contrasts on the correlation rows (mm_contrast_design1_stats): test t applies the sparse weight row
         ``design_grp/design_w[design_ptr[d]:design_ptr[d + 1]]``, d = ``test_design[t]``, to the replicate rows of pair
         ``test_pair[t]`` (device pair order, ``self.order``).  Returns (stats host [n_tests][8], ``rows(idx)`` giving the
         coefficient rows of selected tests on demand; ``to_host`` / ``out`` as in ``Bootstrap1D.contrast``)."""
-        torch = _torch()
-        test_pair, test_design, d_tab = _design_tables(test_pair, test_design, design_ptr, design_grp, design_w, self.n_pairs, self.ng)
-        n_tests = len(test_pair)
-        stats = empty((max(1, n_tests), 8), torch.float64)
-        _lib.call("mm_contrast_design1_stats", P(self.yc), self.ld, self.B, self.ng, *map(P, d_tab), n_tests, P(stats), _stream())
-
-        def rows(idx, to_host=True, out=None):
-            idx = np.asarray(idx, dtype=np.int64)
-            out = _rows_out(out, len(idx), self.ld)
-            a, b = dev(test_pair[idx]), dev(test_design[idx])
-            _lib.call("mm_contrast_design1_rows", P(self.yc), self.ld, self.B, self.ng, P(a), P(b), *map(P, d_tab[2:]), len(idx), P(out), _stream())
-            return host(out)[: len(idx)] if to_host else out[: len(idx)]
-
-        return host(stats)[:n_tests], rows
+        (stats,), rows = _contrast_design([self.yc], self.ld, self.B, self.ng, self.n_pairs, test_pair, test_design, design_ptr, design_grp,
+                                          design_w)
+        return stats, functools.partial(rows, 0)
 
     def joint(self, test_pair, tables):
         """Joint tests of a treatment block on the correlation rows (mm_joint1_stats): test t applies the linear forms of design
         ``tables.test_design[t]`` (``memento._ht.joint_tables``, as for ``Bootstrap1D.joint``) to the replicate rows of pair
         ``test_pair[t]`` (device pair order, ``self.order``).  Returns stats, a host array [n_tests][8]: the joint record of
         include/memento_hip.h."""
-        torch = _torch()
-        test_pair, d_tab = _joint_tables(test_pair, tables, self.n_pairs, self.ng)
-        n_tests = len(test_pair)
-        stats = empty((max(1, n_tests), 8), torch.float64)
-        _lib.call("mm_joint1_stats", P(self.yc), self.ld, self.B, self.ng, *map(P, d_tab), n_tests, P(stats), _stream())
-        return host(stats)[:n_tests]
+        return _joint([self.yc], self.ld, self.B, self.ng, self.n_pairs, test_pair, tables)[0]

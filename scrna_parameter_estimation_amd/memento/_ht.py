@@ -133,6 +133,17 @@ def chunks_1d(st, mv, num_boot, chunk):
     st.last_bootstrap, st.last_chunk = c.bs, (c.g0, c.g1)
 
 
+def run_chunk_1d(c, mv, rng, fill_seed, fill_keys, chain_keys, uniforms=None):
+    """Bootstrap the chunk's chains (K6-K8, invalid replicates re-filled on the device): the two hash ``uniforms`` [2][pair] come
+    from the global ``np.random`` stream unless they are passed in; ``fill_keys`` / ``chain_keys`` [pair] key the refill and the
+    rng='fast' streams.  -> (``good`` [gene][group], hypothesis_test.py:193-200; ``n_inv`` [pair][2], the refilled replicates)."""
+    r1, r0 = hash_uniforms(~c.skip, 2) if uniforms is None else uniforms
+    n_inv = c.bs.run(c.skip, r1, r0, mv.fit, fill_mode=0, fill_seed=fill_seed, fast=(rng == 'fast'), mean_only=mv.mean_only,
+                     fill_keys=fill_keys, chain_keys=chain_keys)
+    good = (~c.skip) & (c.bs.K >= 2) & ~(n_inv < 0).any(axis=1)      # bootstrap.py:97-98: a single bin gives NaN replicates
+    return good.reshape(c.G, mv.ng), n_inv
+
+
 def gene_columns(treatment, treatment_for_gene, names):
     """Treatment columns of every gene, looked up once per call: a tuple of column positions, or None = all columns."""
     if treatment_for_gene is None:

@@ -461,15 +461,11 @@ def ht_1d_moments(adata, covariate, treatment, treatment_for_gene=None, inplace=
         g0, g1, G, bs, skip = c.g0, c.g1, c.G, c.bs, c.skip
         rep_assign = bcol_assign = None
         if not strict:
-            if shard_stream is not None:      # gene-sharded: this rank's slice of the ONE global stream (see above)
-                r1, r0 = shard_stream[0][g0 * ng:g1 * ng], shard_stream[1][g0 * ng:g1 * ng]
-            else:
-                r1, r0 = _ht.hash_uniforms(~skip, 2)
+            # gene-sharded: this rank's slice of the ONE global stream (see above)
+            uniforms = None if shard_stream is None else (shard_stream[0][g0 * ng:g1 * ng], shard_stream[1][g0 * ng:g1 * ng])
             keys = (fill_pos[g0:g1, None] * ng + np.arange(ng)[None, :]).reshape(-1)      # refill streams keyed by (gene, group)
             chain_keys = (chain_pos[g0:g1, None] * ng + np.arange(ng)[None, :]).reshape(-1)     # rng='fast' streams, likewise
-            n_inv = bs.run(skip, r1, r0, mv.fit, fill_mode=0, fill_seed=fill_seed, fast=(rng == 'fast'), mean_only=mv.mean_only,
-                           fill_keys=keys, chain_keys=chain_keys)                         # K6-K8
-            bad_fill = (n_inv < 0).any(axis=1)
+            good, n_inv = _ht.run_chunk_1d(c, mv, rng, fill_seed, keys, chain_keys, uniforms)    # K6-K8
             # how much of the result depends on the device refill (strict=True replays the reference's own _fill draws instead):
             # chains / genes with at least one refilled replicate -- all others are bit-identical to the strict path
             refilled = (n_inv > 0).any(axis=1) & ~skip
@@ -485,9 +481,8 @@ def ht_1d_moments(adata, covariate, treatment, treatment_for_gene=None, inplace=
             replay = _strict1d.StrictReplay(c, run_from, gene_trt)
             bad_fill = replay.run()
             rep_assign, bcol_assign = replay.rep_assign, replay.bcol_assign
-
-        active_all = (~skip) & (bs.K >= 2)                       # bootstrap.py:97-98: a single bin gives NaN replicates
-        good = (active_all & ~bad_fill).reshape(G, ng)           # hypothesis_test.py:193-200
+            active_all = (~skip) & (bs.K >= 2)                       # bootstrap.py:97-98: a single bin gives NaN replicates
+            good = (active_all & ~bad_fill).reshape(G, ng)           # hypothesis_test.py:193-200
         # tests: gene-major x treatment column (main.py:399-404)
         d = _ht.design_tables(good, gene_cols[g0:g1], cov, trt_all, mv.Nc_list, resampled=resample_rep)
         test_gene = d.test_row
@@ -632,20 +627,13 @@ def ht_1d_vs_control(adata, control, num_boot=10000, num_cpus=1, rng='replay', f
     st.last_bootstrap = st.last_good = None    # (see ht_1d_moments: free the previous call's replicate rows first)
 
     def run_chunk(c):
-        g0, g1, G, bs, skip = c.g0, c.g1, c.G, c.bs, c.skip
-        r1, r0 = _ht.hash_uniforms(~skip, 2)
-        keys = np.arange(g0 * ng, g1 * ng, dtype=np.int64)      # (g0 + gene) * ng + group: the chain's row in the one-chunk call
-        n_inv = bs.run(skip, r1, r0, mv.fit, fill_mode=0, fill_seed=fill_seed, fast=(rng == 'fast'), mean_only=mv.mean_only,
-                       fill_keys=keys, chain_keys=keys)
-        good = ((~skip) & (bs.K >= 2) & ~(n_inv < 0).any(axis=1)).reshape(G, ng)
+        G, bs = c.G, c.bs
+        keys = np.arange(c.g0 * ng, c.g1 * ng, dtype=np.int64)  # (g0 + gene) * ng + group: the chain's row in the one-chunk call
+        good, _ = _ht.run_chunk_1d(c, mv, rng, fill_seed, keys, keys)
         st.last_good = good                    # (diagnostics / tests: the good groups of the last gene chunk)
         test_gene = np.repeat(np.arange(G), len(tested))
-        if designs is None:
-            test_grp = np.tile(others, G)
-            st_m, st_v, rows = bs.contrast(test_gene, test_grp, ctrl, good)
-        else:
-            test_design = designs.tests(good)
-            st_m, st_v, rows = bs.contrast_design(test_gene, test_design, *designs.tables())
+        st_m, st_v, rows = (bs.contrast(test_gene, np.tile(others, G), ctrl, good) if designs is None
+                            else bs.contrast_design(test_gene, designs.tests(good), *designs.tables()))
         for tag, stt, which in (('mean', st_m, 0), ('var', st_v, 1)):
             p = _asl.asl_from_stats(stt, approx, lambda idx, w=which: rows(w, idx), num_cpus, resampling)
             cols[tag + '_coef'].append(stt[:, 0])
@@ -769,17 +757,13 @@ def ht_1d_joint(adata, treatment, covariate=None, num_boot=10000, rng='replay', 
     st.last_bootstrap = st.last_good = None    # (see ht_1d_moments: free the previous call's replicate rows first)
 
     def run_chunk(c):
-        g0, g1, G, bs, skip = c.g0, c.g1, c.G, c.bs, c.skip
-        r1, r0 = _ht.hash_uniforms(~skip, 2)
+        g0, g1 = c.g0, c.g1
         keys = (fill_pos[g0:g1, None] * ng + np.arange(ng)[None, :]).reshape(-1)
-        chain_keys = np.arange(g0 * ng, g1 * ng, dtype=np.int64)
-        n_inv = bs.run(skip, r1, r0, mv.fit, fill_mode=0, fill_seed=fill_seed, fast=(rng == 'fast'), mean_only=mv.mean_only,
-                       fill_keys=keys, chain_keys=chain_keys)
-        good = ((~skip) & (bs.K >= 2) & ~(n_inv < 0).any(axis=1)).reshape(G, ng)
+        good, _ = _ht.run_chunk_1d(c, mv, rng, fill_seed, keys, np.arange(g0 * ng, g1 * ng, dtype=np.int64))
         st.last_good = good
         tables = _ht.joint_tables(good, cov, trt, mv.Nc_list)
         st.last_joint_tables = tables          # (diagnostics / tests: the designs of the last gene chunk)
-        st_m, st_v = bs.joint(np.arange(G), tables)
+        st_m, st_v = c.bs.joint(np.arange(c.G), tables)
         for tag, stt in (('mean', st_m), ('var', st_v)):
             cols[tag + '_stat'].append(stt[:, 0])
             cols[tag + '_asl'].append(joint_pvalues(stt, approx))
@@ -1025,11 +1009,6 @@ def ht_2d_vs_control(adata, control, num_boot=10000, num_cpus=1, fill_seed=0, ma
     st = m['_hip']
     st.last_bootstrap2d = None                 # (free the previous call's replicate rows before this call allocates its own)
     tested, designs, (ctrl, others), meta = _vs_control_plan(m, control, treatment_col)
-    if designs is None:
-        # design k = {(guide k, +1), (control, -1)}; the last design is empty (a guide or the control is not good -> NaN test)
-        plain_ptr = np.concatenate([2 * np.arange(len(others) + 1), [2 * len(others)]]).astype(np.int32)
-        plain_grp = np.column_stack([others, np.full(len(others), ctrl)]).reshape(-1).astype(np.int32)
-        plain_w = np.tile([1.0, -1.0], len(others))
     n_t = len(tested)
     plan = _ht.pair_plan(m, st, num_boot, max_rows)
     uniforms = _ht.hash_uniforms(~plan.skip.reshape(-1), 3)
@@ -1039,12 +1018,8 @@ def ht_2d_vs_control(adata, control, num_boot=10000, num_cpus=1, fill_seed=0, ma
     def run_chunk(c):
         good = _ht.run_chunk_2d(c, plan, uniforms, rng, fill_seed)                 # device order
         test_pair = np.repeat(np.arange(c.n_ch), n_t)     # pair-major: a pair's control rows stay in L2 for its consecutive guides
-        if designs is None:
-            both = good[:, others] & good[:, [ctrl]]
-            test_design = np.where(both, np.arange(n_t)[None, :], n_t).reshape(-1)
-            stt, rows = c.bs.contrast_design(test_pair, test_design, plain_ptr, plain_grp, plain_w)
-        else:
-            stt, rows = c.bs.contrast_design(test_pair, designs.tests(good), *designs.tables())
+        stt, rows = (c.bs.contrast(test_pair, np.tile(others, c.n_ch), ctrl, good) if designs is None
+                     else c.bs.contrast_design(test_pair, designs.tests(good), *designs.tables()))
         pvals = _asl.asl_from_stats(stt, approx, rows, num_cpus, resampling)
         for key, src in (('corr_coef', stt[:, 0]), ('corr_se', stt[:, 1]), ('corr_asl', pvals)):
             _ht.scatter_pairs(c, plan, out[key], src)

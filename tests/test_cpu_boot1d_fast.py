@@ -34,15 +34,21 @@ def test_cabi_declares_and_binds_the_keyed_fast_1d_bootstrap():
 
 
 def test_both_api_calls_pass_chain_keys():
-    """Neither call reaches Bootstrap1D.run without a device, so this reads the calls: each hands ``chain_keys`` (and ``fill_keys``)
-    to its one non-strict ``bs.run``."""
-    from scrna_parameter_estimation_amd.memento import main
+    """Neither call reaches Bootstrap1D.run without a device, so this reads the calls: each hands its ``fill_keys`` and ``chain_keys``
+    to its one ``_ht.run_chunk_1d``, whose one ``bs.run`` (the non-strict one, ``fill_mode=0``) passes them on."""
+    from scrna_parameter_estimation_amd.memento import _ht, main
 
+    src = inspect.getsource(_ht.run_chunk_1d)
+    assert src.startswith("def run_chunk_1d(c, mv, rng, fill_seed, fill_keys, chain_keys, uniforms=None):")
+    calls = [c for c in re.findall(r"bs\.run\(([^#]*?)\)\s", src, flags=re.S) if "fill_mode=0" in c]
+    assert len(calls) == 1
+    assert "fill_keys=fill_keys" in calls[0] and "chain_keys=chain_keys" in calls[0] and "fast=(rng == 'fast')" in calls[0]
     for fn in (main.ht_1d_moments, main.ht_1d_vs_control):
         src = inspect.getsource(fn)
-        calls = [c for c in re.findall(r"bs\.run\(([^#]*?)\)\s", src, flags=re.S) if "fill_mode=0" in c]
+        assert not [c for c in re.findall(r"bs\.run\(([^#]*?)\)\s", src, flags=re.S) if "fill_mode=0" in c], fn.__name__
+        calls = re.findall(r"_ht\.run_chunk_1d\(([^#]*?)\)\s", src, flags=re.S)
         assert len(calls) == 1, fn.__name__
-        assert re.search(r"\bfill_keys=\w+", calls[0]) and re.search(r"\bchain_keys=\w+", calls[0]), fn.__name__
-        assert "fast=(rng == 'fast')" in calls[0]
+        assert re.fullmatch(r"c, mv, rng, fill_seed, \w+, \w+(, uniforms)?", calls[0]), fn.__name__
     src = inspect.getsource(main.ht_1d_vs_control)
-    assert "keys = np.arange(g0 * ng, g1 * ng, dtype=np.int64)" in src and "fill_keys=keys, chain_keys=keys" in src
+    assert "keys = np.arange(c.g0 * ng, c.g1 * ng, dtype=np.int64)" in src and "run_chunk_1d(c, mv, rng, fill_seed, keys, keys)" in src
+    assert "run_chunk_1d(c, mv, rng, fill_seed, keys, chain_keys, uniforms)" in inspect.getsource(main.ht_1d_moments)

@@ -1,5 +1,6 @@
 """The last stage on synthetic replicate planes: mm_boot_fill_log (K8), the contractions and the 8-double test record
-(mm_contract_stats, mm_contrast_stats / mm_contrast_rows, K9+K10) and the resample_rep helpers (mm_valid_cols, mm_residualize,
+(mm_contract_stats; the plain two-group ``contrast`` of Bootstrap1D / Bootstrap2D, which runs the two-entry designs
+{(group, +1), (control, -1)} through mm_contrast_design_stats / _rows and their one-plane twins; K9+K10) and the resample_rep helpers (mm_valid_cols, mm_residualize,
 mm_cross_resampled), each against a plain numpy restatement (tests/_replicate_ref.py) at the sizes where the kernels change
 path: one replicate, one short of / exactly / one past a wave and a 256-thread workgroup, several tiles, more groups than
 threads.  The planes are hand-built: every kernel here takes plain [rows][ld] fp64 planes."""
@@ -297,7 +298,7 @@ def test_refill_streams_are_keyed_by_seed_key_and_plane(eng):
 
 
 # -------------------------------------------------------------------------------------------------
-# B. the test record: mm_contract_stats, mm_contrast_stats, mm_contrast_rows
+# B. the test record: mm_contract_stats, and the plain two-group contrast on the design kernels
 # -------------------------------------------------------------------------------------------------
 
 
@@ -346,9 +347,10 @@ def _check_contract(eng, ym, yv, B, ng, good, test_gene, W):
 
 
 def _check_contrast(eng, ym, yv, B, ng, good, test_gene, test_grp, ctrl):
-    """Bootstrap1D.contrast: both records of mm_contrast_stats and both rows(which, ...) of mm_contrast_rows; a column is
-    valid when all four operands are finite.  A bad guide or control group gives the NaN record; mm_contrast_rows does not
-    take the mask and writes the difference row all the same."""
+    """Bootstrap1D.contrast: both records and both rows(which, ...); a column is valid when all four operands are finite.  A
+    bad guide or control group gives the NaN record; rows does not take the mask and gives the difference row all the same.
+    The rows are the IEEE difference y[a] - y[c] bit for bit (up to the sign of an exact zero, which assert_array_equal
+    does not see): (0.0 + 1.0 * a) + (-1.0 * b), unfused, is a - b."""
     bs = _planes(eng, ym, yv, B, ng)
     st_m, st_v, rows_of = bs.contrast(test_gene, test_grp, ctrl, good)
     idx = np.arange(len(test_gene))
@@ -362,7 +364,7 @@ def _check_contrast(eng, ym, yv, B, ng, good, test_gene, test_grp, ctrl):
             with np.errstate(invalid="ignore"):
                 want_row = np.where(ok, y[a, :B + 1] - y[c, :B + 1], np.nan)
             msg = f"which {which} test {t}"
-            np.testing.assert_allclose(rows[t, :B + 1], want_row, rtol=1e-13, atol=1e-13, equal_nan=True, err_msg=msg)
+            np.testing.assert_array_equal(rows[t, :B + 1], want_row, err_msg=msg)
             nothing = not (good[gene, grp] and good[gene, ctrl])
             _assert_record(st[t], want_row, nothing_to_test=nothing, msg=msg)
             n_nan += int(nothing)
@@ -423,6 +425,69 @@ def test_contrast_records_and_rows_against_numpy(eng, B):
     test_gene = np.array([0, 0, 0, 0, 1, 1, 1, 2, 2, 3, 3, 4, 4, 4, 1, 0])
     test_grp = np.array([0, 1, 2, 5, 0, 2, 3, 0, 5, 4, 1, 1, 0, 5, 4, 3])     # a bad guide, a bad control, guide == control
     assert _check_contrast(eng, ym, yv, B, ng, good, test_gene, test_grp, ctrl) == 2 * 6
+
+
+def _plane(eng, yc, B, ng):
+    """A Bootstrap2D that only holds replicate rows: one plane [pair * ng + group][ld]."""
+    bs = object.__new__(eng.Bootstrap2D)
+    bs.yc, bs.ld, bs.B, bs.ng, bs.n_q = eng.dev(yc), yc.shape[1], B, ng, yc.shape[0]
+    bs.n_pairs = yc.shape[0] // ng
+    return bs
+
+
+@pytest.mark.parametrize("B", [1, 256, 257])
+def test_one_plane_contrast_records_and_rows_against_numpy(eng, B):
+    """Bootstrap2D.contrast, the one-plane mirror of the test above: the mean plane of _stat_planes as the correlation rows of 5
+    pairs.  A column is valid when the guide's and the control's entries are finite; the rows are the IEEE difference; a masked
+    test has the NaN record and the rows that contrast_design gives for its unmasked design."""
+    ng, n_pairs, ctrl = 6, 5, 4
+    y, _, good = _stat_planes(B, ng, n_pairs, seed=400 + B)
+    test_pair = np.array([0, 0, 0, 0, 1, 1, 1, 2, 2, 3, 3, 4, 4, 4, 1, 0])
+    test_grp = np.array([0, 1, 2, 5, 0, 2, 3, 0, 5, 4, 1, 1, 0, 5, 4, 3])     # a bad guide, a bad control, guide == control
+    bs = _plane(eng, y, B, ng)
+    stats, rows_of = bs.contrast(test_pair, test_grp, ctrl, good)
+    idx = np.arange(len(test_pair))
+    rows = rows_of(idx)
+    assert stats.shape == (len(test_pair), 8) and rows.shape == (len(test_pair), y.shape[1])
+    n_nan = 0
+    for t, (pair, grp) in enumerate(zip(test_pair, test_grp)):
+        a, c = pair * ng + grp, pair * ng + ctrl
+        ok = np.isfinite(y[[a, c], :B + 1]).all(axis=0)
+        with np.errstate(invalid="ignore"):
+            want_row = np.where(ok, y[a, :B + 1] - y[c, :B + 1], np.nan)
+        np.testing.assert_array_equal(rows[t, :B + 1], want_row, err_msg=f"test {t}")
+        nothing = not (good[pair, grp] and good[pair, ctrl])
+        _assert_record(stats[t], want_row, nothing_to_test=nothing, msg=f"test {t}")
+        n_nan += int(nothing)
+    assert n_nan == 6
+    np.testing.assert_array_equal(rows_of([3, 0])[:, :B + 1], rows[[3, 0], :B + 1])
+    # the unmasked designs, built here: design j = {(j, +1), (ctrl, -1)}
+    ptr = 2 * np.arange(ng + 1)
+    dgrp = np.stack([np.arange(ng), np.full(ng, ctrl)], axis=1).reshape(-1)
+    st_all, rows_all = bs.contrast_design(test_pair, test_grp, ptr, dgrp, np.tile([1.0, -1.0], ng))
+    np.testing.assert_array_equal(_bits(rows[:, :B + 1]), _bits(rows_all(idx)[:, :B + 1]))        # (the padding is not written)
+    live = good[test_pair, test_grp] & good[test_pair, ctrl]
+    np.testing.assert_array_equal(_bits(stats[live]), _bits(st_all[live]))
+
+
+@pytest.mark.parametrize("plane", ["two planes", "one plane"])
+def test_contrast_refuses_groups_out_of_range(eng, monkeypatch, plane):
+    """``ctrl`` or an entry of ``test_grp`` outside [0, ng): ValueError, and nothing is launched."""
+    B, ng, n = 5, 6, 5
+    ym, yv, good = _stat_planes(B, ng, n, seed=7)
+    bs = _planes(eng, ym, yv, B, ng) if plane == "two planes" else _plane(eng, ym, B, ng)
+
+    def no_launch(name, *args):
+        raise AssertionError(f"{name} was called")
+
+    monkeypatch.setattr(eng._lib, "call", no_launch)
+    rows, grps = np.array([0, 1, 2]), np.array([0, 5, 2])
+    for ctrl in (-1, ng, ng + 7):
+        with pytest.raises(ValueError, match="contrast:"):
+            bs.contrast(rows, grps, ctrl, good)
+    for bad in (-1, ng, 2 ** 20):
+        with pytest.raises(ValueError, match="contrast:"):
+            bs.contrast(rows, np.array([0, bad, 2]), 4, good)
 
 
 def test_records_at_exact_ties(eng):

@@ -198,7 +198,7 @@ print("ok")
 
 
 def _np_stats(row):
-    """The 8-double record of k_contrast_stats / k_contract_stats restated in numpy for one coefficient row (NaN = dropped)."""
+    """The 8-double record of k_contrast_design_stats / k_contract_stats restated in numpy for one coefficient row (NaN = dropped)."""
     c0 = row[0]
     ok = np.isfinite(row)
     v = row[1:][ok[1:]]
