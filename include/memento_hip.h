@@ -208,7 +208,8 @@ int mm_debug_replay_arith(int32_t exact);
  * for every pair, bootstrap.py:102).  pcg_state = {state_hi, state_lo, inc_hi, inc_lo}.
  * d_slot_nobs = N_g, d_slot_omq = 1 - q_g of the slot's group.
  * Writes mean_b / var_b to d_out_mean[row*ld + 1 + b], row = d_slot_row[slot]; K == 1 pairs get NaN rows.
- * d_w_dump (optional, NULL in production) receives the int32 weights [slot][k][b] with stride kmax_dump. */
+ * d_w_dump (optional, NULL in production) receives the int32 weights [slot][k][b] with stride kmax_dump: every k < K of an active
+ * slot is written (0 behind the bin where a replicate's cells ran out), nothing else is. */
 /* Optional argument of mm_boot1d_replay: tiles that are really chains of the one-wave-per-chain form (see mm_boot1d_chain, whose
  * operand records, per-chain arrays and jump table these are).  d_tile_chain[tile] = chain index or -1; a flagged tile owns no
  * bin rows (tile_ptr[t + 1] == tile_ptr[t]) and its wave runs the chain instead -- at the tile's place in the launch's dispatch
@@ -237,7 +238,9 @@ int mm_boot1d_replay(const double *d_pk, const double *d_lq, const double *d_v, 
  * d_recs; d_slot_rec[s] < 0 or d_slot_K[s] <= 0 = unused lane.  The lanes of a tile share the instruction stream only: a BTPE draw makes
  * one attempt per bin step and a rejected lane retries in the next, a lane that finishes a replicate starts its next one at once.  Same
  * draws, replicate means and variances as mm_boot1d_replay, bit for bit.  ``chains`` as there (tiles that are one-wave-per-chain chains).
- * d_w_dump (optional): int32 weights [slot][k][b], stride kmax_dump. */
+ * d_w_dump (optional): int32 weights [slot][k][b], stride kmax_dump; as in mm_boot1d_replay every k < K of an active slot is written
+ * (0 behind the bin where a replicate's cells ran out), nothing else is.  The weights of a tile that is a chain go to
+ * chains->d_w_dump, [chain][k][b] with stride chains->kmax_dump, under mm_boot1d_chain's rule. */
 int mm_boot1d_free(const double *d_recs, const int64_t *d_slot_rec, int64_t n_tiles, const int32_t *d_slot_K, const double *d_slot_nobs,
                    const double *d_slot_omq, const int64_t *d_slot_row, const uint64_t pcg_state[4], int32_t num_boot, int32_t mean_only,
                    int64_t ld, double *d_out_mean, double *d_out_var, int32_t *d_w_dump, int32_t kmax_dump, const mm_chain_tiles *chains,
@@ -252,7 +255,8 @@ int mm_pcg64_stream(const uint64_t pcg_state[4], int64_t n, double *d_out, void 
  * {A^(lane+1) hi, lo, C_(lane+1) hi, lo} for the stream's increment) and the wave-uniform samplers consume them in order.
  * Draws, replicate means and variances are bit-identical to mm_boot1d_replay's.  Operands: 8-double records written by
  * mm_bins_order for MM_CHAIN_SLOT pairs; chain c reads records [d_ch_base[c], d_ch_base[c] + d_ch_K[c]) of d_ops, needs
- * d_ch_K[c] >= 2, and writes row d_ch_row[c].  d_w_dump (optional) receives int32 weights [chain][k][b], stride kmax_dump. */
+ * d_ch_K[c] >= 2, and writes row d_ch_row[c].  d_w_dump (optional) receives int32 weights [chain][k][b], stride kmax_dump.  The
+ * bins BEHIND the one where a replicate's cells ran out are not written (numpy stops the chain there): the caller zeroes the buffer. */
 int mm_boot1d_chain(const double *d_ops, const int64_t *d_ch_base, const int32_t *d_ch_K, const double *d_ch_nobs,
                     const double *d_ch_omq, const int64_t *d_ch_row, int64_t n_chains, const uint64_t *d_jump /* [64][4] */,
                     const uint64_t pcg_state[4], int32_t num_boot, int32_t mean_only, int64_t ld, double *d_out_mean,
@@ -263,7 +267,9 @@ int mm_boot1d_chain(const double *d_ops, const int64_t *d_ch_base, const int32_t
  * for the lanes that are in it), so no lane waits for the longest search, the unluckiest BTPE draw or the longest chain of its
  * wave.  Slot s = 64 * wave + lane runs chain s: records [d_ch_base[s], d_ch_base[s] + d_ch_K[s]) of d_ops (the 8-double records
  * mm_bins_order writes for MM_CHAIN_SLOT pairs), row d_ch_row[s]; d_ch_K[s] < 2 = unused lane.  Same draws and replicate moments
- * as mm_boot1d_replay, bit for bit.  d_w_dump (optional): int32 weights [slot][k][b], stride kmax_dump. */
+ * as mm_boot1d_replay, bit for bit.  d_w_dump (optional): int32 weights [slot][k][b], stride kmax_dump.  As in mm_boot1d_chain the
+ * bins behind the one where a replicate's cells ran out are not written: the caller zeroes the buffer.  (d_ch_row is not
+ * looked at for an unused lane, and a K == 1 lane is unused here: its NaN row is the caller's.) */
 int mm_boot1d_async(const double *d_ops, const int64_t *d_ch_base, const int32_t *d_ch_K, const double *d_ch_nobs,
                     const double *d_ch_omq, const int64_t *d_ch_row, int64_t n_slots, const uint64_t pcg_state[4], int32_t num_boot,
                     int32_t mean_only, int64_t ld, double *d_out_mean, double *d_out_var, int32_t *d_w_dump, int32_t kmax_dump,
