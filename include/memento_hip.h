@@ -391,6 +391,29 @@ int mm_contrast_design1_rows(const double *d_y, int64_t ld, int32_t num_boot, in
                              const int32_t *d_test_design, const int32_t *d_design_ptr, const int32_t *d_design_grp,
                              const double *d_design_w, int64_t n_tests, double *d_out, void *stream);
 
+/* ---- single-step max-T adjustment over families of design contrasts (ht_1d_posthoc) ---------------------------------
+ * Family f is the tests [family_ptr[f], family_ptr[f + 1]) of the test arrays: consecutive, sharing one row block
+ * d_test_gene, each with its design as in mm_contrast_design_stats (coef_j[c] through the same routine: p ascending, unfused).
+ * d_scale [test][2] (mean, variability plane): 1 / se of the member's record, or 0 for a member without a test.  Per plane,
+ * member j is INCLUDED when its scale is a finite number > 0 and its column 0 is valid; column c >= 1 is FAMILY-VALID when every
+ * included member is valid at c (every listed group finite in BOTH planes).  Over the family-valid columns and the included
+ * members, j ascending:
+ *   M[c] = max_j |coef_j[c] - coef_j[0]| * scale_j,   t0_j = |coef_j[0]| * scale_j,   n_adj_j = #{ c : M[c] > t0_j }   (strict)
+ * so that p_adj_j = (1 + n_adj_j) / (1 + n_valid_family) is the single-step max-T (Westfall-Young) adjusted p-value of member j
+ * within its family.  Outputs:
+ *   d_maxrow [n_fam][2][ld]   M, NaN in column 0 and in the columns that are not family-valid; the padding beyond num_boot is
+ *                             not written (mm_row_quantiles on these rows gives the critical value of the simultaneous interval)
+ *   d_adj    [n_tests][2][2]  (t0, n_adj); (NaN, 0) for a member that is not included
+ *   d_fam    [n_fam][2][2]    (n_valid_family, n_included); an empty family or one without an included member has (0, 0) and
+ *                             an all-NaN row
+ * coef_j[0] and scale_j of a family's first stage_cap members (0 <= stage_cap <= 1024) are staged in LDS, those of the members
+ * beyond come back from global memory: the outputs are the same bit for bit.  One workgroup per family; n_fam == 0 is a no-op.
+ * The tables are trusted: validate them on the host (engine._family_tables). */
+int mm_family_maxt(const double *d_ym, const double *d_yv, int64_t ld, int32_t num_boot, int32_t n_groups, const int32_t *d_family_ptr,
+                   const int32_t *d_test_gene, const int32_t *d_test_design, const int32_t *d_design_ptr, const int32_t *d_design_grp,
+                   const double *d_design_w, const double *d_scale, int32_t stage_cap, int64_t n_fam, double *d_maxrow, double *d_adj,
+                   double *d_fam, void *stream);
+
 /* ---- joint test of a block of treatment columns (ht_1d_joint) ------------------------------------------------------
  * test t applies the r = design_rank[d] linear forms of design d = test_design[t] to every replicate column of gene
  * test_gene[t]: L [r][n_d] row-major at d_design_L + design_lofs[d], over the n_d groups

@@ -474,6 +474,137 @@ __global__ __launch_bounds__(256) void k_contrast_design1_rows(const double *__r
 }
 
 // ------------------------------------------------------------------------------------------------
+// Single-step max-T adjustment over a FAMILY of design contrasts (ht_1d_posthoc): the tests [family_ptr[f], family_ptr[f + 1]) are the
+// m members of family f; they share the row block test_row and each has its design, as in k_contrast_design_stats.  Every (row,
+// group) chain is bootstrapped once, so replicate column c of all members is one joint draw of the whole family, and
+//   M[c] = max_j |coef_j[c] - coef_j[0]| * scale_j,   t0_j = |coef_j[0]| * scale_j,   n_adj_j = #{ family-valid c : M[c] > t0_j }
+// per plane (Westfall-Young within the family; the host forms p_adj_j = (1 + n_adj_j) / (1 + n_valid_family)).  Member j is INCLUDED
+// on a plane when its scale there is a finite number > 0 and its column 0 is valid (the host passes 1 / se, and 0 for a member
+// without a test); the others get t0 = NaN, n_adj = 0 and do not enter the maximum.  Column c >= 1 is family-valid on a plane when
+// every member included there is valid at c (design_coef's verdict: every listed group finite in EVERY plane), so the maximum
+// runs over the same members in every column, j ascending.  One workgroup per family, in three steps:
+//   1  threads over members: coef_j[0] through design_coef (the arithmetic of the records), t0 and the effective scale; the first
+//      stage_cap members keep (coef0, scale) in LDS, every member keeps (t0, coef0) in its adj cells, which the members beyond
+//      stage_cap are read back from: the same doubles, so the outputs do not depend on stage_cap;
+//   2  threads over columns: the maximum row, stored (column 0 and the invalid columns NaN), and n_valid_family;
+//   3  waves over blocks of FM_BLOCK members, lanes over columns: the counts from the stored row, FM_BLOCK comparisons per
+//      element read, summed by ballots -- no reduction across waves; the count replaces coef0 in the adj cell.
+#define FM_BLOCK 8
+#define FM_MAX_STAGED 1024      // 32 KB of LDS at two planes: four workgroups a CU (a choice, not a measurement)
+
+// y[k]: plane k; sm: LDS [2][NP][stage_cap] (coef0, then scale); maxrow [NP][ld], adj [m][NP][2] and fam [NP][2] of THIS family
+template <int NP>
+__device__ __forceinline__ void family_maxt(const double *const (&y)[NP], int64_t ld, int32_t num_boot, int32_t n_groups, int row, int t0,
+                                            int m, const int32_t *__restrict__ test_design, const int32_t *__restrict__ design_ptr,
+                                            const int32_t *__restrict__ design_grp, const double *__restrict__ design_w,
+                                            const double *__restrict__ scale, int32_t stage_cap, double *__restrict__ maxrow,
+                                            double *__restrict__ adj, double *__restrict__ fam, double *sm, double *red) {
+  double *c0s = sm, *scs = sm + NP * (int64_t)stage_cap;
+  const int64_t row_base = (int64_t)row * n_groups;
+  // step 1
+  double ninc[NP];
+  for (int k = 0; k < NP; k++) ninc[k] = 0.0;
+  for (int j = threadIdx.x; j < m; j += K9_THREADS) {
+    int d = test_design[t0 + j];
+    int p0 = design_ptr[d], p1 = design_ptr[d + 1];
+    double v[NP];
+    bool good = design_coef<NP>(y, ld, row_base, design_grp, design_w, p0, p1, 0, v) && p1 > p0;
+    for (int k = 0; k < NP; k++) {
+      double s = scale[(int64_t)(t0 + j) * NP + k];
+      bool inc = good && isfinite(v[k]) && isfinite(s) && s > 0.0;
+      double se = inc ? s : 0.0;
+      adj[((int64_t)j * NP + k) * 2] = inc ? fabs(v[k]) * se : NAN;
+      adj[((int64_t)j * NP + k) * 2 + 1] = v[k];
+      if (j < stage_cap) { c0s[k * stage_cap + j] = v[k]; scs[k * stage_cap + j] = se; }
+      if (inc) ninc[k] += 1.0;
+    }
+  }
+  __threadfence_block();
+  for (int k = 0; k < NP; k++) ninc[k] = wg_sum(ninc[k], red);      // (its barriers also publish the LDS and the adj cells)
+  // step 2
+  double nval[NP];
+  for (int k = 0; k < NP; k++) nval[k] = 0.0;
+  for (int c = threadIdx.x; c <= num_boot; c += K9_THREADS) {
+    double mx[NP];
+    bool ok[NP];
+    for (int k = 0; k < NP; k++) { mx[k] = -INFINITY; ok[k] = c > 0 && ninc[k] > 0.0; }
+    for (int j = 0; j < m && c > 0; j++) {
+      double c0[NP], sc[NP];
+      bool any = false;
+      for (int k = 0; k < NP; k++) {
+        if (j < stage_cap) { c0[k] = c0s[k * stage_cap + j]; sc[k] = scs[k * stage_cap + j]; }
+        else {
+          const double *a = adj + ((int64_t)j * NP + k) * 2;
+          c0[k] = a[1];
+          sc[k] = a[0] == a[0] ? scale[(int64_t)(t0 + j) * NP + k] : 0.0;
+        }
+        any = any || sc[k] > 0.0;
+      }
+      if (!any) continue;
+      int d = test_design[t0 + j];
+      double v[NP];
+      bool good = design_coef<NP>(y, ld, row_base, design_grp, design_w, design_ptr[d], design_ptr[d + 1], c, v);
+      for (int k = 0; k < NP; k++) {
+        if (sc[k] > 0.0) {
+          ok[k] = ok[k] && good;
+          mx[k] = fmax(mx[k], fabs(v[k] - c0[k]) * sc[k]);
+        }
+      }
+    }
+    for (int k = 0; k < NP; k++) {
+      maxrow[k * ld + c] = ok[k] ? mx[k] : NAN;
+      if (ok[k]) nval[k] += 1.0;
+    }
+  }
+  __threadfence_block();
+  for (int k = 0; k < NP; k++) nval[k] = wg_sum(nval[k], red);      // (its barriers also publish the row)
+  if (threadIdx.x == 0)
+    for (int k = 0; k < NP; k++) { fam[k * 2] = nval[k]; fam[k * 2 + 1] = ninc[k]; }
+  // step 3
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int j0 = wave * FM_BLOCK; j0 < m; j0 += FM_BLOCK * (K9_THREADS / 64)) {
+    for (int k = 0; k < NP; k++) {
+      double t[FM_BLOCK];
+      uint32_t cnt[FM_BLOCK];
+#pragma unroll
+      for (int i = 0; i < FM_BLOCK; i++) {
+        t[i] = j0 + i < m ? adj[((int64_t)(j0 + i) * NP + k) * 2] : NAN;
+        cnt[i] = 0;
+      }
+      const double *r = maxrow + k * ld;
+      for (int cb = 1; cb <= num_boot; cb += 64) {
+        int c = cb + lane;
+        double x = c <= num_boot ? r[c] : NAN;
+#pragma unroll
+        for (int i = 0; i < FM_BLOCK; i++) cnt[i] += (uint32_t)__popcll(__ballot(x > t[i]));      // (NaN on either side: not counted)
+      }
+      if (lane == 0) {
+#pragma unroll
+        for (int i = 0; i < FM_BLOCK; i++)
+          if (j0 + i < m) adj[((int64_t)(j0 + i) * NP + k) * 2 + 1] = (double)cnt[i];
+      }
+    }
+  }
+}
+
+__global__ __launch_bounds__(K9_THREADS) void k_family_maxt(const double *__restrict__ ym, const double *__restrict__ yv, int64_t ld,
+                                                            int32_t num_boot, int32_t n_groups, const int32_t *__restrict__ family_ptr,
+                                                            const int32_t *__restrict__ test_row, const int32_t *__restrict__ test_design,
+                                                            const int32_t *__restrict__ design_ptr, const int32_t *__restrict__ design_grp,
+                                                            const double *__restrict__ design_w, const double *__restrict__ scale,
+                                                            int32_t stage_cap, double *__restrict__ maxrow, double *__restrict__ adj,
+                                                            double *__restrict__ fam) {
+  extern __shared__ double sm[];
+  __shared__ double red[K9_THREADS / 64];
+  int64_t f = blockIdx.x;
+  int t0 = family_ptr[f], m = family_ptr[f + 1] - t0;
+  const double *const y[2] = {ym, yv};
+  // (an empty family has no test to take its row block from: row 0 is never read, m == 0 leaves the NaN row and the zero counts)
+  family_maxt<2>(y, ld, num_boot, n_groups, m > 0 ? test_row[t0] : 0, t0, m, test_design, design_ptr, design_grp, design_w, scale, stage_cap,
+                 maxrow + f * 2 * ld, adj + (int64_t)t0 * 4, fam + f * 4, sm, red);
+}
+
+// ------------------------------------------------------------------------------------------------
 // Joint test of a block of treatment columns (ht_1d_joint): test t applies the r linear forms of design d = test_design[t] --
 // L [r][n_d] row-major at design_L + design_lofs[d], over the n_d groups design_grp[design_ptr[d] .. design_ptr[d + 1]) -- to
 // every replicate column of gene test_gene[t] and reduces the quadratic statistic
@@ -972,6 +1103,22 @@ int mm_contrast_design1_rows(const double *d_y, int64_t ld, int32_t num_boot, in
   if (rc != MM_OK || n_tests == 0) return rc;
   hipLaunchKernelGGL(k_contrast_design1_rows, dim3((unsigned)n_tests), dim3(256), 0, (hipStream_t)stream, d_y, ld, num_boot, n_groups,
                      d_test_row, d_test_design, d_design_ptr, d_design_grp, d_design_w, d_out);
+  MM_LAUNCH_CHECK();
+  return MM_OK;
+}
+
+int mm_family_maxt(const double *d_ym, const double *d_yv, int64_t ld, int32_t num_boot, int32_t n_groups, const int32_t *d_family_ptr,
+                   const int32_t *d_test_gene, const int32_t *d_test_design, const int32_t *d_design_ptr, const int32_t *d_design_grp,
+                   const double *d_design_w, const double *d_scale, int32_t stage_cap, int64_t n_fam, double *d_maxrow, double *d_adj,
+                   double *d_fam, void *stream) {
+  MM_ARG(n_fam >= 0 && n_fam < 2147483647LL && stage_cap >= 0 && stage_cap <= FM_MAX_STAGED);
+  int rc = design_args(d_ym && d_yv && d_family_ptr && d_scale && d_maxrow && d_adj && d_fam, ld, num_boot, n_groups, d_test_gene,
+                       d_test_design, d_design_ptr, d_design_grp, d_design_w, 0);
+  if (rc != MM_OK || n_fam == 0) return rc;
+  size_t shm = (size_t)stage_cap * 2 * 2 * 8;
+  hipLaunchKernelGGL(k_family_maxt, dim3((unsigned)n_fam), dim3(K9_THREADS), shm, (hipStream_t)stream, d_ym, d_yv, ld, num_boot, n_groups,
+                     d_family_ptr, d_test_gene, d_test_design, d_design_ptr, d_design_grp, d_design_w, d_scale, stage_cap, d_maxrow, d_adj,
+                     d_fam);
   MM_LAUNCH_CHECK();
   return MM_OK;
 }

@@ -1014,6 +1014,30 @@ class Bootstrap1D:
                                               design_grp, design_w)
         return st_m, st_v, rows
 
+    def family_maxt(self, family_ptr, test_gene, test_design, design_ptr, design_grp, design_w, scale, stage_cap=None):
+        """Single-step max-T adjustment over families of design contrasts (mm_family_maxt): the tests
+        ``family_ptr[f]:family_ptr[f + 1]`` -- consecutive, on one gene -- are family f, with the tables of ``contrast_design``, and
+        ``scale`` [test][2] holds 1 / se of every member on the mean and the variability plane, 0 for a member without a test
+        (``family_scale`` of its records).  ``stage_cap``: how many members of a family keep their (coef0, scale) in LDS (default:
+        the largest family, at most ``FAMILY_MAX_STAGED``); no number depends on it.  Returns ``maxrow`` (device [n_fam][2][ld]:
+        the maximum row of every family and plane, NaN in column 0 and the columns that are not family-valid), ``adj`` (host
+        [n_tests][2][2]: t0, n_adj) and ``fam`` (host [n_fam][2][2]: n_valid_family, n_included)."""
+        torch = _torch()
+        family_ptr, scale, d_tab = _family_tables(family_ptr, test_gene, test_design, design_ptr, design_grp, design_w, scale, self.n_tested,
+                                                  self.ng)
+        n_fam, n_tests = len(family_ptr) - 1, len(scale)
+        if stage_cap is None:
+            stage_cap = min(FAMILY_MAX_STAGED, int(np.diff(family_ptr).max()) if n_fam else 0)
+        if not 0 <= int(stage_cap) <= FAMILY_MAX_STAGED:
+            raise ValueError(f"family_maxt: stage_cap must lie in [0, {FAMILY_MAX_STAGED}]")
+        maxrow = empty((max(1, n_fam), 2, self.ld), torch.float64)
+        adj = empty((max(1, n_tests), 2, 2), torch.float64)
+        fam = empty((max(1, n_fam), 2, 2), torch.float64)
+        d_fp, d_scale = dev(family_ptr), _up(scale.reshape(-1))
+        _lib.call("mm_family_maxt", P(self.ym), P(self.yv), self.ld, self.B, self.ng, P(d_fp), *map(P, d_tab), P(d_scale), int(stage_cap),
+                  n_fam, P(maxrow), P(adj), P(fam), _stream())
+        return maxrow[:n_fam], host(adj)[:n_tests], host(fam)[:n_fam]
+
     def joint(self, test_gene, tables):
         """Joint tests of a treatment block (mm_joint_stats): test t applies the linear forms of design ``tables.test_design[t]``
         (``memento._ht.joint_tables``: ``design_ptr``, ``design_rank``, ``design_lofs``, ``design_grp``, ``design_L``) to the
@@ -1082,16 +1106,55 @@ def _csr_tables(what, test_row, test_design, design_ptr, design_grp, n_rows, ng)
     return test_row, test_design, design_ptr, design_grp
 
 
-def _design_tables(test_row, test_design, design_ptr, design_grp, design_w, n_rows, ng):
+def _design_tables(test_row, test_design, design_ptr, design_grp, design_w, n_rows, ng, what="contrast_design", check=None):
     """The tables of the design-contrast kernels (``contrast_design`` of Bootstrap1D / Bootstrap2D): the CSR rows of
     ``_csr_tables`` with one weight ``design_w`` per listed group, checked and uploaded, empty arrays padded to one element.
     Returns test_row and test_design as int32 host arrays and the device tensors (test_row, test_design, design_ptr, design_grp,
-    design_w), the order in which the kernels take them."""
+    design_w), the order in which the kernels take them.  ``what`` names the caller in the messages; ``check(test_row)`` holds a
+    caller's further checks, which also run before anything is uploaded."""
     design_w = np.asarray(design_w, dtype=np.float64)
     if len(design_w) != len(np.asarray(design_grp)):
-        raise ValueError("contrast_design: inconsistent table sizes")
-    test_row, test_design, design_ptr, design_grp = _csr_tables("contrast_design", test_row, test_design, design_ptr, design_grp, n_rows, ng)
+        raise ValueError(f"{what}: inconsistent table sizes")
+    test_row, test_design, design_ptr, design_grp = _csr_tables(what, test_row, test_design, design_ptr, design_grp, n_rows, ng)
+    if check is not None:
+        check(test_row)
     return test_row, test_design, (_up(test_row), _up(test_design), dev(design_ptr), _up(design_grp), _up(design_w))
+
+
+FAMILY_MAX_STAGED = 1024      # members of a family whose (coef0, scale) mm_family_maxt can keep in LDS (contract.hip: FM_MAX_STAGED)
+
+
+def family_scale(st_m, st_v):
+    """``scale`` [test][2] of ``Bootstrap1D.family_maxt`` from the records of ``contrast_design``: 1 / se where the record is a test
+    (finite coef0, finite se > 0, n_valid >= 1, not all_equal), else 0."""
+    out = np.zeros((len(st_m), 2))
+    for k, st in enumerate((st_m, st_v)):
+        st = np.asarray(st, dtype=np.float64).reshape(-1, 8)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            live = np.isfinite(st[:, 0]) & np.isfinite(st[:, 1]) & (st[:, 1] > 0) & (st[:, 2] >= 1) & (st[:, 5] == 0)
+            out[:, k] = np.where(live, 1.0 / st[:, 1], 0.0)
+    return out
+
+
+def _family_tables(family_ptr, test_row, test_design, design_ptr, design_grp, design_w, scale, n_rows, ng):
+    """The tables of mm_family_maxt, checked (the kernel trusts them) and uploaded: those of ``_design_tables``, ``family_ptr`` a
+    CSR pointer over the tests whose families each sit on one row block, and one ``scale`` pair per test.  Returns family_ptr
+    (int32) and scale (fp64 [n_tests][2]) as host arrays and the device tensors of ``_design_tables``."""
+    family_ptr = np.asarray(family_ptr, dtype=np.int64).reshape(-1)
+    scale = np.asarray(scale, dtype=np.float64)
+
+    def check(test_row):
+        n_tests = len(test_row)
+        if len(family_ptr) < 1 or family_ptr[0] != 0 or family_ptr[-1] != n_tests or (np.diff(family_ptr) < 0).any():
+            raise ValueError("family_maxt: family_ptr is not a CSR pointer over the tests")
+        fam_of = np.repeat(np.arange(len(family_ptr) - 1), np.diff(family_ptr))
+        if n_tests and (test_row != test_row[family_ptr[fam_of]]).any():
+            raise ValueError("family_maxt: the tests of a family must share one test_row")
+        if scale.shape != (n_tests, 2):
+            raise ValueError("family_maxt: scale must be [n_tests][2]")
+
+    _, _, d_tab = _design_tables(test_row, test_design, design_ptr, design_grp, design_w, n_rows, ng, what="family_maxt", check=check)
+    return family_ptr.astype(np.int32), scale, d_tab
 
 
 def _contrast_design(planes, ld, B, ng, n_rows, test_row, test_design, design_ptr, design_grp, design_w, rows_design=None):

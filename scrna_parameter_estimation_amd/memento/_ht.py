@@ -246,6 +246,74 @@ def joint_tables(good, cov, trt, Nc):
         design_L=np.concatenate(Ls).astype(np.float64) if Ls else np.zeros(0))
 
 
+class _TwoGroupDesigns:
+    """What ``design.VsControlDesigns`` is to a label column, for whole groups (``treatment_col=None``): every group but ``ctrl`` is a
+    guide, tested by the design {(guide, +1), (ctrl, -1)} where both groups are good and by the empty design otherwise."""
+
+    def __init__(self, ng, ctrl):
+        self.ng, self.ctrl = ng, ctrl
+        self.guides = [j for j in range(ng) if j != ctrl]
+
+    def tests(self, good):
+        good = np.asarray(good, dtype=bool)
+        g = np.asarray(self.guides, dtype=np.int64)
+        return np.where(good[:, g] & good[:, [self.ctrl]], g[None, :], self.ng).astype(np.int32).reshape(-1)
+
+    def tables(self):
+        ng = self.ng
+        grp = np.column_stack([np.arange(ng), np.full(ng, self.ctrl)]).reshape(-1).astype(np.int32)
+        return np.concatenate([2 * np.arange(ng + 1), [2 * ng]]).astype(np.int32), grp, np.tile([1.0, -1.0], ng)
+
+
+class PosthocDesigns:
+    """The families of ``ht_1d_posthoc``: pairwise contrasts between the levels of a factor, as merged vs-control design tables.
+
+    ``labels`` [group][label column] (strings), ``k_trt``: the factor's column, or None = every group is a level of its own;
+    ``control``: None = all unordered pairs, else a level (``k_trt`` None: a group index) that every other level is tested against.
+    ``levels`` are in first-appearance order; ``pairs`` [(a, b)] as level indices, a after b, ordered by b then a.  The test of a
+    against b is the one ``VsControlDesigns(control=b)`` makes of guide a (``k_trt`` None: the two-entry design): one such object
+    per control level, whose design ids are shifted by the designs of the objects before it when the tables are merged."""
+
+    def __init__(self, labels, k_trt, control, Nc):
+        labels = np.asarray(labels, dtype=object).astype(str)
+        ng = len(labels)
+        self.levels = list(range(ng)) if k_trt is None else list(dict.fromkeys(labels[:, k_trt]))
+        if control is None:
+            ctrl_levels = range(len(self.levels) - 1)
+        elif control in self.levels:
+            ctrl_levels = [self.levels.index(control)]
+        else:
+            raise ValueError(f"control value {control!r} does not occur in the treatment column")
+        self.pairs, self.parts = [], []
+        for b in ctrl_levels:
+            d = _TwoGroupDesigns(ng, self.levels[b]) if k_trt is None else _design.VsControlDesigns(labels, k_trt, self.levels[b], Nc)
+            # with a given control every other level is tested; among all pairs, the levels after b
+            guides = [self.levels.index(g) for g in d.guides]
+            cols = [i for i, a in enumerate(guides) if control is not None or a > b]
+            self.pairs.extend((guides[i], b) for i in cols)
+            self.parts.append((d, np.asarray(cols, dtype=np.int64)))
+
+    def tests(self, good):
+        """Design id per test, into the tables ``tables()`` returns AFTER this call, for the genes of ``good`` [gene][group]:
+        gene-major x pair."""
+        good = np.asarray(good, dtype=bool)
+        ids = [d.tests(good).reshape(good.shape[0], -1)[:, cols] for d, cols in self.parts]     # (adds this chunk's new designs)
+        n_designs = [len(d.tables()[0]) - 1 for d, _ in self.parts]
+        first = np.concatenate([[0], np.cumsum(n_designs)[:-1]]).astype(np.int64)
+        return np.concatenate([i + f for i, f in zip(ids, first)], axis=1).astype(np.int32).reshape(-1)
+
+    def tables(self):
+        """(design_ptr, design_grp, design_w) of every part's designs, one part after the other."""
+        ptr, grp, w, n = [np.zeros(1, np.int32)], [], [], 0
+        for d, _ in self.parts:
+            p, g, ww = d.tables()
+            ptr.append(p[1:] + n)
+            grp.append(g)
+            w.append(ww)
+            n += len(g)
+        return np.concatenate(ptr).astype(np.int32), np.concatenate(grp).astype(np.int32), np.concatenate(w).astype(np.float64)
+
+
 def surviving_cols(bs, good, num_boot):
     """The replicate columns that survive hypothesis_test.py:249-251 / :372-373 (``bs.valid_cols``); (None, None) when nothing
     was dropped (the usual case): identity map."""

@@ -17,6 +17,7 @@ matrix, p-values); every O(nnz) or O(G x groups x B) step is a kernel launch via
 
 import functools
 import itertools
+from types import SimpleNamespace
 
 import numpy as np
 import pandas as pd
@@ -776,6 +777,137 @@ def ht_1d_joint(adata, treatment, covariate=None, num_boot=10000, rng='replay', 
     m['1d_ht_joint'] = dict(out, treatment=trt_names, covariate=cov_names)
     return pd.DataFrame({'gene': names[:G_all], 'df': out['df'], 'de_stat': out['mean_stat'], 'de_pval': out['mean_asl'],
                          'dv_stat': out['var_stat'], 'dv_pval': out['var_asl']})
+
+
+def _posthoc_plan(m, treatment_col, control):
+    """What ``ht_1d_posthoc`` tests: (``_ht.PosthocDesigns``, the level names).  Without ``treatment_col`` a level is a group
+    (``control``: a group label or index); with it, a value of that label column (``control``: such a value, compared as a string)."""
+    groups = m['groups']
+    Nc = np.array([m['group_cells'][g].shape[0] for g in groups], dtype=np.float64)
+    labels = [g.split(m['label_delimiter'])[1:] for g in groups]
+    if treatment_col is None:
+        if control is not None:
+            if not isinstance(control, (int, np.integer)) and control not in groups:
+                raise ValueError(f"control {control!r} is not one of the groups")
+            control = groups.index(control) if not isinstance(control, (int, np.integer)) else int(control)
+            if not 0 <= control < len(groups):
+                raise ValueError(f"control index {control!r} is not one of the {len(groups)} groups")
+        return _ht.PosthocDesigns(labels, None, control, Nc), list(groups)
+    label_columns = list(m['label_columns'])
+    if treatment_col not in label_columns:
+        raise ValueError(f"treatment_col {treatment_col!r} is not one of the label columns {label_columns}")
+    designs = _ht.PosthocDesigns(labels, label_columns.index(treatment_col), None if control is None else str(control), Nc)
+    return designs, designs.levels
+
+
+def ht_1d_posthoc(adata, treatment_col=None, control=None, num_boot=10000, num_cpus=1, rng='replay', fill_seed=0, max_rows=None,
+                  approx=False, *, ci=None):
+    """WHICH levels of a factor differ: the pairwise contrasts between the levels for every kept gene, each with its own test and
+    with a p-value adjusted for the gene's whole family of contrasts (``ht_1d_joint`` answers whether the gene differs at all).
+
+    Levels and strata are those of ``ht_1d_vs_control``.  ``treatment_col=None``: every group is a level and a contrast is the
+    plain two-group difference.  ``treatment_col='x'`` (a label column of ``create_groups``): the levels are the values of that
+    column and every other label column is a covariate; the test of level a against level b is EXACTLY the test
+    ``ht_1d_vs_control(control=b, treatment_col='x')`` makes of a -- the same subset regression, the same weight row, and with the same
+    ``np.random`` seed, ``fill_seed`` and ``max_rows`` the same numbers.  ``control=None``: the family of a gene is all unordered
+    pairs of levels (the Tukey form); levels are in first-appearance order, the pair (level_a, level_b) has a after b, and rows
+    are ordered by b, then a.  ``control=value``: every other level against that one (the Dunnett form).
+
+    The adjustment is the single-step max-T of Westfall and Young within the gene's family.  Every (gene, group) chain is
+    bootstrapped once, so replicate column c of all contrasts of a gene is one joint draw of the family.  A member is INCLUDED when
+    it has a test (finite coefficient, finite se > 0, a valid replicate, replicates that are not all equal); with
+    t_j[c] = |coef_j[c] - coef_j[0]| / se_j and M[c] = max_j t_j[c] over the included members, on the replicate columns that are
+    valid for all of them,  p_adj_j = (1 + #{c : M[c] > |coef_j[0]| / se_j}) / (1 + n_valid).  There is no tail fit: the floor is
+    1 / (n_valid + 1).  The reported ``*_pval_adj`` is max(p_adj_j, the member's own p-value), so it is never below the
+    unadjusted one whatever ``approx`` and the tail fit did to that.  A member without a test has NaN adjusted values and does not
+    enter the maximum: a gene that lost a whole level keeps the family of its other levels.  ``n_family`` is the number of
+    included members of the gene's family on the mean plane (``var_n_family`` in ``uns``: the variability plane).
+
+    ``ci=level`` (0 < level < 1) adds simultaneous intervals: crit = np.nanquantile(M[1:], level) and
+    coef_j[0] -+ crit * se_j, which cover all members of the family at once: ``de_sci_lo, de_sci_hi, dv_sci_lo, dv_sci_hi``.
+
+    ``rng``, ``fill_seed``, ``max_rows``, ``num_cpus`` and ``approx`` as in ``ht_1d_vs_control``; genes run in chunks, a family never
+    spans chunks and the chunking changes no number.  Not offered: ``resampling`` other than the centred bootstrap,
+    ``resample_rep``, ``strict`` and ``treatment_for_gene``; a gene-sharded run raises NotImplementedError.
+
+    Returns a DataFrame (gene, level_a, level_b, de_coef, de_se, de_pval, de_pval_adj, dv_coef, dv_se, dv_pval, dv_pval_adj,
+    n_family) and stores the arrays in ``uns['memento']['1d_ht_posthoc']``."""
+    _ht.check_args(rng, resampling='bootstrap')
+    _ht.ci_probs(ci)
+    m = adata.uns['memento']
+    st = m['_hip']
+    comm = getattr(st, 'comm', None)
+    if comm is not None and comm.world > 1:
+        raise NotImplementedError("ht_1d_posthoc on a gene-sharded run: the results are not gathered across ranks")
+    designs, level_names = _posthoc_plan(m, treatment_col, control)
+    pairs = designs.pairs
+    n_mem = len(pairs)
+    if n_mem == 0:
+        raise ValueError("ht_1d_posthoc needs at least two levels")
+    mv = _ht.moments_view(m)
+    ng = mv.ng
+    names = _var_names(adata)
+    G_all = len(st.gene_idx)
+    if max_rows is None:
+        max_rows = engine.auto_max_rows(num_boot + 1, arrays=2)
+    chunk = max(1, int(max_rows) // max(1, ng))
+    cols = {tag + k: [] for tag in ('mean', 'var') for k in ('_coef', '_se', '_asl', '_asl_adj', '_n_family')}
+    if ci is not None:
+        cols.update(mean_sci=[], var_sci=[])
+    st.last_bootstrap = st.last_good = st.last_posthoc = None    # (see ht_1d_moments: free the previous call's replicate rows first)
+
+    def run_chunk(c):
+        G, bs = c.G, c.bs
+        keys = np.arange(c.g0 * ng, c.g1 * ng, dtype=np.int64)      # the keys of ht_1d_vs_control: the same replicate planes
+        good, _ = _ht.run_chunk_1d(c, mv, rng, fill_seed, keys, keys)
+        st.last_good = good
+        test_gene = np.repeat(np.arange(G), n_mem)
+        family_ptr = np.arange(G + 1, dtype=np.int64) * n_mem
+        tables = (test_gene, designs.tests(good), *designs.tables())
+        st_m, st_v, rows = bs.contrast_design(*tables)
+        scale = engine.family_scale(st_m, st_v)
+        maxrow, adj, fam = bs.family_maxt(family_ptr, *tables, scale)
+        st.last_posthoc = SimpleNamespace(family_ptr=family_ptr, tables=tables, scale=scale, adj=adj, fam=fam)   # (diagnostics / tests: the last gene chunk)
+        if ci is not None:
+            q, _ = engine.row_quantiles(maxrow.reshape(-1, bs.ld), bs.ld, num_boot, [float(ci)])
+            crit = engine.host(q).reshape(G, 2)
+        for k, (tag, stt) in enumerate((('mean', st_m), ('var', st_v))):
+            p = _asl.asl_from_stats(stt, approx, lambda idx, w=k: rows(w, idx), num_cpus, 'bootstrap')
+            live = ~np.isnan(adj[:, k, 0])
+            p_adj = (1 + adj[:, k, 1]) / (1 + np.repeat(fam[:, k, 0], n_mem))
+            with np.errstate(invalid="ignore"):
+                p_adj = np.where(live, np.maximum(p_adj, p), np.nan)
+            cols[tag + '_coef'].append(stt[:, 0])
+            cols[tag + '_se'].append(stt[:, 1])
+            cols[tag + '_asl'].append(p)
+            cols[tag + '_asl_adj'].append(p_adj)
+            cols[tag + '_n_family'].append(np.repeat(fam[:, k, 1], n_mem).astype(np.int64))
+            if ci is not None:
+                half = np.where(live, np.repeat(crit[:, k], n_mem) * stt[:, 1], np.nan)
+                cols[tag + '_sci'].append(np.column_stack([stt[:, 0] - half, stt[:, 0] + half]))
+
+    for c in _ht.chunks_1d(st, mv, num_boot, chunk):
+        run_chunk(c)
+
+    def empty_of(k):
+        return np.zeros((0, 2) if k.endswith('_sci') else 0, dtype=np.int64 if k.endswith('_n_family') else np.float64)
+
+    out = {k: (np.concatenate(v) if v else empty_of(k)) for k, v in cols.items()}
+    out['n_family'] = out.pop('mean_n_family')
+    level_a = [level_names[a] for a, _ in pairs]
+    level_b = [level_names[b] for _, b in pairs]
+    m['1d_ht_posthoc'] = dict(out, levels=list(level_names), level_a=level_a, level_b=level_b, treatment_col=treatment_col,
+                              control=None if control is None else level_b[0])
+    df = pd.DataFrame({'gene': np.repeat(names[:G_all], n_mem), 'level_a': np.tile(np.asarray(level_a, dtype=object), G_all),
+                       'level_b': np.tile(np.asarray(level_b, dtype=object), G_all)})
+    df['de_coef'], df['de_se'], df['de_pval'], df['de_pval_adj'] = out['mean_coef'], out['mean_se'], out['mean_asl'], out['mean_asl_adj']
+    df['dv_coef'], df['dv_se'], df['dv_pval'], df['dv_pval_adj'] = out['var_coef'], out['var_se'], out['var_asl'], out['var_asl_adj']
+    df['n_family'] = out['n_family']
+    if ci is not None:
+        m['1d_ht_posthoc']['ci'] = float(ci)
+        for name, a in (('de', out['mean_sci']), ('dv', out['var_sci'])):
+            df[name + '_sci_lo'], df[name + '_sci_hi'] = a[:, 0], a[:, 1]
+    return df
 
 
 # ----------------------------------------------------------------------------------------------
