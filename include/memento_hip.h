@@ -498,7 +498,13 @@ int mm_bins_order2d(const uint32_t *d_tab, const int64_t *d_tab_ptr, const int32
                     const int64_t *d_pair_slot, const int64_t *d_tile_ptr, const double *d_grp_ncells, double *d_pk, double *d_lq,
                     double *d_v1, double *d_v2, double *d_a, double *d_b, int32_t *d_status, void *stream);
 /* 2D replay bootstrap: replicate covariance + the two variances folded into the correlation
- * replaces bootstrap._bootstrap_2d + estimator._corr_from_cov   memento/bootstrap.py:119-157, estimator.py:273-292 */
+ * replaces bootstrap._bootstrap_2d + estimator._corr_from_cov   memento/bootstrap.py:119-157, estimator.py:273-292
+ * Slot s = 64 * tile + lane reads bin k of its chain at [d_tile_ptr[tile] + k][lane] of the six planes; d_slot_K[s] <= 0 or
+ * d_slot_row[s] < 0 = unused lane (it reads its tile's first row and stores nothing).  A K == 1 chain is replayed like any other
+ * (the reference has no shortcut for it in 2D, unlike mm_boot1d_replay's NaN row): its one bin takes every cell, a variance is
+ * <= 0 and every replicate is the clipped sentinel 1.0.  Replicate b of an active slot goes to d_out_corr[row * ld + 1 + b],
+ * b < num_boot; nothing outside [row][1 .. num_boot] of the active slots' rows is written (column 0 and the columns behind
+ * num_boot are the caller's; ld >= num_boot + 1).  0 <= n_tiles < 2^31 - 1; n_tiles == 0 launches nothing. */
 int mm_boot2d_replay(const double *d_pk, const double *d_lq, const double *d_v1, const double *d_v2, const double *d_a,
                      const double *d_b, const int64_t *d_tile_ptr, int64_t n_tiles, const int32_t *d_slot_K,
                      const double *d_slot_nobs, const double *d_slot_omq, const int64_t *d_slot_row, const uint64_t pcg_state[4],
@@ -508,7 +514,10 @@ int mm_boot2d_replay(const double *d_pk, const double *d_lq, const double *d_v1,
  * (mm_bins_order2d for pairs given as d_pair_slot[q] = MM_CHAIN_SLOT | first record: pk, lq, x_i, x_j, 1/sf, 1/sf^2, two spare) are
  * [d_slot_rec[s], d_slot_rec[s] + d_slot_K[s]) of d_recs; d_slot_rec[s] < 0 = unused lane.  A lane then reads memory of its own whatever
  * bin it is on, so a BTPE draw can make one attempt per bin step and retry in the next (as mm_boot1d_replay does).  Same draws and
- * replicate correlations as mm_boot2d_replay, bit for bit.   memento/bootstrap.py:119-157, estimator.py:273-292 */
+ * replicate correlations as mm_boot2d_replay, bit for bit.   memento/bootstrap.py:119-157, estimator.py:273-292
+ * Unused lanes: d_slot_K[s] <= 0, d_slot_row[s] < 0 or d_slot_rec[s] < 0 -- such a lane reads record 0 at most and stores nothing.
+ * K == 1 chains, the cells written (only [row][1 .. num_boot] of the active slots' rows) and the n_tiles limit (< 2^31 - 1) as
+ * in mm_boot2d_replay. */
 int mm_boot2d_replay_rec(const double *d_recs, const int64_t *d_slot_rec, int64_t n_tiles, const int32_t *d_slot_K,
                          const double *d_slot_nobs, const double *d_slot_omq, const int64_t *d_slot_row, const uint64_t pcg_state[4],
                          int32_t num_boot, int64_t ld, double *d_out_corr, void *stream);

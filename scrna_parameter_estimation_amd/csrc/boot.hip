@@ -816,7 +816,13 @@ __global__ __launch_bounds__(256, MINW) void k_boot2d_replay(const double *__res
   int64_t row = slot_row[slot];
   if (K <= 0 || row < 0) K = 0;
   // REC: pk_ is the record buffer (8 doubles per bin: pk, lq, x_i, x_j, 1/sf, 1/sf^2, mm_bins_order2d with MM_CHAIN_SLOT pairs) and the
-  // lane's chain starts at record slot_rec[slot]; otherwise six [row][64] planes, the tile's rows from tile_ptr[tile]
+  // lane's chain starts at record slot_rec[slot] (< 0: an unused lane, like K <= 0 or row < 0 -- decided here, before ``run``, so that
+  // such a lane stores nothing); otherwise six [row][64] planes, the tile's rows from tile_ptr[tile]
+  int64_t r0 = 0;
+  if constexpr (REC) {
+    r0 = slot_rec[slot];
+    if (r0 < 0) K = 0;
+  }
   int64_t row0 = REC ? 0 : tile_ptr[tile];
   double nobs = slot_nobs[slot];
   double omq = slot_omq[slot];
@@ -828,11 +834,7 @@ __global__ __launch_bounds__(256, MINW) void k_boot2d_replay(const double *__res
   // alone in its wave and is the critical path of the launch, so an exposed L2 round trip per step is paid in full there
   const int64_t obase = row0 * 64 + lane;
   const double *__restrict__ rec = pk_;
-  if constexpr (REC) {
-    int64_t r0 = slot_rec[slot];
-    if (r0 < 0) K = 0;
-    rec = pk_ + (K >= 1 ? r0 : 0) * 8;
-  }
+  if constexpr (REC) rec = pk_ + (K >= 1 ? r0 : 0) * 8;
   double c_pk, c_lq, c_x1, c_x2, c_a, c_b;
   if constexpr (REC) {
     double2 t0 = *(const double2 *)(rec), t1 = *(const double2 *)(rec + 2), t2 = *(const double2 *)(rec + 4);
@@ -1089,6 +1091,7 @@ int mm_boot2d_replay(const double *d_pk, const double *d_lq, const double *d_v1,
   MM_ARG(d_pk && d_lq && d_v1 && d_v2 && d_a && d_b && d_tile_ptr && d_slot_K && d_slot_nobs && d_slot_omq && d_slot_row && pcg_state);
   MM_ARG(d_out_corr && n_tiles >= 0 && num_boot > 0 && ld >= (int64_t)num_boot + 1);
   if (n_tiles == 0) return MM_OK;
+  MM_ARG(n_tiles < 2147483647LL);
   auto kern = tile_kernel(n_tiles > 2048, [](auto minw, auto fast) { return &k_boot2d_replay<minw(), fast(), false>; });
   hipLaunchKernelGGL(kern, dim3((unsigned)((n_tiles + 3) / 4)), dim3(256), 0, (hipStream_t)stream, d_pk, d_lq, d_v1, d_v2, d_a, d_b,
                      d_tile_ptr, n_tiles, d_slot_K, d_slot_nobs, d_slot_omq, d_slot_row, pcg_state[0], pcg_state[1], pcg_state[2],
@@ -1103,6 +1106,7 @@ int mm_boot2d_replay_rec(const double *d_recs, const int64_t *d_slot_rec, int64_
   MM_ARG(d_recs && d_slot_rec && d_slot_K && d_slot_nobs && d_slot_omq && d_slot_row && pcg_state);
   MM_ARG(d_out_corr && n_tiles >= 0 && num_boot > 0 && ld >= (int64_t)num_boot + 1);
   if (n_tiles == 0) return MM_OK;
+  MM_ARG(n_tiles < 2147483647LL);
   auto kern = tile_kernel(n_tiles > 2048, [](auto minw, auto fast) { return &k_boot2d_replay<minw(), fast(), true>; });
   const double *nul = nullptr;
   hipLaunchKernelGGL(kern, dim3((unsigned)((n_tiles + 3) / 4)), dim3(256), 0, (hipStream_t)stream, d_recs, nul, nul, nul, nul, nul,
