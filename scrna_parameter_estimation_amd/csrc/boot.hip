@@ -11,6 +11,9 @@
 // pair).  The 64 pairs of a tile walk their bins in lock step so every operand load is a coalesced
 // 512-B row; the multinomial weights never leave registers (the K x B matrix is never materialised).
 // fp64, contraction OFF (-ffp-contract=off): replicate means/variances are bit-identical to numpy's.
+// The three tile kernels (k_boot1d_replay, k_boot1d_free, k_boot2d_replay) are built from parts defined once, above k_boot1d_replay:
+// tile_lane (the lane's chain, the unused-lane rule), a plane and a record cursor for Ops1D / Ops2D, draw_bin (the draw of one bin), Stat1D /
+// Stat2D (the replicate statistic), tile_lockstep (the lock-step loop).  chain_body and k_boot1d_async draw in their own forms.
 #include "mm_common.h"
 #include "npy_rng.h"
 #include <type_traits>
@@ -110,6 +113,148 @@ __device__ __forceinline__ bool run_tile_as_chain(const ChainArgs &ca, int64_t t
   return false;
 }
 
+// ------------------------------------------------------------------------------------------------
+// The tile kernels' parts.  A lane's chain: K = 0 marks an unused lane (K <= 0 or row < 0 in the tables; where the chains are read as
+// records, REC, slot_rec < 0 as well): such a lane draws nothing and stores nothing, so whether a lane runs is decided from this K alone.
+// The loader also raises the wave's issue priority in the first half of the grid: two waves share a SIMD, the host puts the long tiles
+// there (engine.pair_tiles) and pairs each with a short one from the second half; the long tile is the critical path and is served first.
+struct TileLane {
+  int64_t slot, row, rec;   // slot of the tables, output row, the chain's first record (REC; 0 otherwise)
+  int K;
+  double nobs, omq;         // N_g, 1 - q of the pair's group
+  int32_t n;                // N_g < 2^31 (checked by the host)
+  __device__ __forceinline__ double *out(double *plane, int64_t ld) const { return plane + row * ld + 1; }   // the replicates' cells
+};
+template <bool REC>
+__device__ __forceinline__ TileLane tile_lane(int64_t tile, int64_t n_tiles, int lane, const int32_t *__restrict__ slot_K,
+                                              const double *__restrict__ slot_nobs, const double *__restrict__ slot_omq,
+                                              const int64_t *__restrict__ slot_row, const int64_t *__restrict__ slot_rec) {
+  if (tile * 2 < n_tiles) __builtin_amdgcn_s_setprio(BOOT_SETPRIO);
+  const int64_t slot = tile * 64 + lane;
+  TileLane t{slot, slot_row[slot], REC ? slot_rec[slot] : 0, slot_K[slot], slot_nobs[slot], slot_omq[slot], 0};
+  if (t.K <= 0 || t.row < 0 || t.rec < 0) t.K = 0;
+  t.n = (int32_t)t.nobs;
+  return t;
+}
+// The operands of one bin, and where a lane's chain keeps them: [row][64] planes (the 64 lanes of a tile read one coalesced 512-B row
+// per plane and bin) or the chain's own 8-double records (mm_bins_order / mm_bins_order2d with MM_CHAIN_SLOT pairs: one 64-B half line
+// per bin).  The kernels load bin k + 1 while bin k computes: one lane is one latency-bound sequential chain, so an exposed L2 / HBM
+// round trip per step would be a large part of the step.
+struct Ops1D { double pk, lq, v, a, b; };
+struct Planes1D {
+  const double *__restrict__ pk, *__restrict__ lq, *__restrict__ v, *__restrict__ a, *__restrict__ b;
+  int64_t obase;   // first row of the tile * 64 + lane
+  __device__ __forceinline__ Ops1D load(int k) const {
+    int64_t o = obase + (int64_t)k * 64;
+    return Ops1D{pk[o], lq[o], v[o], a[o], b[o]};
+  }
+};
+struct Records1D {
+  const double *__restrict__ rec;   // [K][8]: pk, lq, count, 1/sf, 1/sf^2, (3 spare)
+  __device__ __forceinline__ Ops1D load(int k) const {
+    const double *p = rec + (int64_t)k * 8;
+    double2 t0 = *(const double2 *)(p), t1 = *(const double2 *)(p + 2);
+    return Ops1D{t0.x, t0.y, t1.x, t1.y, p[4]};
+  }
+};
+
+// The draw of one bin of a lane's chain: the weight of the bin.  Every bin but the last draws a binomial from what the replicate has
+// left (``dn``; ``live`` goes off when nothing is left, and the later bins get 0 without a draw, as in numpy); the last bin takes the
+// remainder.  The lanes share the instruction stream, not the bin index: with ``cap`` > 0 a BTPE draw makes that many attempt(s) per bin
+// step, and a lane whose attempts were all rejected comes back ``pending``: it stays on its bin and tries again in the next step, beside
+// its neighbours' next draws (npyrng::binomial_pre_capped) -- so a step costs the wave one attempt, not as many as its unluckiest lane
+// needs.  The kernels' cap is a constant while more than BOOT_TAIL_LANES lanes are inside the replicate; then draws run to completion (0).
+// dn and live go in and come back by value: taken by reference, k_boot2d_replay<., false, .> came out with other registers (180 VGPRs
+// for 185 in the two-wave builds), and every kernel is to keep its resources (profiles/replay_shared_step_resources.txt).
+struct BinDraw {
+  int32_t w, dn;        // the bin's weight (meaningless when pending); what the replicate has left behind this bin
+  bool live, pending;
+};
+template <bool FAST>
+__device__ __forceinline__ BinDraw draw_bin(npyrng::Pcg64 &g, double pk, double lq, int32_t dn, bool live, bool last_bin, int cap) {
+  int32_t w;
+  bool pending = false;
+  if (!last_bin) {
+    w = 0;
+    if (live) {
+      if constexpr (FAST) w = npyrng::binomial_pre_capped<int32_t>(g, pk, lq, dn, cap, pending);
+      else w = npyrng::binomial_pre<int32_t, false>(g, pk, lq, dn);
+      if (!pending) {
+        dn -= w;
+        if (dn <= 0) live = false;
+      }
+    }
+  } else {
+    w = dn > 0 ? dn : 0;
+  }
+  return BinDraw{w, dn, live, pending};
+}
+// The replicate statistic of a 1D chain: the two sums of accumulate_1d, closed into the replicate's cell of the mean and the variance
+// row.  Chains of fewer than MIN_K bins do not run; a single bin gives all-NaN replicates (bootstrap.py:97-98).
+// w_dump (optional): int32 weights [slot][k < kmax_dump][r < num_boot].
+struct Stat1D {
+  static constexpr int MIN_K = 2;
+  const TileLane &t;
+  int32_t num_boot, mean_only;
+  double *om, *ov;   // t.out() of the two planes
+  int32_t *__restrict__ w_dump;
+  int32_t kmax_dump;
+  double M1, M2;
+  __device__ __forceinline__ void short_chain() {
+    if (t.K == 1) {
+      for (int r = 0; r < num_boot; r++) om[r] = ov[r] = NAN;
+    }
+  }
+  __device__ __forceinline__ void begin() { M1 = 0.0, M2 = 0.0; }
+  __device__ __forceinline__ void dump(int k, int r, int32_t w) { if (w_dump) w_dump[((int64_t)t.slot * kmax_dump + k) * num_boot + r] = w; }
+  __device__ __forceinline__ void add(int32_t w, const Ops1D &c) { accumulate_1d(M1, M2, w, c.v, c.a, c.b, t.omq); }
+  __device__ __forceinline__ void close(int r) { close_replicate(M1, M2, t.nobs, mean_only, om + r, ov + r); }
+};
+
+// The lock-step tile body (k_boot1d_replay, k_boot2d_replay): one lane = one chain, every lane of the wave in the same replicate.
+// Within a replicate each lane is on its own bin (draw_bin: a pending lane stays behind); the lanes meet again at the replicate's end.
+// ``Stat`` is the replicate statistic (Stat1D, Stat2D), ``ops`` the lane's operand cursor, CAP the BTPE attempts per bin step.
+template <bool FAST, int CAP, typename Stat, typename Cursor>
+__device__ __forceinline__ void tile_lockstep(const TileLane &t, uint64_t st0, uint64_t st1, uint64_t st2, uint64_t st3, int32_t num_boot,
+                                              Stat &stat, const Cursor &ops) {
+  const int K = t.K;
+  stat.short_chain();
+  npyrng::Pcg64 g{st0, st1, st2, st3};
+  const bool run = K >= Stat::MIN_K;
+  auto c = ops.load(0);
+  for (int r = 0; r < num_boot; r++) {
+    stat.begin();
+    int32_t dn = t.n;
+    bool live = true;
+    int kl = 0;
+    for (;;) {
+      const bool act = run && kl < K;
+      const uint64_t act_mask = __ballot(act);
+      if (act_mask == 0) break;
+      const int cap = (CAP > 0 && __popcll(act_mask) > BOOT_TAIL_LANES) ? CAP : 0;
+      const auto nx = ops.load(kl + 1 < K ? kl + 1 : 0);
+      bool adv = false;
+      if (act) {
+        const BinDraw d = draw_bin<FAST>(g, c.pk, c.lq, dn, live, kl >= K - 1, cap);
+        dn = d.dn;
+        live = d.live;
+        if (!d.pending) {
+          stat.dump(kl, r, d.w);
+          if (d.w != 0) stat.add(d.w, c);
+          adv = true;
+        }
+      }
+      if (adv) {
+        kl++;
+        c = nx;
+      }
+    }
+    if (run) stat.close(r);
+  }
+}
+
+// The strict 1D tile kernel: the lock-step body on [row][64] operand planes, the tile's rows from tile_ptr[tile].  A tile flagged in
+// ca.tile_chain is a chain of the one-wave-per-chain form instead.
 template <int MINW, bool FAST>
 __global__ __launch_bounds__(256, MINW) void k_boot1d_replay(const double *__restrict__ pk_, const double *__restrict__ lq_,
                                                        const double *__restrict__ v, const double *__restrict__ a,
@@ -126,83 +271,10 @@ __global__ __launch_bounds__(256, MINW) void k_boot1d_replay(const double *__res
   if (tile >= n_tiles) return;
   if (run_tile_as_chain<FAST>(ca, tile, n_tiles, lane, st0, st1, num_boot, mean_only, ld, out_mean, out_var, wave_clock)) return;
   int64_t t_start = wave_clock ? (int64_t)wall_clock64() : 0;
-  // Two waves share a SIMD.  The host puts the long tiles in the first half of the grid (engine.pair_tiles) and pairs
-  // each with a short one from the second half: the long tile is the critical path, so it is served first.
-  if (tile * 2 < n_tiles) __builtin_amdgcn_s_setprio(BOOT_SETPRIO);
-  int64_t slot = tile * 64 + lane;
-  int K = slot_K[slot];
-  int64_t row = slot_row[slot];
-  if (K <= 0 || row < 0) K = 0;  // unused lane
-  int64_t row0 = tile_ptr[tile];
-  double nobs = slot_nobs[slot];
-  double omq = slot_omq[slot];  // 1 - q of the pair's group
-  int32_t n = (int32_t)nobs;  // N_g < 2^31 (checked by the host)
-  double *om = out_mean + row * ld + 1;
-  double *ov = out_var + row * ld + 1;
-  if (K == 1) {  // bootstrap.py:97-98: a single bin -> all-NaN replicates
-    for (int r = 0; r < num_boot; r++) {
-      om[r] = NAN;
-      ov[r] = NAN;
-    }
-  }
-  npyrng::Pcg64 g{st0, st1, st2, st3};
-  const bool run = K >= 2;
-  // operands of the NEXT bin step are loaded while the current one computes (one lane = one latency-bound
-  // sequential chain, so an exposed L2/HBM round trip per step would be a large part of the step)
-  const int64_t obase = row0 * 64 + lane;
-  double c_pk = pk_[obase], c_lq = lq_[obase], c_v = v[obase], c_a = a[obase], c_b = b[obase];
-  for (int r = 0; r < num_boot; r++) {
-    double M1 = 0.0, M2 = 0.0;
-    int32_t dn = n;
-    bool live = true;
-    // The lanes share the instruction stream, not the bin index: a BTPE draw makes BOOT_BTPE_CAP attempt(s) per bin step, and a lane
-    // whose attempts were all rejected stays on its bin and tries again in the next step, beside its neighbours' next draws
-    // (binomial_pre_capped) -- so a step costs the wave one attempt, not as many as its unluckiest lane needs.  The lanes meet again
-    // at the end of the replicate; while only stragglers (<= BOOT_TAIL_LANES lanes) are left, draws run to completion.
-    int kl = 0;
-    for (;;) {
-      const bool act = run && kl < K;
-      const uint64_t act_mask = __ballot(act);
-      if (act_mask == 0) break;
-      const int cap = (BOOT_BTPE_CAP > 0 && __popcll(act_mask) > BOOT_TAIL_LANES) ? BOOT_BTPE_CAP : 0;
-      int kn = kl + 1 < K ? kl + 1 : 0;
-      int64_t on = obase + (int64_t)kn * 64;
-      double n_pk = pk_[on], n_lq = lq_[on], n_v = v[on], n_a = a[on], n_b = b[on];
-      bool adv = false;
-      if (act) {
-        int32_t w;
-        bool pending = false;
-        if (kl < K - 1) {
-          w = 0;
-          if (live) {
-            if constexpr (FAST) w = npyrng::binomial_pre_capped<int32_t>(g, c_pk, c_lq, dn, cap, pending);
-            else w = npyrng::binomial_pre<int32_t, false>(g, c_pk, c_lq, dn);
-            if (!pending) {
-              dn -= w;
-              if (dn <= 0) live = false;
-            }
-          }
-        } else {
-          w = dn > 0 ? dn : 0;
-        }
-        if (!pending) {
-          if (w_dump) w_dump[((int64_t)slot * kmax_dump + kl) * num_boot + r] = (int32_t)w;
-          if (w != 0) accumulate_1d(M1, M2, w, c_v, c_a, c_b, omq);
-          adv = true;
-        }
-      }
-      if (adv) {
-        kl++;
-        c_pk = n_pk; c_lq = n_lq; c_v = n_v; c_a = n_a; c_b = n_b;
-      }
-    }
-    if (run) {
-      double mean, var;
-      close_replicate(M1, M2, nobs, mean_only, &mean, &var);
-      om[r] = mean;
-      ov[r] = var;
-    }
-  }
+  const TileLane t = tile_lane<false>(tile, n_tiles, lane, slot_K, slot_nobs, slot_omq, slot_row, nullptr);
+  Stat1D stat{t, num_boot, mean_only, t.out(out_mean, ld), t.out(out_var, ld), w_dump, kmax_dump};
+  const Planes1D ops{pk_, lq_, v, a, b, tile_ptr[tile] * 64 + lane};
+  tile_lockstep<FAST, BOOT_BTPE_CAP>(t, st0, st1, st2, st3, num_boot, stat, ops);
   if (wave_clock && lane == 0) {  // profiling hook (mm_debug_wave_clock): when and where this wave ran
     wave_clock[tile * 4 + 0] = t_start;
     wave_clock[tile * 4 + 1] = (int64_t)wall_clock64();
@@ -362,18 +434,8 @@ __global__ __launch_bounds__(256, CHAIN_MIN_WAVES) void k_boot1d_chain(ChainArgs
 #ifndef ASYNC_MIN_WAVES
 #define ASYNC_MIN_WAVES 2     // 64 chains per wave: the chains of a launch rarely fill two waves per SIMD; no register spills
 #endif
-struct BinOps {
-  double pk, lq, v, a, b;
-};
-__device__ __forceinline__ BinOps load_bin(const double *__restrict__ rec) {
-  BinOps o;
-  o.pk = rec[0];
-  o.lq = rec[1];
-  o.v = rec[2];
-  o.a = rec[3];
-  o.b = rec[4];
-  return o;
-}
+// one record with five 8-byte loads, as this kernel has always read it (Records1D reads the same record with two 16-byte loads)
+__device__ __forceinline__ Ops1D load_bin(const double *__restrict__ rec) { return Ops1D{rec[0], rec[1], rec[2], rec[3], rec[4]}; }
 
 template <bool FAST>
 __global__ __launch_bounds__(256, ASYNC_MIN_WAVES) void k_boot1d_async(const double *__restrict__ ops, const int64_t *__restrict__ ch_base,
@@ -400,7 +462,7 @@ __global__ __launch_bounds__(256, ASYNC_MIN_WAVES) void k_boot1d_async(const dou
   int32_t state = K ? LS_RESTART : LS_IDLE;
   int32_t r = 0, k = 0, dn = n;
   double M1 = 0.0, M2 = 0.0;
-  BinOps cur = load_bin(rec), nxt = load_bin(rec + (K ? 8 : 0));
+  Ops1D cur = load_bin(rec), nxt = load_bin(rec + (K ? 8 : 0));
   int64_t passes = 0;
   while (__ballot(state != LS_IDLE)) {
     passes++;
@@ -484,6 +546,12 @@ __device__ __forceinline__ uint64_t mix64(uint64_t x) {  // splitmix64 finaliser
   x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
   x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
   return x ^ (x >> 31);
+}
+
+// rng='fast' (k_boot1d_fast, k_boot2d_fast): the PCG64 stream that replicate r of the chain with key ``key`` owns
+__device__ __forceinline__ npyrng::Pcg64 fast_stream(uint64_t seed, uint64_t key, int r) {
+  uint64_t h = mix64(seed ^ mix64(key * 0x100000001B3ull + (uint64_t)r));
+  return npyrng::Pcg64{mix64(h), mix64(h + 1), mix64(h + 2), mix64(h + 3) | 1ull};
 }
 
 // counter of the refill draws of replicate r in plane ``which`` (0 mean, 1 res_var) of the row with key ``key``
@@ -628,8 +696,7 @@ __global__ __launch_bounds__(256) void k_boot1d_fast(const double *__restrict__ 
   int64_t obase = tile_ptr[slot >> 6] * 64 + (slot & 63);
   double nobs = slot_nobs[slot], omq = slot_omq[slot];
   int32_t n = (int32_t)nobs;
-  uint64_t h = mix64(seed ^ mix64((uint64_t)slot_key[slot] * 0x100000001B3ull + (uint64_t)r));
-  npyrng::Pcg64 g{mix64(h), mix64(h + 1), mix64(h + 2), mix64(h + 3) | 1ull};
+  npyrng::Pcg64 g = fast_stream(seed, (uint64_t)slot_key[slot], r);
   int32_t *wd = (w_dump && mine) ? w_dump + (slot * kmax_dump) * (int64_t)num_boot + r : nullptr;
   double M1 = 0.0, M2 = 0.0;
   int32_t dn = n;
@@ -654,8 +721,9 @@ __global__ __launch_bounds__(256) void k_boot1d_fast(const double *__restrict__ 
 }
 
 // ------------------------------------------------------------------------------------------------
-// FREE-RUNNING tile kernel: one lane = one chain, the lanes of a wave share the instruction stream and nothing else.  As in
-// k_boot1d_replay a BTPE draw makes BOOT_BTPE_CAP attempt(s) per bin step and a rejected lane retries in the next step -- but here a
+// FREE-RUNNING tile kernel: one lane = one chain, the lanes of a wave share the instruction stream and nothing else.  The lane, the
+// draw of a bin (BOOT_BTPE_CAP attempt(s) per bin step, a rejected lane retries in the next step) and the replicate statistic are the
+// shared parts above k_boot1d_replay (tile_lane, draw_bin, Stat1D); the loop is this kernel's own: a
 // lane that finishes a replicate starts its next one at once instead of waiting for the slowest lane of its wave (in-kernel stamps of
 // k_boot1d_replay: a 64-wide tile makes 1.23 bin steps per nominal step, 1.095 is the lanes' average), so every lane carries its own
 // replicate index as well.  The lanes drift apart without bound, and operand ROWS shared by the wave (one coalesced 512-B row per plane
@@ -677,32 +745,18 @@ __global__ __launch_bounds__(256, MINW) void k_boot1d_free(const double *__restr
   if (tile >= n_tiles) return;
   if (run_tile_as_chain<FAST>(ca, tile, n_tiles, lane, st0, st1, num_boot, mean_only, ld, out_mean, out_var, wave_clock)) return;
   int64_t t_start = wave_clock ? (int64_t)wall_clock64() : 0;
-  if (tile * 2 < n_tiles) __builtin_amdgcn_s_setprio(BOOT_SETPRIO);
-  int64_t slot = tile * 64 + lane;
-  int K = slot_K[slot];
-  int64_t row = slot_row[slot];
-  int64_t rec0 = slot_rec[slot];
-  if (K <= 0 || row < 0 || rec0 < 0) K = 0;  // unused lane
-  double nobs = slot_nobs[slot];
-  double omq = slot_omq[slot];
-  int32_t n = (int32_t)nobs;
-  double *om = out_mean + row * ld + 1;
-  double *ov = out_var + row * ld + 1;
-  if (K == 1) {  // bootstrap.py:97-98: a single bin -> all-NaN replicates
-    for (int r = 0; r < num_boot; r++) {
-      om[r] = NAN;
-      ov[r] = NAN;
-    }
-  }
+  const TileLane t = tile_lane<true>(tile, n_tiles, lane, slot_K, slot_nobs, slot_omq, slot_row, slot_rec);
+  const int K = t.K;
+  Stat1D stat{t, num_boot, mean_only, t.out(out_mean, ld), t.out(out_var, ld), w_dump, kmax_dump};
+  stat.short_chain();
   npyrng::Pcg64 g{st0, st1, st2, st3};
-  const double *__restrict__ rec = recs + (K >= 2 ? rec0 : 0) * 8;
-  bool more = K >= 2;                       // this lane still has replicates to draw
+  bool more = K >= Stat1D::MIN_K;           // this lane still has replicates to draw
+  const Records1D ops{recs + (more ? t.rec : 0) * 8};
   int rl = 0, kl = 0;                       // its replicate and its bin
-  double M1 = 0.0, M2 = 0.0;
-  int32_t dn = n;
+  stat.begin();
+  int32_t dn = t.n;
   bool live = true;
-  double2 c01 = *(const double2 *)(rec), c23 = *(const double2 *)(rec + 2);
-  double c_b = rec[4];
+  Ops1D c = ops.load(0);
   int64_t steps = 0;
   for (;;) {
     const bool act = more;
@@ -710,42 +764,22 @@ __global__ __launch_bounds__(256, MINW) void k_boot1d_free(const double *__restr
     if (act_mask == 0) break;
     steps++;
     const int cap = (BOOT_BTPE_CAP > 0 && __popcll(act_mask) > BOOT_TAIL_LANES) ? BOOT_BTPE_CAP : 0;
-    const int kn = kl + 1 < K ? kl + 1 : 0;
-    const double *nx = rec + (int64_t)kn * 8;
-    double2 n01 = *(const double2 *)(nx), n23 = *(const double2 *)(nx + 2);
-    double n_b = nx[4];
+    const Ops1D nx = ops.load(kl + 1 < K ? kl + 1 : 0);
     if (act) {
-      const double c_pk = c01.x, c_lq = c01.y, c_v = c23.x, c_a = c23.y;
-      int32_t w;
-      bool pending = false;
-      if (kl < K - 1) {
-        w = 0;
-        if (live) {
-          if constexpr (FAST) w = npyrng::binomial_pre_capped<int32_t>(g, c_pk, c_lq, dn, cap, pending);
-          else w = npyrng::binomial_pre<int32_t, false>(g, c_pk, c_lq, dn);
-          if (!pending) {
-            dn -= w;
-            if (dn <= 0) live = false;
-          }
-        }
-      } else {
-        w = dn > 0 ? dn : 0;
-      }
-      if (!pending) {
-        if (w_dump) w_dump[((int64_t)slot * kmax_dump + kl) * num_boot + rl] = (int32_t)w;
-        if (w != 0) accumulate_1d(M1, M2, w, c_v, c_a, c_b, omq);
+      const BinDraw d = draw_bin<FAST>(g, c.pk, c.lq, dn, live, kl >= K - 1, cap);
+      dn = d.dn;
+      live = d.live;
+      if (!d.pending) {
+        stat.dump(kl, rl, d.w);
+        if (d.w != 0) stat.add(d.w, c);
         kl++;
-        c01 = n01; c23 = n23; c_b = n_b;
+        c = nx;
         if (kl == K) {                       // the replicate is complete (the operands just taken over are bin 0's again)
-          double mean, var;
-          close_replicate(M1, M2, nobs, mean_only, &mean, &var);
-          om[rl] = mean;
-          ov[rl] = var;
+          stat.close(rl);
           rl++;
           kl = 0;
-          M1 = 0.0;
-          M2 = 0.0;
-          dn = n;
+          stat.begin();
+          dn = t.n;
           live = true;
           more = rl < num_boot;
         }
@@ -798,6 +832,42 @@ __device__ __forceinline__ double close_replicate_2d(const Sums2D &s, double nob
 #ifndef BOOT2D_REC_BTPE_CAP
 #define BOOT2D_REC_BTPE_CAP 1    // attempts per bin step when the chains read their own operand records (REC): no shared rows to scatter
 #endif
+// A 2D bin's operands in the two layouts (the 1D forms: Ops1D, Planes1D, Records1D).
+struct Ops2D { double pk, lq, x1, x2, a, b; };
+struct Planes2D {
+  const double *__restrict__ pk, *__restrict__ lq, *__restrict__ x1, *__restrict__ x2, *__restrict__ a, *__restrict__ b;
+  int64_t obase;   // first row of the tile * 64 + lane
+  __device__ __forceinline__ Ops2D load(int k) const {
+    int64_t o = obase + (int64_t)k * 64;
+    return Ops2D{pk[o], lq[o], x1[o], x2[o], a[o], b[o]};
+  }
+};
+struct Records2D {
+  const double *__restrict__ rec;   // [K][8]: pk, lq, x_i, x_j, 1/sf, 1/sf^2, (2 spare)
+  __device__ __forceinline__ Ops2D load(int k) const {
+    const double *p = rec + (int64_t)k * 8;
+    double2 t0 = *(const double2 *)(p), t1 = *(const double2 *)(p + 2), t2 = *(const double2 *)(p + 4);
+    return Ops2D{t0.x, t0.y, t1.x, t1.y, t2.x, t2.y};
+  }
+};
+// The replicate statistic of a 2D chain: the five sums, closed into the replicate's cell of the one output row.  Every chain with a
+// bin runs (K == 1: every replicate is the observed sample); there is no weight dump.
+struct Stat2D {
+  static constexpr int MIN_K = 1;
+  const TileLane &t;
+  double *oc;   // t.out() of the plane
+  Sums2D sums;
+  __device__ __forceinline__ void short_chain() {}
+  __device__ __forceinline__ void begin() { sums = Sums2D(); }
+  __device__ __forceinline__ void dump(int, int, int32_t) {}
+  __device__ __forceinline__ void add(int32_t w, const Ops2D &c) { accumulate_2d(sums, w, c.x1, c.x2, c.a, c.b, t.omq); }
+  __device__ __forceinline__ void close(int r) { oc[r] = close_replicate_2d(sums, t.nobs); }
+};
+// The lock-step body (tile_lockstep) with Stat2D.  REC: pk_ is the record buffer and the lane's chain starts at record slot_rec[slot];
+// otherwise six [row][64] planes, the tile's rows from tile_ptr[tile].  BOOT2D_BTPE_CAP is 0: measured on configs[3]'s share (250 x 2000
+// pairs, 335 bins per chain on average, 64-wide tiles in several rounds) one attempt per step takes 29.2 s against 16.8 s: the steps of
+// this kernel are short (small inversion searches), and lanes that fall behind by different amounts turn the six coalesced 512-B operand
+// rows of a step into up to 64 separate lines each.  (The load one bin ahead: the longest pair runs alone in its wave.)
 template <int MINW, bool FAST, bool REC>
 __global__ __launch_bounds__(256, MINW) void k_boot2d_replay(const double *__restrict__ pk_, const double *__restrict__ lq_,
                                                        const double *__restrict__ v1_, const double *__restrict__ v2_,
@@ -810,91 +880,14 @@ __global__ __launch_bounds__(256, MINW) void k_boot2d_replay(const double *__res
   int lane = mm_lane();
   int64_t tile = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   if (tile >= n_tiles) return;
-  if (tile * 2 < n_tiles) __builtin_amdgcn_s_setprio(BOOT_SETPRIO);  // long tiles first, see k_boot1d_replay
-  int64_t slot = tile * 64 + lane;
-  int K = slot_K[slot];
-  int64_t row = slot_row[slot];
-  if (K <= 0 || row < 0) K = 0;
-  // REC: pk_ is the record buffer (8 doubles per bin: pk, lq, x_i, x_j, 1/sf, 1/sf^2, mm_bins_order2d with MM_CHAIN_SLOT pairs) and the
-  // lane's chain starts at record slot_rec[slot] (< 0: an unused lane, like K <= 0 or row < 0 -- decided here, before ``run``, so that
-  // such a lane stores nothing); otherwise six [row][64] planes, the tile's rows from tile_ptr[tile]
-  int64_t r0 = 0;
+  const TileLane t = tile_lane<REC>(tile, n_tiles, lane, slot_K, slot_nobs, slot_omq, slot_row, slot_rec);
+  Stat2D stat{t, t.out(out_corr, ld)};
   if constexpr (REC) {
-    r0 = slot_rec[slot];
-    if (r0 < 0) K = 0;
-  }
-  int64_t row0 = REC ? 0 : tile_ptr[tile];
-  double nobs = slot_nobs[slot];
-  double omq = slot_omq[slot];
-  int32_t n = (int32_t)nobs;
-  double *oc = out_corr + row * ld + 1;
-  npyrng::Pcg64 g{st0, st1, st2, st3};
-  const bool run = K >= 1;
-  // operands of the NEXT bin step are loaded while the current one computes (as in k_boot1d_replay): the longest pair runs
-  // alone in its wave and is the critical path of the launch, so an exposed L2 round trip per step is paid in full there
-  const int64_t obase = row0 * 64 + lane;
-  const double *__restrict__ rec = pk_;
-  if constexpr (REC) rec = pk_ + (K >= 1 ? r0 : 0) * 8;
-  double c_pk, c_lq, c_x1, c_x2, c_a, c_b;
-  if constexpr (REC) {
-    double2 t0 = *(const double2 *)(rec), t1 = *(const double2 *)(rec + 2), t2 = *(const double2 *)(rec + 4);
-    c_pk = t0.x; c_lq = t0.y; c_x1 = t1.x; c_x2 = t1.y; c_a = t2.x; c_b = t2.y;
+    const Records2D ops{pk_ + (t.K >= Stat2D::MIN_K ? t.rec : 0) * 8};
+    tile_lockstep<FAST, BOOT2D_REC_BTPE_CAP>(t, st0, st1, st2, st3, num_boot, stat, ops);
   } else {
-    c_pk = pk_[obase]; c_lq = lq_[obase]; c_x1 = v1_[obase]; c_x2 = v2_[obase]; c_a = a[obase]; c_b = b[obase];
-  }
-  for (int r = 0; r < num_boot; r++) {
-    Sums2D sums;
-    int32_t dn = n;
-    bool live = true;
-    // this lane's bin, as in k_boot1d_replay -- but BOOT2D_BTPE_CAP is 0: measured on configs[3]'s share (250 x 2000 pairs, 335 bins
-    // per chain on average, 64-wide tiles in several rounds) one attempt per step takes 29.2 s against 16.8 s: the steps of this
-    // kernel are short (small inversion searches), and lanes that fall behind by different amounts turn the six coalesced 512-B
-    // operand rows of a step into up to 64 separate lines each.
-    int kl = 0;
-    for (;;) {
-      const bool act = run && kl < K;
-      const uint64_t act_mask = __ballot(act);
-      if (act_mask == 0) break;
-      constexpr int CAP2D = REC ? BOOT2D_REC_BTPE_CAP : BOOT2D_BTPE_CAP;
-      const int cap = (CAP2D > 0 && __popcll(act_mask) > BOOT_TAIL_LANES) ? CAP2D : 0;
-      int kn = kl + 1 < K ? kl + 1 : 0;
-      double n_pk, n_lq, n_x1, n_x2, n_a, n_b;
-      if constexpr (REC) {
-        const double *nx = rec + (int64_t)kn * 8;
-        double2 t0 = *(const double2 *)(nx), t1 = *(const double2 *)(nx + 2), t2 = *(const double2 *)(nx + 4);
-        n_pk = t0.x; n_lq = t0.y; n_x1 = t1.x; n_x2 = t1.y; n_a = t2.x; n_b = t2.y;
-      } else {
-        int64_t on = obase + (int64_t)kn * 64;
-        n_pk = pk_[on]; n_lq = lq_[on]; n_x1 = v1_[on]; n_x2 = v2_[on]; n_a = a[on]; n_b = b[on];
-      }
-      bool adv = false;
-      if (act) {
-        int32_t w;
-        bool pending = false;
-        if (kl < K - 1) {
-          w = 0;
-          if (live) {
-            if constexpr (FAST) w = npyrng::binomial_pre_capped<int32_t>(g, c_pk, c_lq, dn, cap, pending);
-            else w = npyrng::binomial_pre<int32_t, false>(g, c_pk, c_lq, dn);
-            if (!pending) {
-              dn -= w;
-              if (dn <= 0) live = false;
-            }
-          }
-        } else {
-          w = dn > 0 ? dn : 0;
-        }
-        if (!pending) {
-          if (w != 0) accumulate_2d(sums, w, c_x1, c_x2, c_a, c_b, omq);
-          adv = true;
-        }
-      }
-      if (adv) {
-        kl++;
-        c_pk = n_pk; c_lq = n_lq; c_x1 = n_x1; c_x2 = n_x2; c_a = n_a; c_b = n_b;
-      }
-    }
-    if (run) oc[r] = close_replicate_2d(sums, nobs);
+    const Planes2D ops{pk_, lq_, v1_, v2_, a, b, tile_ptr[tile] * 64 + lane};
+    tile_lockstep<FAST, BOOT2D_BTPE_CAP>(t, st0, st1, st2, st3, num_boot, stat, ops);
   }
 }
 
@@ -929,8 +922,7 @@ __global__ __launch_bounds__(256) void k_boot2d_fast(const double *__restrict__ 
   bool mine = r < num_boot;
   int64_t obase = tile_ptr[slot >> 6] * 64 + (slot & 63);
   double nobs = slot_nobs[slot], omq = slot_omq[slot];
-  uint64_t h = mix64(seed ^ mix64((uint64_t)slot_key[slot] * 0x100000001B3ull + (uint64_t)r));
-  npyrng::Pcg64 g{mix64(h), mix64(h + 1), mix64(h + 2), mix64(h + 3) | 1ull};
+  npyrng::Pcg64 g = fast_stream(seed, (uint64_t)slot_key[slot], r);
   int32_t *wd = (w_dump && mine) ? w_dump + (slot * kmax_dump) * (int64_t)num_boot + r : nullptr;
   Sums2D sums;
   int32_t dn = (int32_t)nobs;  // N_g < 2^31 (checked by the host)
@@ -977,6 +969,14 @@ static auto tile_kernel(bool three, Pick pick) {
   return g_exact_arith ? pick(w2, std::false_type()) : pick(w2, std::true_type());
 }
 
+// What the four tile entry points check alike (``ptrs``: every table, operand and output pointer of the entry point is there), and
+// their grid (0: no tile, nothing to launch).  4 tiles per 256-thread workgroup: tiles t and t + 1024 (+-3) then meet on one SIMD,
+// which engine.pair_tiles relies on (one tile per workgroup was measured too: worse when everything is resident, a wash otherwise).
+static int tile_grid(bool ptrs, int64_t n_tiles, int32_t num_boot, int64_t ld, unsigned *blocks) {
+  MM_ARG(ptrs && n_tiles >= 0 && n_tiles < 2147483647LL && num_boot > 0 && ld >= (int64_t)num_boot + 1);
+  *blocks = (unsigned)((n_tiles + 3) / 4);
+  return MM_OK;
+}
 extern "C" {
 
 int mm_debug_wave_clock(int64_t *d_buf) {
@@ -994,19 +994,17 @@ int mm_boot1d_replay(const double *d_pk, const double *d_lq, const double *d_v, 
                      const double *d_slot_omq, const int64_t *d_slot_row, const uint64_t pcg_state[4], int32_t num_boot,
                      int32_t mean_only, int64_t ld, double *d_out_mean, double *d_out_var, int32_t *d_w_dump, int32_t kmax_dump,
                      int64_t co_resident_waves, const mm_chain_tiles *chains, void *stream) {
-  MM_ARG(d_pk && d_lq && d_v && d_a && d_b && d_tile_ptr && d_slot_K && d_slot_nobs && d_slot_omq && d_slot_row && pcg_state);
+  unsigned blocks;
+  const bool ptrs = d_pk && d_lq && d_v && d_a && d_b && d_tile_ptr && d_slot_K && d_slot_nobs && d_slot_omq && d_slot_row && pcg_state;
+  if (int rc = tile_grid(ptrs && d_out_mean && d_out_var, n_tiles, num_boot, ld, &blocks)) return rc;
   ChainArgs ca;
   if (int rc = chain_args_of(chains, &ca)) return rc;
-  MM_ARG(d_out_mean && d_out_var && n_tiles >= 0 && num_boot > 0 && ld >= (int64_t)num_boot + 1);
-  if (n_tiles == 0) return MM_OK;
-  MM_ARG(n_tiles < 2147483647LL);
-  // 4 tiles per 256-thread workgroup: tiles t and t + 1024 (+-3) then meet on one SIMD, which engine.pair_tiles relies on
-  // (one tile per workgroup was measured too: worse when everything is resident, a wash in the many-tile regime)
+  if (blocks == 0) return MM_OK;
   // the 168-VGPR build (three waves per SIMD) when this launch and the chain-kernel waves running beside it need more than two
   // wave slots per SIMD; the two-wave build otherwise
   const bool three = n_tiles + (co_resident_waves > 0 ? co_resident_waves : 0) > 2048;
   auto kern = tile_kernel(three, [](auto minw, auto fast) { return &k_boot1d_replay<minw(), fast()>; });
-  hipLaunchKernelGGL(kern, dim3((unsigned)((n_tiles + 3) / 4)), dim3(256), 0, (hipStream_t)stream, d_pk, d_lq, d_v, d_a, d_b,
+  hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), 0, (hipStream_t)stream, d_pk, d_lq, d_v, d_a, d_b,
                      d_tile_ptr, n_tiles, d_slot_K, d_slot_nobs, d_slot_omq, d_slot_row, pcg_state[0], pcg_state[1], pcg_state[2],
                      pcg_state[3], num_boot, mean_only, ld, d_out_mean, d_out_var, d_w_dump, kmax_dump, g_wave_clock, ca);
   MM_LAUNCH_CHECK();
@@ -1017,15 +1015,15 @@ int mm_boot1d_free(const double *d_recs, const int64_t *d_slot_rec, int64_t n_ti
                    const double *d_slot_omq, const int64_t *d_slot_row, const uint64_t pcg_state[4], int32_t num_boot, int32_t mean_only,
                    int64_t ld, double *d_out_mean, double *d_out_var, int32_t *d_w_dump, int32_t kmax_dump, const mm_chain_tiles *chains,
                    void *stream) {
-  MM_ARG(d_recs && d_slot_rec && d_slot_K && d_slot_nobs && d_slot_omq && d_slot_row && pcg_state);
+  unsigned blocks;
+  const bool ptrs = d_recs && d_slot_rec && d_slot_K && d_slot_nobs && d_slot_omq && d_slot_row && pcg_state;
+  if (int rc = tile_grid(ptrs && d_out_mean && d_out_var, n_tiles, num_boot, ld, &blocks)) return rc;
   ChainArgs ca;
   if (int rc = chain_args_of(chains, &ca)) return rc;
-  MM_ARG(d_out_mean && d_out_var && n_tiles >= 0 && num_boot > 0 && ld >= (int64_t)num_boot + 1);
-  if (n_tiles == 0) return MM_OK;
-  MM_ARG(n_tiles < 2147483647LL);
+  if (blocks == 0) return MM_OK;
   // the register budgets of mm_boot1d_replay: three waves per SIMD beyond 2,048 tiles
   auto kern = tile_kernel(n_tiles > 2048, [](auto minw, auto fast) { return &k_boot1d_free<minw(), fast()>; });
-  hipLaunchKernelGGL(kern, dim3((unsigned)((n_tiles + 3) / 4)), dim3(256), 0, (hipStream_t)stream, d_recs, d_slot_rec, n_tiles, d_slot_K,
+  hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), 0, (hipStream_t)stream, d_recs, d_slot_rec, n_tiles, d_slot_K,
                      d_slot_nobs, d_slot_omq, d_slot_row, pcg_state[0], pcg_state[1], pcg_state[2], pcg_state[3], num_boot, mean_only, ld,
                      d_out_mean, d_out_var, d_w_dump, kmax_dump, g_wave_clock, ca);
   MM_LAUNCH_CHECK();
@@ -1088,12 +1086,12 @@ int mm_boot2d_replay(const double *d_pk, const double *d_lq, const double *d_v1,
                      const double *d_b, const int64_t *d_tile_ptr, int64_t n_tiles, const int32_t *d_slot_K,
                      const double *d_slot_nobs, const double *d_slot_omq, const int64_t *d_slot_row, const uint64_t pcg_state[4],
                      int32_t num_boot, int64_t ld, double *d_out_corr, void *stream) {
-  MM_ARG(d_pk && d_lq && d_v1 && d_v2 && d_a && d_b && d_tile_ptr && d_slot_K && d_slot_nobs && d_slot_omq && d_slot_row && pcg_state);
-  MM_ARG(d_out_corr && n_tiles >= 0 && num_boot > 0 && ld >= (int64_t)num_boot + 1);
-  if (n_tiles == 0) return MM_OK;
-  MM_ARG(n_tiles < 2147483647LL);
+  unsigned blocks;
+  const bool ptrs = d_pk && d_lq && d_v1 && d_v2 && d_a && d_b && d_tile_ptr && d_slot_K && d_slot_nobs && d_slot_omq && d_slot_row && pcg_state;
+  if (int rc = tile_grid(ptrs && d_out_corr, n_tiles, num_boot, ld, &blocks)) return rc;
+  if (blocks == 0) return MM_OK;
   auto kern = tile_kernel(n_tiles > 2048, [](auto minw, auto fast) { return &k_boot2d_replay<minw(), fast(), false>; });
-  hipLaunchKernelGGL(kern, dim3((unsigned)((n_tiles + 3) / 4)), dim3(256), 0, (hipStream_t)stream, d_pk, d_lq, d_v1, d_v2, d_a, d_b,
+  hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), 0, (hipStream_t)stream, d_pk, d_lq, d_v1, d_v2, d_a, d_b,
                      d_tile_ptr, n_tiles, d_slot_K, d_slot_nobs, d_slot_omq, d_slot_row, pcg_state[0], pcg_state[1], pcg_state[2],
                      pcg_state[3], num_boot, ld, d_out_corr, (const int64_t *)nullptr);
   MM_LAUNCH_CHECK();
@@ -1103,13 +1101,13 @@ int mm_boot2d_replay(const double *d_pk, const double *d_lq, const double *d_v1,
 int mm_boot2d_replay_rec(const double *d_recs, const int64_t *d_slot_rec, int64_t n_tiles, const int32_t *d_slot_K,
                          const double *d_slot_nobs, const double *d_slot_omq, const int64_t *d_slot_row, const uint64_t pcg_state[4],
                          int32_t num_boot, int64_t ld, double *d_out_corr, void *stream) {
-  MM_ARG(d_recs && d_slot_rec && d_slot_K && d_slot_nobs && d_slot_omq && d_slot_row && pcg_state);
-  MM_ARG(d_out_corr && n_tiles >= 0 && num_boot > 0 && ld >= (int64_t)num_boot + 1);
-  if (n_tiles == 0) return MM_OK;
-  MM_ARG(n_tiles < 2147483647LL);
+  unsigned blocks;
+  const bool ptrs = d_recs && d_slot_rec && d_slot_K && d_slot_nobs && d_slot_omq && d_slot_row && pcg_state;
+  if (int rc = tile_grid(ptrs && d_out_corr, n_tiles, num_boot, ld, &blocks)) return rc;
+  if (blocks == 0) return MM_OK;
   auto kern = tile_kernel(n_tiles > 2048, [](auto minw, auto fast) { return &k_boot2d_replay<minw(), fast(), true>; });
   const double *nul = nullptr;
-  hipLaunchKernelGGL(kern, dim3((unsigned)((n_tiles + 3) / 4)), dim3(256), 0, (hipStream_t)stream, d_recs, nul, nul, nul, nul, nul,
+  hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), 0, (hipStream_t)stream, d_recs, nul, nul, nul, nul, nul,
                      (const int64_t *)nullptr, n_tiles, d_slot_K, d_slot_nobs, d_slot_omq, d_slot_row, pcg_state[0], pcg_state[1],
                      pcg_state[2], pcg_state[3], num_boot, ld, d_out_corr, d_slot_rec);
   MM_LAUNCH_CHECK();
