@@ -413,6 +413,14 @@ int mm_family_maxt(const double *d_ym, const double *d_yv, int64_t ld, int32_t n
                    const int32_t *d_test_gene, const int32_t *d_test_design, const int32_t *d_design_ptr, const int32_t *d_design_grp,
                    const double *d_design_w, const double *d_scale, int32_t stage_cap, int64_t n_fam, double *d_maxrow, double *d_adj,
                    double *d_fam, void *stream);
+/* the same adjustment on ONE response plane (the replicate correlations of Bootstrap2D: ht_2d_posthoc), with the tables of
+ * mm_contrast_design1_stats: d_scale [n_tests][1], d_maxrow [n_fam][ld], d_adj [n_tests][1][2] (t0, n_adj), d_fam [n_fam][1][2]
+ * (n_valid_family, n_included).  A column is valid for a member when every listed group is finite there in this plane; everything
+ * else -- inclusion, family-valid columns, the order of the maximum, stage_cap, the cells that are written -- as above. */
+int mm_family_maxt1(const double *d_y, int64_t ld, int32_t num_boot, int32_t n_groups, const int32_t *d_family_ptr,
+                    const int32_t *d_test_row, const int32_t *d_test_design, const int32_t *d_design_ptr, const int32_t *d_design_grp,
+                    const double *d_design_w, const double *d_scale, int32_t stage_cap, int64_t n_fam, double *d_maxrow, double *d_adj,
+                    double *d_fam, void *stream);
 
 /* ---- joint test of a block of treatment columns (ht_1d_joint) ------------------------------------------------------
  * test t applies the r = design_rank[d] linear forms of design d = test_design[t] to every replicate column of gene

@@ -81,6 +81,7 @@ _SIGS = {
     "mm_contrast_design_rows": ([c_void_p, c_void_p, c_int64, c_int32, c_int32] + [c_void_p] * 5 + [c_int64, c_int32, c_void_p, c_void_p],
                                 ctypes.c_int),
     "mm_family_maxt": ([c_void_p, c_void_p, c_int64, c_int32, c_int32] + [c_void_p] * 7 + [c_int32, c_int64] + [c_void_p] * 4, ctypes.c_int),
+    "mm_family_maxt1": ([c_void_p, c_int64, c_int32, c_int32] + [c_void_p] * 7 + [c_int32, c_int64] + [c_void_p] * 4, ctypes.c_int),
     "mm_joint_stats": ([c_void_p, c_void_p, c_int64, c_int32, c_int32] + [c_void_p] * 7 + [c_int64, c_void_p, c_void_p, c_void_p], ctypes.c_int),
     "mm_joint1_stats": ([c_void_p, c_int64, c_int32, c_int32] + [c_void_p] * 7 + [c_int64, c_void_p, c_void_p], ctypes.c_int),
     "mm_contrast_design1_stats": ([c_void_p, c_int64, c_int32, c_int32] + [c_void_p] * 5 + [c_int64, c_void_p, c_void_p], ctypes.c_int),

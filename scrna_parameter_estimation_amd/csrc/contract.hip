@@ -604,6 +604,24 @@ __global__ __launch_bounds__(K9_THREADS) void k_family_maxt(const double *__rest
                  maxrow + f * 2 * ld, adj + (int64_t)t0 * 4, fam + f * 4, sm, red);
 }
 
+// The one-plane entry (ht_2d_posthoc: the replicate correlations of Bootstrap2D): scale [test][1], maxrow [family][ld],
+// adj [test][1][2], fam [family][1][2]; a column is valid for a member when every listed group is finite in this plane.
+__global__ __launch_bounds__(K9_THREADS) void k_family_maxt1(const double *__restrict__ y, int64_t ld, int32_t num_boot, int32_t n_groups,
+                                                             const int32_t *__restrict__ family_ptr, const int32_t *__restrict__ test_row,
+                                                             const int32_t *__restrict__ test_design,
+                                                             const int32_t *__restrict__ design_ptr, const int32_t *__restrict__ design_grp,
+                                                             const double *__restrict__ design_w, const double *__restrict__ scale,
+                                                             int32_t stage_cap, double *__restrict__ maxrow, double *__restrict__ adj,
+                                                             double *__restrict__ fam) {
+  extern __shared__ double sm[];
+  __shared__ double red[K9_THREADS / 64];
+  int64_t f = blockIdx.x;
+  int t0 = family_ptr[f], m = family_ptr[f + 1] - t0;
+  const double *const yp[1] = {y};
+  family_maxt<1>(yp, ld, num_boot, n_groups, m > 0 ? test_row[t0] : 0, t0, m, test_design, design_ptr, design_grp, design_w, scale, stage_cap,
+                 maxrow + f * ld, adj + (int64_t)t0 * 2, fam + f * 2, sm, red);
+}
+
 // ------------------------------------------------------------------------------------------------
 // Joint test of a block of treatment columns (ht_1d_joint): test t applies the r linear forms of design d = test_design[t] --
 // L [r][n_d] row-major at design_L + design_lofs[d], over the n_d groups design_grp[design_ptr[d] .. design_ptr[d + 1]) -- to
@@ -1118,6 +1136,22 @@ int mm_family_maxt(const double *d_ym, const double *d_yv, int64_t ld, int32_t n
   size_t shm = (size_t)stage_cap * 2 * 2 * 8;
   hipLaunchKernelGGL(k_family_maxt, dim3((unsigned)n_fam), dim3(K9_THREADS), shm, (hipStream_t)stream, d_ym, d_yv, ld, num_boot, n_groups,
                      d_family_ptr, d_test_gene, d_test_design, d_design_ptr, d_design_grp, d_design_w, d_scale, stage_cap, d_maxrow, d_adj,
+                     d_fam);
+  MM_LAUNCH_CHECK();
+  return MM_OK;
+}
+
+int mm_family_maxt1(const double *d_y, int64_t ld, int32_t num_boot, int32_t n_groups, const int32_t *d_family_ptr,
+                    const int32_t *d_test_row, const int32_t *d_test_design, const int32_t *d_design_ptr, const int32_t *d_design_grp,
+                    const double *d_design_w, const double *d_scale, int32_t stage_cap, int64_t n_fam, double *d_maxrow, double *d_adj,
+                    double *d_fam, void *stream) {
+  MM_ARG(n_fam >= 0 && n_fam < 2147483647LL && stage_cap >= 0 && stage_cap <= FM_MAX_STAGED);
+  int rc = design_args(d_y && d_family_ptr && d_scale && d_maxrow && d_adj && d_fam, ld, num_boot, n_groups, d_test_row, d_test_design,
+                       d_design_ptr, d_design_grp, d_design_w, 0);
+  if (rc != MM_OK || n_fam == 0) return rc;
+  size_t shm = (size_t)stage_cap * 1 * 2 * 8;
+  hipLaunchKernelGGL(k_family_maxt1, dim3((unsigned)n_fam), dim3(K9_THREADS), shm, (hipStream_t)stream, d_y, ld, num_boot, n_groups,
+                     d_family_ptr, d_test_row, d_test_design, d_design_ptr, d_design_grp, d_design_w, d_scale, stage_cap, d_maxrow, d_adj,
                      d_fam);
   MM_LAUNCH_CHECK();
   return MM_OK;

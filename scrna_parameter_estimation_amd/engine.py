@@ -1022,21 +1022,8 @@ class Bootstrap1D:
         the largest family, at most ``FAMILY_MAX_STAGED``); no number depends on it.  Returns ``maxrow`` (device [n_fam][2][ld]:
         the maximum row of every family and plane, NaN in column 0 and the columns that are not family-valid), ``adj`` (host
         [n_tests][2][2]: t0, n_adj) and ``fam`` (host [n_fam][2][2]: n_valid_family, n_included)."""
-        torch = _torch()
-        family_ptr, scale, d_tab = _family_tables(family_ptr, test_gene, test_design, design_ptr, design_grp, design_w, scale, self.n_tested,
-                                                  self.ng)
-        n_fam, n_tests = len(family_ptr) - 1, len(scale)
-        if stage_cap is None:
-            stage_cap = min(FAMILY_MAX_STAGED, int(np.diff(family_ptr).max()) if n_fam else 0)
-        if not 0 <= int(stage_cap) <= FAMILY_MAX_STAGED:
-            raise ValueError(f"family_maxt: stage_cap must lie in [0, {FAMILY_MAX_STAGED}]")
-        maxrow = empty((max(1, n_fam), 2, self.ld), torch.float64)
-        adj = empty((max(1, n_tests), 2, 2), torch.float64)
-        fam = empty((max(1, n_fam), 2, 2), torch.float64)
-        d_fp, d_scale = dev(family_ptr), _up(scale.reshape(-1))
-        _lib.call("mm_family_maxt", P(self.ym), P(self.yv), self.ld, self.B, self.ng, P(d_fp), *map(P, d_tab), P(d_scale), int(stage_cap),
-                  n_fam, P(maxrow), P(adj), P(fam), _stream())
-        return maxrow[:n_fam], host(adj)[:n_tests], host(fam)[:n_fam]
+        return _family_maxt([self.ym, self.yv], self.ld, self.B, self.ng, self.n_tested, family_ptr, test_gene, test_design, design_ptr,
+                            design_grp, design_w, scale, stage_cap)
 
     def joint(self, test_gene, tables):
         """Joint tests of a treatment block (mm_joint_stats): test t applies the linear forms of design ``tables.test_design[t]``
@@ -1124,11 +1111,12 @@ def _design_tables(test_row, test_design, design_ptr, design_grp, design_w, n_ro
 FAMILY_MAX_STAGED = 1024      # members of a family whose (coef0, scale) mm_family_maxt can keep in LDS (contract.hip: FM_MAX_STAGED)
 
 
-def family_scale(st_m, st_v):
-    """``scale`` [test][2] of ``Bootstrap1D.family_maxt`` from the records of ``contrast_design``: 1 / se where the record is a test
-    (finite coef0, finite se > 0, n_valid >= 1, not all_equal), else 0."""
-    out = np.zeros((len(st_m), 2))
-    for k, st in enumerate((st_m, st_v)):
+def family_scale(*stats):
+    """``scale`` [test][plane] of ``family_maxt`` from the records of ``contrast_design``, one record array per plane (st_m, st_v of
+    Bootstrap1D: [test][2]; the one of Bootstrap2D: [test][1]): 1 / se where the record is a test (finite coef0, finite se > 0,
+    n_valid >= 1, not all_equal), else 0."""
+    out = np.zeros((len(stats[0]), len(stats)))
+    for k, st in enumerate(stats):
         st = np.asarray(st, dtype=np.float64).reshape(-1, 8)
         with np.errstate(invalid="ignore", divide="ignore"):
             live = np.isfinite(st[:, 0]) & np.isfinite(st[:, 1]) & (st[:, 1] > 0) & (st[:, 2] >= 1) & (st[:, 5] == 0)
@@ -1136,10 +1124,10 @@ def family_scale(st_m, st_v):
     return out
 
 
-def _family_tables(family_ptr, test_row, test_design, design_ptr, design_grp, design_w, scale, n_rows, ng):
-    """The tables of mm_family_maxt, checked (the kernel trusts them) and uploaded: those of ``_design_tables``, ``family_ptr`` a
-    CSR pointer over the tests whose families each sit on one row block, and one ``scale`` pair per test.  Returns family_ptr
-    (int32) and scale (fp64 [n_tests][2]) as host arrays and the device tensors of ``_design_tables``."""
+def _family_tables(family_ptr, test_row, test_design, design_ptr, design_grp, design_w, scale, n_rows, ng, n_planes=2):
+    """The tables of mm_family_maxt / mm_family_maxt1, checked (the kernel trusts them) and uploaded: those of ``_design_tables``,
+    ``family_ptr`` a CSR pointer over the tests whose families each sit on one row block, and one ``scale`` per test and plane.
+    Returns family_ptr (int32) and scale (fp64 [n_tests][n_planes]) as host arrays and the device tensors of ``_design_tables``."""
     family_ptr = np.asarray(family_ptr, dtype=np.int64).reshape(-1)
     scale = np.asarray(scale, dtype=np.float64)
 
@@ -1150,11 +1138,31 @@ def _family_tables(family_ptr, test_row, test_design, design_ptr, design_grp, de
         fam_of = np.repeat(np.arange(len(family_ptr) - 1), np.diff(family_ptr))
         if n_tests and (test_row != test_row[family_ptr[fam_of]]).any():
             raise ValueError("family_maxt: the tests of a family must share one test_row")
-        if scale.shape != (n_tests, 2):
-            raise ValueError("family_maxt: scale must be [n_tests][2]")
+        if scale.shape != (n_tests, n_planes):
+            raise ValueError(f"family_maxt: scale must be [n_tests][{n_planes}]")
 
     _, _, d_tab = _design_tables(test_row, test_design, design_ptr, design_grp, design_w, n_rows, ng, what="family_maxt", check=check)
     return family_ptr.astype(np.int32), scale, d_tab
+
+
+def _family_maxt(planes, ld, B, ng, n_rows, family_ptr, test_row, test_design, design_ptr, design_grp, design_w, scale, stage_cap=None):
+    """``family_maxt`` of Bootstrap1D (``planes`` = [ym, yv]: mm_family_maxt) and Bootstrap2D ([yc]: mm_family_maxt1).  Returns
+    ``maxrow`` (device [n_fam][n_planes][ld]), ``adj`` (host [n_tests][n_planes][2]) and ``fam`` (host [n_fam][n_planes][2])."""
+    torch = _torch()
+    n_planes = len(planes)
+    family_ptr, scale, d_tab = _family_tables(family_ptr, test_row, test_design, design_ptr, design_grp, design_w, scale, n_rows, ng, n_planes)
+    n_fam, n_tests = len(family_ptr) - 1, len(scale)
+    if stage_cap is None:
+        stage_cap = min(FAMILY_MAX_STAGED, int(np.diff(family_ptr).max()) if n_fam else 0)
+    if not 0 <= int(stage_cap) <= FAMILY_MAX_STAGED:
+        raise ValueError(f"family_maxt: stage_cap must lie in [0, {FAMILY_MAX_STAGED}]")
+    maxrow = empty((max(1, n_fam), n_planes, ld), torch.float64)
+    adj = empty((max(1, n_tests), n_planes, 2), torch.float64)
+    fam = empty((max(1, n_fam), n_planes, 2), torch.float64)
+    d_fp, d_scale = dev(family_ptr), _up(scale.reshape(-1))
+    _lib.call("mm_family_maxt1" if n_planes == 1 else "mm_family_maxt", *map(P, planes), ld, B, ng, P(d_fp), *map(P, d_tab), P(d_scale),
+              int(stage_cap), n_fam, P(maxrow), P(adj), P(fam), _stream())
+    return maxrow[:n_fam], host(adj)[:n_tests], host(fam)[:n_fam]
 
 
 def _contrast_design(planes, ld, B, ng, n_rows, test_row, test_design, design_ptr, design_grp, design_w, rows_design=None):
@@ -1513,6 +1521,15 @@ class Bootstrap2D:
         (stats,), rows = _contrast_design([self.yc], self.ld, self.B, self.ng, self.n_pairs, test_pair, test_design, design_ptr, design_grp,
                                           design_w)
         return stats, functools.partial(rows, 0)
+
+    def family_maxt(self, family_ptr, test_pair, test_design, design_ptr, design_grp, design_w, scale, stage_cap=None):
+        """Single-step max-T adjustment over families of design contrasts on the correlation rows (mm_family_maxt1), as
+        ``Bootstrap1D.family_maxt`` on one plane: the tests ``family_ptr[f]:family_ptr[f + 1]`` -- consecutive, on one pair of
+        ``test_pair`` (device pair order, ``self.order``) -- are family f, with the tables of ``contrast_design``; ``scale``
+        [test][1] is ``family_scale`` of its records.  Returns ``maxrow`` (device [n_fam][1][ld]), ``adj`` (host [n_tests][1][2]:
+        t0, n_adj) and ``fam`` (host [n_fam][1][2]: n_valid_family, n_included)."""
+        return _family_maxt([self.yc], self.ld, self.B, self.ng, self.n_pairs, family_ptr, test_pair, test_design, design_ptr, design_grp,
+                            design_w, scale, stage_cap)
 
     def joint(self, test_pair, tables):
         """Joint tests of a treatment block on the correlation rows (mm_joint1_stats): test t applies the linear forms of design

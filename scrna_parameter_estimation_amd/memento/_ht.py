@@ -314,6 +314,21 @@ class PosthocDesigns:
         return np.concatenate(ptr).astype(np.int32), np.concatenate(grp).astype(np.int32), np.concatenate(w).astype(np.float64)
 
 
+def adjusted_columns(p, adj, fam, n_mem, se=None, crit=None):
+    """The adjusted columns of ``ht_1d_posthoc`` / ``ht_2d_posthoc`` on ONE plane, from what ``family_maxt`` returns for families
+    of ``n_mem`` members each: ``p`` [test] the members' own p-values, ``adj`` [test][2] (t0, n_adj), ``fam`` [family][2]
+    (n_valid_family, n_included).  -> (``p_adj`` [test]: max((1 + n_adj) / (1 + n_valid_family), p) where the member is included,
+    NaN elsewhere; ``n_family`` [test] int64: the family's included members; ``half`` [test]: the half-width ``crit`` [family] x
+    ``se`` [test] of the simultaneous interval of an included member, NaN elsewhere -- None without ``crit``)."""
+    live = ~np.isnan(adj[:, 0])
+    p_adj = (1 + adj[:, 1]) / (1 + np.repeat(fam[:, 0], n_mem))
+    with np.errstate(invalid="ignore"):
+        p_adj = np.where(live, np.maximum(p_adj, p), np.nan)
+    n_family = np.repeat(fam[:, 1], n_mem).astype(np.int64)
+    half = None if crit is None else np.where(live, np.repeat(crit, n_mem) * se, np.nan)
+    return p_adj, n_family, half
+
+
 def surviving_cols(bs, good, num_boot):
     """The replicate columns that survive hypothesis_test.py:249-251 / :372-373 (``bs.valid_cols``); (None, None) when nothing
     was dropped (the usual case): identity map."""
@@ -351,11 +366,12 @@ def distinct_pairs(idx1, idx2):
     return np.asarray(first, dtype=np.int64), members
 
 
-def pair_plan(m, st, num_boot, max_rows):
+def pair_plan(m, st, num_boot, max_rows, extra_rows=0):
     """The pairs of ``compute_2d_moments`` as the 2D tests run them: ``first`` / ``members`` (``distinct_pairs`` over the
     ``n_conv`` requested pairs), ``c1`` / ``c2`` = the distinct pairs' column slots, ``true_corr`` [pair][group], ``skip``
     (hypothesis_test.py:325), ``chain_key`` and the chunk ``bounds``: pairs are independent, so they run in chunks of at most
-    ``max_rows`` replicate rows ([pair x group][B+1] fp64) AND at most a third of the free HBM in histogram tables."""
+    ``max_rows`` replicate rows ([pair x group][B+1] fp64) AND at most a third of the free HBM in histogram tables.  ``extra_rows``:
+    the rows of that width a pair holds beside its groups' (the maximum row of ``ht_2d_posthoc``), counted against ``max_rows``."""
     groups = m['groups']
     ng = len(groups)
     idx1, idx2 = m['2d_moments']['gene_idx_1'], m['2d_moments']['gene_idx_2']
@@ -369,7 +385,7 @@ def pair_plan(m, st, num_boot, max_rows):
         skip = np.isnan(true_corr) | (np.abs(true_corr) == 1)
     if max_rows is None:
         max_rows = min(1 << 19, engine.auto_max_rows(num_boot + 1, arrays=1))   # also bounds the per-pair 2D tables
-    chunk = max(1, int(max_rows) // max(1, ng))
+    chunk = max(1, int(max_rows) // max(1, ng + int(extra_rows)))
     tab_bytes = engine.pair_table_bytes(st.maxx, st.cols.genes, c1, c2, ng, len(st.sf_table)) if P_ else np.zeros(0, dtype=np.int64)
     budget = max(1 << 28, engine._torch().cuda.mem_get_info()[0] // 3)
     bounds, acc = [0], 0

@@ -873,17 +873,13 @@ def ht_1d_posthoc(adata, treatment_col=None, control=None, num_boot=10000, num_c
             crit = engine.host(q).reshape(G, 2)
         for k, (tag, stt) in enumerate((('mean', st_m), ('var', st_v))):
             p = _asl.asl_from_stats(stt, approx, lambda idx, w=k: rows(w, idx), num_cpus, 'bootstrap')
-            live = ~np.isnan(adj[:, k, 0])
-            p_adj = (1 + adj[:, k, 1]) / (1 + np.repeat(fam[:, k, 0], n_mem))
-            with np.errstate(invalid="ignore"):
-                p_adj = np.where(live, np.maximum(p_adj, p), np.nan)
+            p_adj, n_family, half = _ht.adjusted_columns(p, adj[:, k], fam[:, k], n_mem, stt[:, 1], crit[:, k] if ci is not None else None)
             cols[tag + '_coef'].append(stt[:, 0])
             cols[tag + '_se'].append(stt[:, 1])
             cols[tag + '_asl'].append(p)
             cols[tag + '_asl_adj'].append(p_adj)
-            cols[tag + '_n_family'].append(np.repeat(fam[:, k, 1], n_mem).astype(np.int64))
+            cols[tag + '_n_family'].append(n_family)
             if ci is not None:
-                half = np.where(live, np.repeat(crit[:, k], n_mem) * stt[:, 1], np.nan)
                 cols[tag + '_sci'].append(np.column_stack([stt[:, 0] - half, stt[:, 0] + half]))
 
     for c in _ht.chunks_1d(st, mv, num_boot, chunk):
@@ -1227,6 +1223,100 @@ def ht_2d_joint(adata, treatment, covariate=None, num_boot=10000, rng='replay', 
     pairs = list(m['2d_moments']['gene_pairs'])
     return pd.DataFrame({'gene_1': [a for a, _ in pairs], 'gene_2': [b for _, b in pairs], 'df': out['df'],
                          'corr_stat': out['corr_stat'], 'corr_pval': out['corr_asl']})
+
+
+def ht_2d_posthoc(adata, treatment_col=None, control=None, num_boot=10000, num_cpus=1, rng='replay', fill_seed=0, max_rows=None,
+                  approx=False, *, ci=None):
+    """WHICH levels of a factor differ in COEXPRESSION: the pairwise contrasts between the levels for every gene pair of
+    ``compute_2d_moments``, each with its own test and with a p-value adjusted for the pair's whole family of contrasts
+    (``ht_2d_joint`` answers whether the pair's correlation differs at all).
+
+    Every argument means what it means in ``ht_1d_posthoc``.  Levels, strata, ``control`` and ``treatment_col`` are those of
+    ``ht_2d_vs_control``: ``treatment_col=None`` makes every group a level and a contrast the plain two-group difference of the
+    correlations; ``treatment_col='x'`` makes the values of that label column the levels and every other label column a
+    covariate, and the test of level a against level b is EXACTLY the test ``ht_2d_vs_control(control=b, treatment_col='x')`` makes
+    of a -- with the same ``np.random`` seed, ``fill_seed`` and ``max_rows`` the same ``corr_coef``, ``corr_se`` and ``corr_pval``,
+    NaNs included.  ``control=None``: all unordered pairs of levels, levels in first-appearance order, (level_a, level_b) with a
+    after b, rows ordered by b, then a.  ``control=value``: every other level against that one.
+
+    Every (pair, group) chain is bootstrapped once (instead of once per control level in a loop of ``ht_2d_vs_control`` calls),
+    so replicate column c of all contrasts of a gene pair is one joint draw of its family, and the adjustment is the single-step
+    max-T of ``ht_1d_posthoc`` on the one plane of replicate correlations (mm_family_maxt1): a member is INCLUDED when it has a test;
+    M[c] = max_j |coef_j[c] - coef_j[0]| / se_j over the included members on the columns valid for all of them;
+    p_adj_j = (1 + #{c : M[c] > |coef_j[0]| / se_j}) / (1 + n_valid), reported as ``corr_pval_adj`` = max(p_adj_j, the member's own
+    p-value); NaN for a member without a test, which does not enter the maximum.  ``n_family`` is the number of included members.
+    ``ci=level`` adds the simultaneous intervals coef_j[0] -+ np.nanquantile(M[1:], level) * se_j: ``corr_sci_lo, corr_sci_hi``.
+
+    Pairs and the random stream are those of ``ht_2d_moments`` / ``ht_2d_vs_control`` / ``ht_2d_joint``: unordered duplicates
+    share the first one's result, a self pair stays NaN with ``n_family`` 0, a (pair, group) with a NaN or +-1 correlation is
+    skipped and the pair keeps the family of its other groups or levels; three hash uniforms per live (pair, group) come from the
+    global ``np.random`` stream, pair-major, up front.  A family is the contrasts of one pair and never spans chunks; chunking and
+    ``max_rows`` (which also counts the one maximum row a pair adds) change no number under either generator.
+
+    Not offered: ``resampling`` other than the centred bootstrap, ``resample_rep``, ``strict`` and ``treatment_for_gene``; a run
+    over several ranks raises NotImplementedError.
+
+    Returns a DataFrame (gene_1, gene_2, level_a, level_b, corr_coef, corr_se, corr_pval, corr_pval_adj, n_family), pair-major:
+    one block of rows per requested pair in the order of ``compute_2d_moments``, and stores the arrays in
+    ``uns['memento']['2d_ht_posthoc']``."""
+    _ht.check_args(rng, resampling='bootstrap')
+    _ht.ci_probs(ci)
+    m = adata.uns['memento']
+    st = m['_hip']
+    comm = getattr(st, 'comm', None)
+    if comm is not None and comm.world > 1:
+        raise NotImplementedError("ht_2d_posthoc on a run over several ranks: the results are not gathered across ranks")
+    designs, level_names = _posthoc_plan(m, treatment_col, control)
+    n_mem = len(designs.pairs)
+    if n_mem == 0:
+        raise ValueError("ht_2d_posthoc needs at least two levels")
+    st.last_bootstrap2d = st.last_posthoc2d = None    # (free the previous call's replicate rows before this call allocates its own)
+    plan = _ht.pair_plan(m, st, num_boot, max_rows, extra_rows=1)
+    uniforms = _ht.hash_uniforms(~plan.skip.reshape(-1), 3)
+    out = {k: np.full((plan.n_conv, n_mem), np.nan) for k in ('corr_coef', 'corr_se', 'corr_asl', 'corr_asl_adj')}
+    out['n_family'] = np.zeros((plan.n_conv, n_mem), dtype=np.int64)
+    if ci is not None:
+        out['corr_sci'] = np.full((plan.n_conv, n_mem * 2), np.nan)
+
+    def run_chunk(c):
+        bs, n_ch = c.bs, c.n_ch
+        good = _ht.run_chunk_2d(c, plan, uniforms, rng, fill_seed)                 # device order
+        test_pair = np.repeat(np.arange(n_ch), n_mem)
+        family_ptr = np.arange(n_ch + 1, dtype=np.int64) * n_mem
+        tables = (test_pair, designs.tests(good), *designs.tables())
+        stt, rows = bs.contrast_design(*tables)
+        scale = engine.family_scale(stt)
+        maxrow, adj, fam = bs.family_maxt(family_ptr, *tables, scale)
+        st.last_posthoc2d = SimpleNamespace(family_ptr=family_ptr, tables=tables, scale=scale, adj=adj, fam=fam)   # (diagnostics / tests: the last pair chunk)
+        crit = None
+        if ci is not None:
+            q, _ = engine.row_quantiles(maxrow.reshape(-1, bs.ld), bs.ld, num_boot, [float(ci)])
+            crit = engine.host(q).reshape(n_ch)
+        p = _asl.asl_from_stats(stt, approx, rows, num_cpus, 'bootstrap')
+        p_adj, n_family, half = _ht.adjusted_columns(p, adj[:, 0], fam[:, 0], n_mem, stt[:, 1], crit)
+        for key, src in (('corr_coef', stt[:, 0]), ('corr_se', stt[:, 1]), ('corr_asl', p), ('corr_asl_adj', p_adj), ('n_family', n_family)):
+            _ht.scatter_pairs(c, plan, out[key], src)
+        if ci is not None:
+            _ht.scatter_pairs(c, plan, out['corr_sci'], np.column_stack([stt[:, 0] - half, stt[:, 0] + half]))
+
+    for c in _ht.chunks_2d(st, plan, num_boot):
+        run_chunk(c)
+    out = {k: v.reshape(-1, 2) if k == 'corr_sci' else v.reshape(-1) for k, v in out.items()}
+    level_a = [level_names[a] for a, _ in designs.pairs]
+    level_b = [level_names[b] for _, b in designs.pairs]
+    m['2d_ht_posthoc'] = dict(out, levels=list(level_names), level_a=level_a, level_b=level_b, treatment_col=treatment_col,
+                              control=None if control is None else level_b[0])
+    n_conv = plan.n_conv
+    pairs = list(m['2d_moments']['gene_pairs'])
+    df = pd.DataFrame({'gene_1': np.repeat([a for a, _ in pairs], n_mem), 'gene_2': np.repeat([b for _, b in pairs], n_mem),
+                       'level_a': np.tile(np.asarray(level_a, dtype=object), n_conv),
+                       'level_b': np.tile(np.asarray(level_b, dtype=object), n_conv)})
+    df['corr_coef'], df['corr_se'], df['corr_pval'], df['corr_pval_adj'] = out['corr_coef'], out['corr_se'], out['corr_asl'], out['corr_asl_adj']
+    df['n_family'] = out['n_family']
+    if ci is not None:
+        m['2d_ht_posthoc']['ci'] = float(ci)
+        df['corr_sci_lo'], df['corr_sci_hi'] = out['corr_sci'][:, 0], out['corr_sci'][:, 1]
+    return df
 
 
 # ----------------------------------------------------------------------------------------------
