@@ -288,6 +288,30 @@ int mm_boot1d_fast(const double *d_pk, const double *d_lq, const double *d_v, co
                    int32_t mean_only, int64_t ld, double *d_out_mean, double *d_out_var, int32_t *d_w_dump, int32_t kmax_dump,
                    void *stream);
 
+/* mm_boot1d_fast on a replicate RANGE (sequential bootstrap, ht_1d_vs_control(max_boot=...)): local replicate i in [0, rep_n)
+ * draws from the stream of global replicate rep_lo + i -- (seed, d_slot_key[s], rep_lo + i) -- and is stored in column 1 + i of
+ * row d_slot_row[s]; ld >= 1 + rep_n; d_w_dump (optional) is [slot][k < kmax_dump][i < rep_n].  mm_boot1d_fast is the case
+ * rep_lo = 0, rep_n = num_boot of the same kernel, so replicates [rep_lo, rep_lo + rep_n) made later, for some of the chains,
+ * are bit for bit those of a one-shot launch over [0, rep_lo + rep_n).
+ *   - rep_lo >= 0, rep_n >= 1 and rep_lo + rep_n <= 2^31 - 1.
+ *   - The stream seed is a function of key * 0x100000001B3 + r (mod 2^64): distinct (key, r) with 0 <= r < 0x100000001B3, the key
+ *     multiplier, and keys below 2^64 / 0x100000001B3 give distinct values, so no replicate range of one chain collides with a
+ *     range of another chain.
+ *   - A slot with d_slot_row[s] < 0 (or d_slot_K[s] < 2) writes nothing, as in mm_boot1d_fast: that is how the chains of closed
+ *     tests are skipped without a new tile layout.
+ *   - Column 0, the columns beyond rep_n and the rows of skipped slots are not written.
+ * The caller (memento.ht_1d_vs_control(rng='fast', max_boot=N, min_extreme=M)): every test gets num_boot replicates, and a test
+ * whose extreme count is still <= min_extreme goes on to the totals 2, 4, ... x num_boot, at most max_boot.  The 8-double test
+ * records of the rounds fold into one (counts add, mean and se pool), p = (c + 1) / (n + 1) over all rounds and no tail fit is
+ * made.  mm_boot_fill_log runs per round on the round's own planes: an invalid replicate is refilled from the valid replicates
+ * of the same round, with a refill seed derived from (fill_seed, round) -- uniform over valid replicates like the one-shot
+ * refill, statistically equivalent to it, identical where nothing is refilled. */
+int mm_boot1d_fast_range(const double *d_pk, const double *d_lq, const double *d_v, const double *d_a, const double *d_b,
+                         const int64_t *d_tile_ptr, int64_t n_slots, const int32_t *d_slot_K, const double *d_slot_nobs,
+                         const double *d_slot_omq, const int64_t *d_slot_row, const int64_t *d_slot_key, uint64_t seed, int32_t rep_lo,
+                         int32_t rep_n, int32_t mean_only, int64_t ld, double *d_out_mean, double *d_out_var, int32_t *d_w_dump,
+                         int32_t kmax_dump, void *stream);
+
 /* ---- K8: residual variance, invalid-replicate fill, log  ---------------------------------------
  * replaces estimator._residual_variance + hypothesis_test._fill + np.log
  *   memento/estimator.py:103-111, memento/hypothesis_test.py:186-197.

@@ -911,6 +911,7 @@ class Bootstrap1D:
         torch, s = _torch(), _stream()
         ng, B, ld = self.ng, self.B, self.ld
         n_chain, n_async, n_tiles, n_launch, kmax_dump = self.n_chain, self.n_async, c.n_tiles, c.n_launch, self.kmax_dump
+        self._fast = None
         chain_pairs, async_pairs = c.chain_pairs, c.async_pairs
         self.w_dump = zeros((n_tiles * 64, kmax_dump, B), torch.int32) if dump_weights else None
         d_slot_K, d_nobs, d_omq, d_slot_pair = dev(t.slot_K), dev(t.nobs), dev(t.omq), dev(t.slot_pair)
@@ -963,6 +964,10 @@ class Bootstrap1D:
             _lib.call("mm_boot1d_fast", *[P(o) for o in t.ops], P(t.d_tile_ptr), n_tiles * 64, P(d_slot_K), P(d_nobs), P(d_omq), P(d_slot_pair),
                       P(d_slot_key), int(fill_seed) & ((1 << 64) - 1), B, int(mean_only), ld, P(self.ym), P(self.yv), P(self.w_dump),
                       kmax_dump, s)
+            # what a later launch on a replicate range reads (run_range): the operand planes live in self._opsbuf
+            self._fast = SimpleNamespace(ops=t.ops, d_tile_ptr=t.d_tile_ptr, n_slots=n_tiles * 64, d_slot_K=d_slot_K, d_nobs=d_nobs, d_omq=d_omq,
+                                         pair_slot=self.tile_slot, d_slot_key=d_slot_key, kmax=int(t.tile_k.max()),
+                                         seed=int(fill_seed) & ((1 << 64) - 1))
         elif n_tiles and c.use_free:
             d_slot_rec = dev(t.slot_rec)
             keep.append(d_slot_rec)
@@ -974,6 +979,60 @@ class Bootstrap1D:
         if n_launch:
             torch.cuda.current_stream().wait_stream(side)
         return keep
+
+    def launch_range(self, rep_lo, rep_n, open_pairs, planes, row_of_pair, mean_only=False, dump_weights=False):
+        """After ``run(fast=True)``: the replicates [rep_lo, rep_lo + rep_n) of the chains ``open_pairs`` (mm_boot1d_fast_range on the
+        kept operand planes, tile layout and stream keys; every other slot gets row -1 and writes nothing), raw -- before fill / log
+        -- into columns 1..rep_n of the rows ``row_of_pair`` of the caller's ``planes`` = (mean, var), fp64 device tensors
+        [rows][ld >= 1 + rep_n]; nothing else of them is written.  Chains of ``open_pairs`` that did not run (skipped, K < 2) are
+        left out.  Replicate rep_lo + i of a chain is bit for bit the one a one-shot ``run`` over more replicates stores in column
+        1 + rep_lo + i.  ``dump_weights``: keep the int32 weights in ``self.w_dump_range`` [slot][k][i] (slot =
+        ``self.tile_slot[pair]``)."""
+        torch, f = _torch(), getattr(self, "_fast", None)
+        if f is None:
+            raise RuntimeError("launch_range needs a preceding run(fast=True): the replay kernels keep no per-replicate streams")
+        rep_lo, rep_n = int(rep_lo), int(rep_n)
+        if rep_lo < 0 or rep_n < 1 or rep_lo + rep_n > 2 ** 31 - 1:
+            raise ValueError("launch_range: need rep_lo >= 0, rep_n >= 1 and rep_lo + rep_n <= 2^31 - 1")
+        pm, pv = planes
+        for x in (pm, pv):
+            if x.dtype != torch.float64 or not x.is_cuda or not x.is_contiguous() or x.dim() != 2 or x.shape != pm.shape or x.shape[1] < rep_n + 1:
+                raise ValueError("launch_range: planes must be two contiguous fp64 device tensors [rows][>= 1 + rep_n]")
+        open_pairs, row_of_pair = np.asarray(open_pairs, dtype=np.int64).reshape(-1), np.asarray(row_of_pair, dtype=np.int64).reshape(-1)
+        if len(open_pairs) != len(row_of_pair) or (len(open_pairs) and (open_pairs.min() < 0 or open_pairs.max() >= self.n_pairs)):
+            raise ValueError("launch_range: open_pairs / row_of_pair do not match the chains")
+        if len(row_of_pair) and (row_of_pair.min() < 0 or row_of_pair.max() >= pm.shape[0]):
+            raise ValueError("launch_range: row out of range")       # (the kernel trusts the rows)
+        slot = f.pair_slot[open_pairs]
+        slot_row = np.full(f.n_slots, -1, dtype=np.int64)
+        slot_row[slot[slot >= 0]] = row_of_pair[slot >= 0]
+        d_slot_row = dev(slot_row)
+        self.w_dump_range = zeros((f.n_slots, f.kmax, rep_n), torch.int32) if dump_weights else None
+        _lib.call("mm_boot1d_fast_range", *[P(o) for o in f.ops], P(f.d_tile_ptr), f.n_slots, P(f.d_slot_K), P(f.d_nobs), P(f.d_omq),
+                  P(d_slot_row), P(f.d_slot_key), f.seed, rep_lo, rep_n, int(mean_only), pm.shape[1], P(pm), P(pv),
+                  P(self.w_dump_range), f.kmax if dump_weights else 0, _stream())
+        return d_slot_row      # NB: stays referenced until the caller's next call on the stream
+
+    def run_range(self, rep_lo, rep_n, open_pairs, planes, row_of_pair, mv_fit, fill_seed, fill_keys, mean_only=False):
+        """``launch_range``, then mm_boot_fill_log over ALL rows of ``planes`` with refill seed ``fill_seed`` and the refill keys
+        ``fill_keys`` [row] (the chains' keys of the first run): an invalid replicate of the range is refilled from the valid
+        replicates of the SAME range.  Raises after a replay-mode ``run``.  Returns n_invalid [rows][2] (host), -1 = no valid
+        replicate (every row no chain wrote)."""
+        torch = _torch()
+        keep = self.launch_range(rep_lo, rep_n, open_pairs, planes, row_of_pair, mean_only)
+        pm, pv = planes
+        n_rows = pm.shape[0]
+        if len(np.shape(fill_keys)) != 1 or len(fill_keys) != n_rows:
+            raise ValueError("run_range: fill_keys must have one key per row")
+        n_inv = empty((max(1, n_rows), 2), torch.int32)
+        fit = (ctypes.c_double * 3)(*[float(x) for x in mv_fit])
+        if n_rows > 0:
+            d_keys = dev(np.asarray(fill_keys, dtype=np.int64))
+            _lib.call("mm_boot_fill_log", P(pm), P(pv), n_rows, pm.shape[1], int(rep_n), fit, 0, int(fill_seed) & ((1 << 64) - 1), P(n_inv),
+                      P(d_keys), _stream())
+        out = host(n_inv)[:n_rows]
+        del keep
+        return out
 
     def _fill_log(self, mv_fit, fill_mode, fill_seed, first_pair, fill_keys):
         """mm_boot_fill_log on the rows >= first_pair; returns n_invalid [rows][2] (host)."""

@@ -144,6 +144,171 @@ def run_chunk_1d(c, mv, rng, fill_seed, fill_keys, chain_keys, uniforms=None):
     return good.reshape(c.G, mv.ng), n_inv
 
 
+# ----------------------------------------------------------------------------------------------
+# 1D: sequential bootstrap (ht_1d_vs_control(max_boot=...)): records, schedule, stopping rule, rounds
+# ----------------------------------------------------------------------------------------------
+
+_M64 = (1 << 64) - 1
+
+
+def _mix64(x):
+    """The splitmix64 output function of csrc/boot.hip (mix64) on a Python int."""
+    x = (x + 0x9E3779B97F4A7C15) & _M64
+    x = ((x ^ (x >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    x = ((x ^ (x >> 27)) * 0x94D049BB133111EB) & _M64
+    return x ^ (x >> 31)
+
+
+def check_sequential(max_boot, min_extreme, num_boot, rng, approx, ci):
+    """The ``max_boot`` / ``min_extreme`` keywords of ``ht_1d_vs_control``; pure, runs before ``adata`` is touched.  -> whether
+    the call is sequential (``max_boot`` given)."""
+    if max_boot is None:
+        return False
+
+    def is_int(x):
+        return isinstance(x, (int, np.integer)) and not isinstance(x, (bool, np.bool_))
+
+    if rng != 'fast':
+        raise ValueError("max_boot needs rng='fast': only its replicates own a stream each, so that a later round continues a chain")
+    if approx:
+        raise ValueError("max_boot needs approx=False: the sequential bootstrap reports empirical p-values")
+    if ci is not None:
+        raise ValueError("max_boot needs ci=None: no round holds all replicates of a test")
+    if not is_int(num_boot) or not is_int(max_boot) or max_boot < num_boot:
+        raise ValueError(f"max_boot must be an integer >= num_boot ({num_boot!r}), not {max_boot!r}")
+    if max_boot > 2 ** 31 - 1:
+        raise ValueError("max_boot must be at most 2^31 - 1")
+    if not is_int(min_extreme) or min_extreme < 0:
+        raise ValueError(f"min_extreme must be an integer >= 0, not {min_extreme!r}")
+    return True
+
+
+def sequential_schedule(num_boot, max_boot):
+    """Cumulative replicate totals of the rounds: n_0 = num_boot, n_j = min(2 n_(j-1), max_boot); round j >= 1 covers the global
+    replicates [n_(j-1), n_j).  A function of these two numbers alone -- never of memory or chunking."""
+    num_boot, max_boot = int(num_boot), int(max_boot)
+    if num_boot < 1 or max_boot < num_boot:
+        raise ValueError("sequential_schedule: need 1 <= num_boot <= max_boot")
+    totals = [num_boot]
+    while totals[-1] < max_boot:
+        totals.append(min(2 * totals[-1], max_boot))
+    return totals
+
+
+def round_fill_seed(fill_seed, j):
+    """Refill seed of round j: ``fill_seed`` itself for round 0 (today's call), a splitmix of (fill_seed, j) for j >= 1."""
+    return int(fill_seed) & _M64 if j == 0 else _mix64((int(fill_seed) & _M64) ^ _mix64(int(j)))
+
+
+def merge_records(rounds):
+    """The test records [n_tests][8] of several rounds of one chain of replicates, folded into the record of all of them (THE
+    TEST RECORD of csrc/contract.hip): coef0 from round 0; n_valid, n_extreme, n_raw_extreme summed -- the null is centred on the
+    observed coefficient, not on the replicates' mean, so the counts add; with n_j = n_valid and mean_j = mean - coef0 of round j,
+    N = sum n_j, mean = sum n_j mean_j / N and se = sqrt(sum n_j (se_j^2 + (mean_j - mean)^2) / N); all_equal only if every round
+    with replicates says so; range is NaN (not mergeable, not read after round 0).  A round with n_j = 0 contributes nothing."""
+    rounds = [np.asarray(r, dtype=np.float64).reshape(-1, 8) for r in rounds]
+    first = rounds[0]
+    if len(rounds) == 1:
+        return first.copy()
+    out = first.copy()
+    n = np.stack([r[:, 2] for r in rounds])                    # [round][test]
+    has = n > 0
+    N = n.sum(axis=0)
+    for k in (3, 6):
+        out[:, k] = np.stack([r[:, k] for r in rounds]).sum(axis=0)
+    out[:, 2] = N
+    mean_j = np.where(has, np.stack([r[:, 4] for r in rounds]), 0.0)
+    se_j = np.where(has, np.stack([r[:, 1] for r in rounds]), 0.0)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        mean = (n * mean_j).sum(axis=0) / N
+        se = np.sqrt((n * (se_j ** 2 + (mean_j - mean) ** 2)).sum(axis=0) / N)
+    out[:, 4] = np.where(N > 0, mean, np.nan)
+    out[:, 1] = np.where(N > 0, se, np.nan)
+    alleq = np.stack([r[:, 5] for r in rounds]) != 0
+    out[:, 5] = np.where(N > 0, (alleq | ~has).all(axis=0), first[:, 5] != 0).astype(np.float64)
+    out[:, 7] = np.nan
+    return out
+
+
+def open_tests(merged, min_extreme=10, resampling='bootstrap'):
+    """Which tests [n_tests] go on to the next round: the record is testable (coef0 finite, n_valid > 0, not all_equal) and its
+    extreme count -- [3] for 'bootstrap', the un-centred [6] otherwise -- is still <= ``min_extreme``.  The default 10 is the
+    reference's own threshold for trusting the empirical p-value (hypothesis_test.py:90)."""
+    st = np.asarray(merged, dtype=np.float64).reshape(-1, 8)
+    c = st[:, 3] if resampling == 'bootstrap' else st[:, 6]
+    return np.isfinite(st[:, 0]) & (st[:, 2] > 0) & (st[:, 5] == 0) & (c <= min_extreme)
+
+
+def sequential_pvalues(merged, resampling='bootstrap'):
+    """(c + 1) / (n + 1) of every testable record, c and n the merged extreme and valid counts; NaN elsewhere.  No tail fit."""
+    st = np.asarray(merged, dtype=np.float64).reshape(-1, 8)
+    c = st[:, 3] if resampling == 'bootstrap' else st[:, 6]
+    live = np.isfinite(st[:, 0]) & (st[:, 2] > 0) & (st[:, 5] == 0)
+    return np.where(live, (c + 1) / (st[:, 2] + 1), np.nan)
+
+
+def _design_chains(test_gene, test_design, design_ptr, design_grp, ng):
+    """The distinct chains (gene slot * ng + group) that the designs of the given tests read."""
+    lo, cnt = design_ptr[test_design].astype(np.int64), np.diff(design_ptr)[test_design].astype(np.int64)
+    first = np.cumsum(cnt) - cnt
+    pos = np.repeat(lo - first, cnt) + np.arange(int(cnt.sum()))
+    return np.unique(np.repeat(np.asarray(test_gene, dtype=np.int64), cnt) * ng + design_grp[pos])
+
+
+def continue_chunk_1d(c, mv, test_gene, test_design, tables, stats, schedule, min_extreme, resampling, fill_seed, keys, n_open):
+    """Rounds 1.. of the sequential bootstrap on an open chunk whose round 0 (``run_chunk_1d`` with rng='fast', then the
+    contraction) gave the records ``stats`` = (st_m, st_v) of the tests (``test_gene`` [test] gene slot, ``test_design`` [test]
+    into ``tables`` = (design_ptr, design_grp, design_w)).  A test is continued while it is open on either plane
+    (``open_tests``).  Round j bootstraps the global replicates [schedule[j - 1], schedule[j]) of the chains that an open test's
+    design reads -- every other slot of the chunk's tile layout is skipped -- into gene-granular planes
+    [open genes x groups][1 + rep_n] (column 0 copied from the chunk, the other chains' rows NaN), refills invalid replicates from
+    the round's own valid ones under ``round_fill_seed`` and the chains' keys ``keys`` [pair], contracts the open tests only and
+    folds their records (``merge_records``).  The round's planes are allocated once per round, released before the next, and
+    never hold more bytes than the chunk's: a round with more rows takes its open genes in sub-batches (genes are independent).
+    ``n_open`` [round]: the tests open after round j are added to entry j.  -> the merged (st_m, st_v)."""
+    bs, ng, torch = c.bs, mv.ng, engine._torch()
+    design_ptr, design_grp, design_w = (np.asarray(a) for a in tables)
+    test_gene, test_design = np.asarray(test_gene, dtype=np.int64), np.asarray(test_design, dtype=np.int64)
+    merged = [np.array(s, dtype=np.float64) for s in stats]
+    grp = np.arange(ng)
+    for j in range(1, len(schedule)):
+        is_open = open_tests(merged[0], min_extreme, resampling) | open_tests(merged[1], min_extreme, resampling)
+        n_open[j - 1] += int(is_open.sum())
+        if not is_open.any():
+            break
+        idx = np.flatnonzero(is_open)
+        rep_lo, rep_n = schedule[j - 1], schedule[j] - schedule[j - 1]
+        genes = np.unique(test_gene[idx])
+        per = int(min(len(genes), max(1, (bs.n_pairs * bs.ld) // (ng * (1 + rep_n)))))
+        pm = engine.empty((per * ng, 1 + rep_n), torch.float64)
+        pv = engine.empty((per * ng, 1 + rep_n), torch.float64)
+        new = [np.empty((len(idx), 8)) for _ in merged]
+        for lo in range(0, len(genes), per):
+            gsub = genes[lo:lo + per]
+            n_rows = len(gsub) * ng
+            planes = [pm[:n_rows], pv[:n_rows]]
+            in_sub = np.isin(test_gene[idx], gsub)
+            t_gene, t_design = test_gene[idx[in_sub]], test_design[idx[in_sub]]
+            chains = _design_chains(t_gene, t_design, design_ptr, design_grp, ng)
+            rows_old = (gsub[:, None] * ng + grp).reshape(-1)
+            d_rows = engine.dev(rows_old)
+            for p, y in zip(planes, (bs.ym, bs.yv)):
+                p.fill_(float("nan"))
+                p[:, 0] = y[d_rows, 0]
+            bs.run_range(rep_lo, rep_n, chains, planes, np.searchsorted(gsub, chains // ng) * ng + chains % ng, mv.fit,
+                         round_fill_seed(fill_seed, j), keys[rows_old], mean_only=mv.mean_only)
+            recs, _ = engine._contrast_design(planes, 1 + rep_n, rep_n, ng, len(gsub), np.searchsorted(gsub, t_gene), t_design, design_ptr,
+                                              design_grp, design_w)
+            for k, r in enumerate(recs):
+                new[k][in_sub] = r
+        del pm, pv, planes, p      # release-before-allocate: the next round's planes take these buffers
+        for k in range(len(merged)):
+            merged[k][idx] = merge_records([merged[k][idx], new[k]])
+    else:
+        n_open[len(schedule) - 1] += int((open_tests(merged[0], min_extreme, resampling) | open_tests(merged[1], min_extreme, resampling)).sum())
+    return merged
+
+
 def gene_columns(treatment, treatment_for_gene, names):
     """Treatment columns of every gene, looked up once per call: a tuple of column positions, or None = all columns."""
     if treatment_for_gene is None:

@@ -579,7 +579,7 @@ def _vs_control_plan(m, control, treatment_col):
 
 
 def ht_1d_vs_control(adata, control, num_boot=10000, num_cpus=1, rng='replay', fill_seed=0, max_rows=None, approx=False,
-                     resampling='bootstrap', *, treatment_col=None, ci=None):
+                     resampling='bootstrap', *, treatment_col=None, ci=None, max_boot=None, min_extreme=10):
     """Perturb-seq style batch test: every group against one shared ``control`` group (a label of
     ``adata.uns['memento']['groups']`` or its index), for all kept genes, in one call.
 
@@ -607,9 +607,27 @@ def ht_1d_vs_control(adata, control, num_boot=10000, num_cpus=1, rng='replay', f
     are produced for a slice of tests at a time into one bounded scratch tensor (``_ht.sliced_intervals``), which changes no
     number.  Adds the columns ``de_ci_lo, de_ci_hi, dv_ci_lo, dv_ci_hi`` and ``mean_ci`` / ``var_ci`` [test][2] and ``ci`` to ``uns``.
 
+    ``max_boot`` (needs ``rng='fast'``, ``approx=False``, ``ci=None``; an integer >= ``num_boot``): the sequential bootstrap
+    (Besag & Clifford 1991).  Every test gets ``num_boot`` replicates -- round 0, which is today's call: the same launches, keys
+    and records -- and only the tests that are still open are continued, to the cumulative totals ``num_boot``, ``2 num_boot``,
+    ``4 num_boot``, ..., ``max_boot`` (``_ht.sequential_schedule``).  A test is open while its record is testable and its extreme
+    count is still <= ``min_extreme`` on the mean or the variability plane (default 10, the reference's own threshold for
+    trusting the empirical p-value, hypothesis_test.py:90).  Under ``rng='fast'`` replicate r of a chain owns the stream of (``fill_seed``,
+    chain key, r), so the replicates a later round adds are bit for bit those a one-shot call with more replicates makes; a round
+    bootstraps only the chains that an open test's design reads and contracts only the open tests.  The p-value of every test is
+    ``(c + 1) / (n + 1)`` with c, n the extreme and valid counts over all its rounds, and NO tail fit is made: a test that closed in
+    round 0 with c > ``min_extreme`` reports exactly what the plain call reports, and a test that reaches ``max_boot`` with
+    c <= ``min_extreme`` reports the reference's upper-bound form of the empirical p-value (its fallback where the tail fit fails).
+    ``de_se`` / ``dv_se`` come from the merged record (``_ht.merge_records``).  Invalid replicates of a round are refilled from
+    that round's valid ones, under a refill seed derived from (``fill_seed``, round): uniform over valid replicates like the
+    one-shot refill and statistically equivalent to it, but not the same draws -- the two agree exactly wherever nothing was
+    refilled.  Neither the chunking nor the sub-batching of a round changes a number.  Adds the columns ``de_nboot`` / ``dv_nboot``
+    (the valid replicates behind each p-value) and ``mean_nboot``, ``var_nboot``, ``max_boot``, ``min_extreme`` to ``uns``.
+
     Returns a DataFrame (gene, group, de_coef, de_se, de_pval, dv_coef, dv_se, dv_pval) and stores the arrays in
     ``uns['memento']['1d_ht_vs_control']``."""
     _ht.check_args(rng, resampling=resampling)
+    sequential = _ht.check_sequential(max_boot, min_extreme, num_boot, rng, approx, ci)
     probs = _ht.ci_probs(ci)
     m = adata.uns['memento']
     st = m['_hip']
@@ -625,18 +643,35 @@ def ht_1d_vs_control(adata, control, num_boot=10000, num_cpus=1, rng='replay', f
     cols = {k: [] for k in ('mean_coef', 'mean_se', 'mean_asl', 'var_coef', 'var_se', 'var_asl')}
     if probs is not None:
         cols.update(mean_ci=[], var_ci=[])
+    if sequential:
+        cols.update(mean_nboot=[], var_nboot=[])
+        schedule = _ht.sequential_schedule(num_boot, max_boot)
+        st.last_sequential = SimpleNamespace(schedule=schedule, n_open=[0] * len(schedule))   # (diagnostics: tests open after each round)
+        two_group = _ht._TwoGroupDesigns(ng, ctrl) if designs is None else None
     st.last_bootstrap = st.last_good = None    # (see ht_1d_moments: free the previous call's replicate rows first)
 
     def run_chunk(c):
         G, bs = c.G, c.bs
         keys = np.arange(c.g0 * ng, c.g1 * ng, dtype=np.int64)  # (g0 + gene) * ng + group: the chain's row in the one-chunk call
-        good, _ = _ht.run_chunk_1d(c, mv, rng, fill_seed, keys, keys)
-        st.last_good = good                    # (diagnostics / tests: the good groups of the last gene chunk)
+        good, st.last_n_inv = _ht.run_chunk_1d(c, mv, rng, fill_seed, keys, keys)
+        st.last_good = good                    # (diagnostics / tests: the good groups and the refilled replicates of the last gene chunk)
         test_gene = np.repeat(np.arange(G), len(tested))
+        test_design = None if designs is None else designs.tests(good)
         st_m, st_v, rows = (bs.contrast(test_gene, np.tile(others, G), ctrl, good) if designs is None
-                            else bs.contrast_design(test_gene, designs.tests(good), *designs.tables()))
+                            else bs.contrast_design(test_gene, test_design, *designs.tables()))
+        if sequential:
+            if designs is None:      # (the designs ``bs.contrast`` builds are those of _TwoGroupDesigns)
+                test_design = two_group.tests(good)
+            tables = (two_group if designs is None else designs).tables()
+            st_m, st_v = _ht.continue_chunk_1d(c, mv, test_gene, test_design, tables, (st_m, st_v), schedule, min_extreme, resampling,
+                                               fill_seed, keys, st.last_sequential.n_open)
+        st.last_records = (st_m, st_v)         # (diagnostics / tests: the test records of the last gene chunk)
         for tag, stt, which in (('mean', st_m, 0), ('var', st_v, 1)):
-            p = _asl.asl_from_stats(stt, approx, lambda idx, w=which: rows(w, idx), num_cpus, resampling)
+            if sequential:
+                p = _ht.sequential_pvalues(stt, resampling)
+                cols[tag + '_nboot'].append(stt[:, 2].astype(np.int64))
+            else:
+                p = _asl.asl_from_stats(stt, approx, lambda idx, w=which: rows(w, idx), num_cpus, resampling)
             cols[tag + '_coef'].append(stt[:, 0])
             cols[tag + '_se'].append(stt[:, 1])
             cols[tag + '_asl'].append(p)
@@ -653,6 +688,9 @@ def ht_1d_vs_control(adata, control, num_boot=10000, num_cpus=1, rng='replay', f
     if probs is not None:
         m['1d_ht_vs_control']['ci'] = float(ci)
         _ci_columns(df, ('de', out['mean_ci']), ('dv', out['var_ci']))
+    if sequential:
+        m['1d_ht_vs_control'].update(max_boot=int(max_boot), min_extreme=int(min_extreme))
+        df['de_nboot'], df['dv_nboot'] = out['mean_nboot'], out['var_nboot']
     return df
 
 
