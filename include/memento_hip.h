@@ -200,6 +200,14 @@ int mm_debug_wave_clock(int64_t *d_buf);
  * arithmetic; 0 (default) uses the guarded fp32 evaluation of those loops (csrc/npy_rng.h: same integer draws, the guard sends
  * the ~0.1-0.5 % of draws that land near a decision threshold to the fp64 arithmetic).  Process-wide switch. */
 int mm_debug_replay_arith(int32_t exact);
+/* Test aid: the guarded fp32 inversion search (csrc/npy_rng.h, binomial_inversion_fast) of thread i's (d_U[i], d_n[i], d_p[i]) through
+ * both forms of its ladder: form 0 the nested ifs, form 1 the device's one-saved-mask asm statement.  Needs n >= 1, 0 < p <= 0.5 and
+ * n p <= 30, as the samplers call it.  ``count`` threads are launched (one workgroup of exactly ``count`` threads up to 256); within a
+ * wave only the lanes whose bit is set in lane_mask run the searches.  d_out[(form * 4 + f) * count + i], f = 0..3: the return value
+ * (X, or -1 when a decision fell inside the guard or the search ran past its cap), the steps taken, the bits of Uf and of px where the
+ * search stopped; cells of masked lanes are left as they were.  d_marker[i] = i + 1 from every thread, behind the searches. */
+int mm_debug_inversion_ladder(const double *d_U, const int32_t *d_n, const double *d_p, int64_t count, uint64_t lane_mask, int32_t *d_out,
+                              int32_t *d_marker, void *stream);
 
 /* ---- K6+K7: replay bootstrap -- numpy Generator(PCG64).multinomial draw-for-draw + replicate moments
  * replaces bootstrap._bootstrap_1d  memento/bootstrap.py:97-110 and the tuple branch of

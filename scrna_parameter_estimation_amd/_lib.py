@@ -72,6 +72,7 @@ _SIGS = {
                         c_int32, c_void_p], ctypes.c_int),
     "mm_debug_wave_clock": ([c_void_p], ctypes.c_int),
     "mm_debug_replay_arith": ([c_int32], ctypes.c_int),
+    "mm_debug_inversion_ladder": ([c_void_p, c_void_p, c_void_p, c_int64, c_uint64, c_void_p, c_void_p, c_void_p], ctypes.c_int),
     "mm_boot1d_fast": ([c_void_p] * 6 + [c_int64] + [c_void_p] * 5 + [c_uint64, c_int32, c_int32, c_int64, c_void_p, c_void_p, c_void_p,
                                                                       c_int32, c_void_p], ctypes.c_int),
     "mm_boot1d_fast_range": ([c_void_p] * 6 + [c_int64] + [c_void_p] * 5 + [c_uint64, c_int32, c_int32, c_int32, c_int64, c_void_p, c_void_p,

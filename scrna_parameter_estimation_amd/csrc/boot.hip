@@ -949,6 +949,35 @@ __global__ __launch_bounds__(256) void k_boot2d_fast(const double *__restrict__ 
   if (mine) out_corr[row * ld + 1 + r] = close_replicate_2d(sums, nobs);
 }
 
+// mm_debug_inversion_ladder: the guarded fp32 inversion search of thread i's (U, n, p) through both forms of its ladder -- form 0 the
+// nested ifs, form 1 the one-mask asm statement (csrc/npy_rng.h) -- inside a branch that only the lanes of ``lane_mask`` take, so the
+// asm statement is entered with partial EXEC.  out[(form * 4 + f) * count + i], f = 0..3: the return value (X or -1), the steps
+// taken, the bits of Uf and of px where the search stopped.  They are stored behind the call, inside the branch: a lane the
+// statement failed to switch back on would leave its cells untouched.  marker[i] = i + 1 from every thread, masked or not.
+__global__ __launch_bounds__(256) void k_debug_inversion_ladder(const double *__restrict__ U, const int32_t *__restrict__ n,
+                                                                const double *__restrict__ p, int64_t count, uint64_t lane_mask,
+                                                                int32_t *__restrict__ out, int32_t *__restrict__ marker) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= count) return;
+  if ((lane_mask >> (threadIdx.x & 63)) & 1) {
+    const double Ui = U[i], pi = p[i];
+    const int32_t ni = n[i];
+    const double lq = npyrng::binomial_lq(pi);
+    npyrng::InversionStop st;
+    int32_t ret = npyrng::binomial_inversion_fast<int32_t, true, true>(Ui, ni, pi, lq, &st);
+    out[0 * count + i] = ret;
+    out[1 * count + i] = st.steps;
+    out[2 * count + i] = (int32_t)__float_as_uint(st.Uf);
+    out[3 * count + i] = (int32_t)__float_as_uint(st.px);
+    ret = npyrng::binomial_inversion_fast<int32_t, false, true>(Ui, ni, pi, lq, &st);
+    out[4 * count + i] = ret;
+    out[5 * count + i] = st.steps;
+    out[6 * count + i] = (int32_t)__float_as_uint(st.Uf);
+    out[7 * count + i] = (int32_t)__float_as_uint(st.px);
+  }
+  marker[i] = (int32_t)(i + 1);
+}
+
 static int64_t *g_wave_clock = nullptr;  // set by mm_debug_wave_clock; nullptr = no profiling writes
 static int g_exact_arith = 0;            // set by mm_debug_replay_arith: 1 = numpy's fp64 arithmetic in every search loop (A/B timing, tests)
 
@@ -991,6 +1020,18 @@ int mm_debug_wave_clock(int64_t *d_buf) {
 
 int mm_debug_replay_arith(int32_t exact) {
   g_exact_arith = exact ? 1 : 0;
+  return MM_OK;
+}
+
+int mm_debug_inversion_ladder(const double *d_U, const int32_t *d_n, const double *d_p, int64_t count, uint64_t lane_mask, int32_t *d_out,
+                              int32_t *d_marker, void *stream) {
+  MM_ARG(d_U && d_n && d_p && d_out && d_marker && count >= 0 && count < (1LL << 28));
+  if (count == 0) return MM_OK;
+  // exactly ``count`` threads while they fit one workgroup (a launch of 65 threads has a one-lane wave), 256-thread workgroups beyond
+  const unsigned threads = count < 256 ? (unsigned)count : 256u;
+  hipLaunchKernelGGL(k_debug_inversion_ladder, dim3((unsigned)((count + threads - 1) / threads)), dim3(threads), 0, (hipStream_t)stream,
+                     d_U, d_n, d_p, count, lane_mask, d_out, d_marker);
+  MM_LAUNCH_CHECK();
   return MM_OK;
 }
 

@@ -335,8 +335,95 @@ NPY_HD int32_t inversion_steps(float &Uf, float &px, const float a_s, const floa
   return IT - 1;
 }
 
-template <typename Int>
-NPY_HD int32_t binomial_inversion_fast(double U, Int n, double p, double lq) {
+// ---- the ladder with one saved EXEC mask (device code) --------------------------------------------------------------------
+// inversion_steps above is the statement of what the search computes.  As nested ifs it makes the compiler keep one saved EXEC mask
+// per nesting level: per level an s_and_saveexec with its literal and branch on the way in and an s_or exec on the way out, and
+// from about level 27 on the masks no longer fit the SGPRs and travel through v_writelane / v_readlane.  None of those masks is
+// needed: a lane that stops never resumes.  The device form below is ONE asm statement per segment: it saves EXEC once, every step's
+// compare (v_cmpx) narrows EXEC in place, the wave leaves through s_cbranch_execz as soon as no lane is left, and the single exit
+// restores EXEC.  Same fp32 operations in the same order per lane: the factor a_s * (1/IT) - s as one fused multiply-add (v_fmamk,
+// 1/IT a literal, -s an operand), Uf -= px, px *= factor; a stopped lane keeps the Uf, px and X it stopped with (they are read-write
+// operands and the lane is masked off).
+// Hazards (the assembler adds no wait states): v_cmpx writes EXEC and VCC.  The next instruction is s_cbranch_execz, which the
+// hardware interlocks, and the VALU instructions of a step neither are DPP nor read EXECZ / VCCZ as data, the two uses that need
+// five wait states after a VALU write of EXEC.  The compiler cannot see the v_cmpx when it schedules what follows the statement, so
+// the exit pads the taken branch (s_cbranch_execz, s_mov_b64) with s_nop 2 to five wait states.  The statement opens with the SALU
+// save of EXEC, so a px that comes straight from v_exp_f32 has its wait state before the first compare reads it.
+// NPY_INV_RCP_*: the correctly rounded fp32 values of 1.0f / (float)IT, the literals the compiler folds in inversion_steps.
+#define NPY_INV_RCP_1_9(X) \
+  X(1, 0x3f800000) X(2, 0x3f000000) X(3, 0x3eaaaaab) X(4, 0x3e800000) X(5, 0x3e4ccccd) X(6, 0x3e2aaaab) X(7, 0x3e124925) \
+  X(8, 0x3e000000) X(9, 0x3de38e39)
+#define NPY_INV_RCP_10_60(X) \
+  X(10, 0x3dcccccd) X(11, 0x3dba2e8c) X(12, 0x3daaaaab) X(13, 0x3d9d89d9) X(14, 0x3d924925) X(15, 0x3d888889) X(16, 0x3d800000) \
+  X(17, 0x3d70f0f1) X(18, 0x3d638e39) X(19, 0x3d579436) X(20, 0x3d4ccccd) X(21, 0x3d430c31) X(22, 0x3d3a2e8c) X(23, 0x3d321643) \
+  X(24, 0x3d2aaaab) X(25, 0x3d23d70a) X(26, 0x3d1d89d9) X(27, 0x3d17b426) X(28, 0x3d124925) X(29, 0x3d0d3dcb) X(30, 0x3d088889) \
+  X(31, 0x3d042108) X(32, 0x3d000000) X(33, 0x3cf83e10) X(34, 0x3cf0f0f1) X(35, 0x3cea0ea1) X(36, 0x3ce38e39) X(37, 0x3cdd67c9) \
+  X(38, 0x3cd79436) X(39, 0x3cd20d21) X(40, 0x3ccccccd) X(41, 0x3cc7ce0c) X(42, 0x3cc30c31) X(43, 0x3cbe82fa) X(44, 0x3cba2e8c) \
+  X(45, 0x3cb60b61) X(46, 0x3cb21643) X(47, 0x3cae4c41) X(48, 0x3caaaaab) X(49, 0x3ca72f05) X(50, 0x3ca3d70a) X(51, 0x3ca0a0a1) \
+  X(52, 0x3c9d89d9) X(53, 0x3c9a90e8) X(54, 0x3c97b426) X(55, 0x3c94f209) X(56, 0x3c924925) X(57, 0x3c8fb824) X(58, 0x3c8d3dcb) \
+  X(59, 0x3c8ad8f3) X(60, 0x3c888889)
+#if defined(__clang__) || (defined(__GNUC__) && __GNUC__ >= 11)
+#define NPY_INV_RCP_CHECK(IT, HEX) static_assert(__builtin_bit_cast(uint32_t, 1.0f / (float)IT) == HEX##u, "reciprocal literal of step " #IT);
+NPY_INV_RCP_1_9(NPY_INV_RCP_CHECK)
+NPY_INV_RCP_10_60(NPY_INV_RCP_CHECK)
+#undef NPY_INV_RCP_CHECK
+#endif
+
+// -DNPY_INV_LADDER_CXX (build.py: MM_EXTRA_DEFS): the nested-if ladder in every kernel, for A/B builds.  The host always has it.
+#if defined(NPY_INV_LADDER_CXX)
+#define NPY_INV_LADDER_CXX_DEFAULT true
+#else
+#define NPY_INV_LADDER_CXX_DEFAULT false
+#endif
+
+#if defined(__HIP_DEVICE_COMPILE__)
+// one step: compare (lanes with Uf <= px stop here), leave when no lane is left, then the step for the lanes that go on.  (Testing
+// for "no lane left" only every second or fourth step measured slower, profiles/inversion_ladder.txt: most waves leave early.)
+#define NPY_INV_ASM_STEP(IT, HEX)               \
+  "v_cmpx_gt_f32_e32 %[U], %[px]\n\t"           \
+  "s_cbranch_execz .Lnpy_inv_out_%=\n\t"        \
+  "v_fmamk_f32 %[f], %[as], " #HEX ", %[ns]\n\t" \
+  "v_sub_f32_e32 %[U], %[U], %[px]\n\t"         \
+  "v_mul_f32_e32 %[px], %[px], %[f]\n\t"        \
+  "v_mov_b32_e32 %[X], " #IT "\n\t"
+#define NPY_INV_ASM_LADDER(STEPS)                                                                                       \
+  asm volatile("s_mov_b64 %[save], exec\n\t" STEPS(NPY_INV_ASM_STEP) ".Lnpy_inv_out_%=:\n\t"                            \
+               "s_mov_b64 exec, %[save]\n\t"                                                                            \
+               "s_nop 2"                                                                                                \
+               : [U] "+v"(Uf), [px] "+v"(px), [X] "+v"(X), [f] "=&v"(f), [save] "=&s"(save)                             \
+               : [as] "v"(a_s), [ns] "v"(ns)                                                                            \
+               : "vcc")
+// Steps 1..9 (FIRST = 1) or 10..60 (FIRST = 10) for the lanes that enter; X comes in as the steps taken so far (FIRST - 1) and
+// goes out as the steps taken, as inversion_steps<FIRST, .> returns it.
+template <int FIRST>
+__device__ __forceinline__ void inversion_steps_exec(float &Uf, float &px, int32_t &X, const float a_s, const float s) {
+  static_assert(FIRST == 1 || FIRST == 10, "the two segments of binomial_inversion_fast");
+  const float ns = -s;
+  float f;
+  uint64_t save;
+  if constexpr (FIRST == 1) NPY_INV_ASM_LADDER(NPY_INV_RCP_1_9);
+  else NPY_INV_ASM_LADDER(NPY_INV_RCP_10_60);
+}
+#else
+// the host has no EXEC mask to save: the same steps as the nested ifs
+template <int FIRST>
+NPY_HD void inversion_steps_exec(float &Uf, float &px, int32_t &X, const float a_s, const float s) {
+  X = inversion_steps<FIRST, FIRST == 1 ? 9 : 60>(Uf, px, a_s, s);
+}
+#endif
+
+// Where a search stopped, whatever the guard says of it: the steps taken and the values it stopped with (mm_debug_inversion_ladder,
+// csrc/boot.hip, reports them).
+struct InversionStop {
+  int32_t steps;
+  float Uf, px;
+};
+
+// CXX = true keeps the nested-if ladder: the one-wave-per-chain body (LAZY) asks for it, whose search already runs on scalar branches
+// with no mask nesting and whose values must stay wave-uniform in the compiler's eyes (an asm result is lane-dependent to it).
+// REPORT: fill ``stop`` in.
+template <typename Int, bool CXX = NPY_INV_LADDER_CXX_DEFAULT, bool REPORT = false>
+NPY_HD int32_t binomial_inversion_fast(double U, Int n, double p, double lq, InversionStop *stop = nullptr) {
   float nf = (float)n, pf = (float)p;
   float qf = 1.0f - pf;                       // p <= 0.5
   float s = pf * f_rcp(qf);
@@ -356,17 +443,20 @@ NPY_HD int32_t binomial_inversion_fast(double U, Int n, double p, double lq) {
   // then negative, px stays (-)0 and the search runs on to its last step, where X > cap sends the draw to the exact path; it takes a U
   // above the whole fp32 CDF to get there (~1e-6 of the draws with n < 60, none otherwise).
   int32_t cap_end = n < (Int)9 ? (int32_t)n : 9;
-  X = inversion_steps<1, 9>(Uf, px, a_s, s);
+  if constexpr (CXX) X = inversion_steps<1, 9>(Uf, px, a_s, s);
+  else inversion_steps_exec<1>(Uf, px, X, a_s, s);
   if (X == 9 && Uf > px) {
     float npf = nf * pf;
     float capf = npf + 10.0f * f_sqrt(npf * qf + 1.0f) - 1.5f;
     capf = capf < nf ? capf : nf;
     capf = capf < 60.0f ? capf : 60.0f;
     cap_end = (int32_t)capf;
-    X = inversion_steps<10, 60>(Uf, px, a_s, s);
+    if constexpr (CXX) X = inversion_steps<10, 60>(Uf, px, a_s, s);
+    else inversion_steps_exec<10>(Uf, px, X, a_s, s);
   }
   const float G = (NPY_INV_G0 + (n < (Int)128 ? NPY_INV_GS : 0.0f)) + NPY_INV_GA * fabsf(argf) + NPY_INV_GX * (float)X;
   bool ok = (px - Uf > G) && (X == 0 || Uf > G) && X <= cap_end;
+  if constexpr (REPORT) *stop = InversionStop{X, Uf, px};
   return ok ? X : -1;
 }
 
@@ -1065,7 +1155,7 @@ NPY_HD Int binomial_pre(Gen &g, double pk, double lq, Int n) {
   Int X;
   if (p * (double)n <= 30.0) {
     double U = pcg64_next_double(g);
-    int32_t xf = FAST ? binomial_inversion_fast<Int>(U, n, p, lq) : -1;
+    int32_t xf = FAST ? binomial_inversion_fast<Int, LAZY || NPY_INV_LADDER_CXX_DEFAULT>(U, n, p, lq) : -1;
     if (FAST && xf < 0) NPY_NOTE_FALLBACK(0);
     X = xf >= 0 ? (Int)xf : binomial_inversion_pre<Int>(g, n, p, lq, U);
   } else {
