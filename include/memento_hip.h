@@ -97,7 +97,10 @@ int mm_csr_colsum(const int32_t *d_indices, const float *d_data, int64_t nnz, do
  * mm_moments1d_sell / _reduce write that range's slice of the per-gene outputs; mm_hist1d_sell and mm_extract_cols take that
  * range's slice of d_gene_pairbase / d_col_id and write into the ONE set of tables / columns, which are indexed by pair / column
  * slot, not by gene.  mm_csr_colsplit drops entries whose column lies in no range: compare the ranges' entry counts with
- * d_indptr to keep the column-index validation.  */
+ * d_indptr to keep the column-index validation.
+ * A CSR without a stored entry (a column range that no selected cell touches, an empty matrix) is a valid input: all-zero
+ * d_blk_cnt, no rows, zero moments.  d_indices / d_data must still be non-NULL and hold one readable element -- every entry point
+ * refuses NULL, and mm_sell_scatter_ranges reads element 0 on behalf of a tile without entries (engine.DeviceCSR.entry_ptrs).  */
 int mm_sell_count(const int64_t *d_indptr, const int32_t *d_indices, const float *d_data, const int32_t *d_cell_order,
                   const int32_t *d_blk_cell0, int32_t n_blocks, int32_t n_genes, uint16_t *d_blk_cnt /* [nb][G] */,
                   int32_t *d_status, void *stream);

@@ -145,6 +145,19 @@ class DeviceCSR:
     def nbytes(self):
         return self.indptr.numel() * 8 + self.indices.numel() * 4 + self.data.numel() * 4
 
+    _spare = None
+
+    def entry_ptrs(self):
+        """Device pointers of (indices, data) for the C-ABI.  A tensor without elements has a null pointer, which every entry point
+        refuses, and the tile scatter reads element 0 on behalf of a tile without entries: a CSR without a stored entry lends a
+        one-element buffer of each instead (as colsplit keeps one behind its outputs)."""
+        if self.nnz:
+            return P(self.indices), P(self.data)
+        if self._spare is None:
+            torch = _torch()
+            self._spare = (zeros((1,), torch.int32), zeros((1,), torch.float32))
+        return P(self._spare[0]), P(self._spare[1])
+
     def colsplit(self, lo, hi):
         """The gene (column) range [lo, hi) as a new device CSR with columns renumbered from 0 -- the device-side replacement
         of the host ``X[:, lo:hi]`` in front of gene-sharded multi-GPU runs (mm_csr_colcount + mm_csr_colsplit)."""
@@ -154,14 +167,14 @@ class DeviceCSR:
             raise ValueError("column range out of bounds")
         n = self.shape[0]
         row_nnz = empty((max(1, n),), torch.int64)
-        _lib.call("mm_csr_colcount", P(self.indptr), P(self.indices), n, lo, hi, P(row_nnz), _stream())
+        _lib.call("mm_csr_colcount", P(self.indptr), self.entry_ptrs()[0], n, lo, hi, P(row_nnz), _stream())
         indptr = zeros((n + 1,), torch.int64)
         if n:
             indptr[1:] = torch.cumsum(row_nnz[:n], 0)
         nnz = int(indptr[-1].item())
         indices = empty((max(1, nnz),), torch.int32)
         data = empty((max(1, nnz),), torch.float32)
-        _lib.call("mm_csr_colsplit", P(self.indptr), P(self.indices), P(self.data), n, lo, hi, P(indptr), P(indices), P(data), _stream())
+        _lib.call("mm_csr_colsplit", P(self.indptr), *self.entry_ptrs(), n, lo, hi, P(indptr), P(indices), P(data), _stream())
         return DeviceCSR.from_device(indptr, indices[:nnz], data[:nnz], (n, hi - lo))
 
     def colselect(self, genes):
@@ -178,21 +191,21 @@ class DeviceCSR:
         col_map[genes] = np.arange(len(genes), dtype=np.int32)
         d_map = dev(col_map)
         row_nnz = empty((max(1, n),), torch.int64)
-        _lib.call("mm_csr_mapcount", P(self.indptr), P(self.indices), n, P(d_map), P(row_nnz), _stream())
+        _lib.call("mm_csr_mapcount", P(self.indptr), self.entry_ptrs()[0], n, P(d_map), P(row_nnz), _stream())
         indptr = zeros((n + 1,), torch.int64)
         if n:
             indptr[1:] = torch.cumsum(row_nnz[:n], 0)
         nnz = int(indptr[-1].item())
         indices = empty((max(1, nnz),), torch.int32)
         data = empty((max(1, nnz),), torch.float32)
-        _lib.call("mm_csr_mapsplit", P(self.indptr), P(self.indices), P(self.data), n, P(d_map), P(indptr), P(indices), P(data), _stream())
+        _lib.call("mm_csr_mapsplit", P(self.indptr), *self.entry_ptrs(), n, P(d_map), P(indptr), P(indices), P(data), _stream())
         return DeviceCSR.from_device(indptr, indices[:nnz], data[:nnz], (n, len(genes)))
 
     def colsum(self):
         """Per-gene totals (host array): what the cost-balanced gene sharding is computed from."""
         torch = _torch()
         out = zeros((max(1, self.shape[1]),), torch.float64)
-        _lib.call("mm_csr_colsum", P(self.indices), P(self.data), self.nnz, P(out), _stream())
+        _lib.call("mm_csr_colsum", *self.entry_ptrs(), self.nnz, P(out), _stream())
         return host(out)[: self.shape[1]]
 
     def rowsum(self, gene_mask=None):
@@ -200,7 +213,7 @@ class DeviceCSR:
         torch = _torch()
         out = empty((self.shape[0],), torch.float64)
         m = dev(np.asarray(gene_mask, dtype=np.uint8)) if gene_mask is not None else None
-        _lib.call("mm_csr_rowsum", P(self.indptr), P(self.indices), P(self.data), self.shape[0], P(m), P(out), _stream())
+        _lib.call("mm_csr_rowsum", P(self.indptr), *self.entry_ptrs(), self.shape[0], P(m), P(out), _stream())
         return host(out)
 
 
@@ -284,12 +297,12 @@ class CountBlocks:
         n_sel = len(self.cell_order)
         R = -(-G // RANGE_GENES)          # (<= MAX_RANGES: G <= MAX_PART_GENES)
         rowsplit = empty((R + 1, max(1, n_sel)), torch.int64)     # [range][row]
-        call("mm_sell_split_count", P(csr.indptr), P(csr.indices), P(self.d_cell_order), P(self.d_blk_cell0), nb, n_sel, G, R,
+        call("mm_sell_split_count", P(csr.indptr), csr.entry_ptrs()[0], P(self.d_cell_order), P(self.d_blk_cell0), nb, n_sel, G, R,
              P(rowsplit), P(blk_cnt_buf), P(status), s)
         self.ranged = (int(status.item()) & 2) == 0
         if not self.ranged:       # unsorted rows (or column indices out of range: reported by the count kernel): the unpartitioned kernels
             status.zero_()
-            call("mm_sell_count", P(csr.indptr), P(csr.indices), P(csr.data), P(self.d_cell_order), P(self.d_blk_cell0), nb, G,
+            call("mm_sell_count", P(csr.indptr), *csr.entry_ptrs(), P(self.d_cell_order), P(self.d_blk_cell0), nb, G,
                  P(blk_cnt), P(status), s)
             if int(status.item()) != 0:
                 raise bad_data
@@ -312,12 +325,12 @@ class CountBlocks:
         self.blk_item_base = dev(ibase[:-1])
         self.ent = zeros((max(1, self.total_rows) * 256,), torch.int32)
         if self.ranged:
-            call("mm_sell_scatter_ranges", P(csr.indptr), P(csr.indices), P(csr.data), P(self.d_cell_order), P(self.d_blk_cell0), nb, G, R,
+            call("mm_sell_scatter_ranges", P(csr.indptr), *csr.entry_ptrs(), P(self.d_cell_order), P(self.d_blk_cell0), nb, G, R,
                  n_sel, P(rowsplit), P(self.rank), P(self.slice_ptr), P(self.blk_base), P(self.ent), P(status), s)
             if int(status.item()) & 1:
                 raise bad_data
         else:
-            call("mm_sell_scatter", P(csr.indptr), P(csr.indices), P(csr.data), P(self.d_cell_order), P(self.d_blk_cell0), nb, G,
+            call("mm_sell_scatter", P(csr.indptr), *csr.entry_ptrs(), P(self.d_cell_order), P(self.d_blk_cell0), nb, G,
                  P(self.rank), P(self.slice_ptr), P(self.blk_base), P(self.ent), s)
         del rowsplit
         self.blk_cnt = host(blk_cnt, np.uint16)            # nnz per (block, gene), host copy [nb][G]
