@@ -576,6 +576,26 @@ int mm_boot2d_fast(const double *d_pk, const double *d_lq, const double *d_v1, c
                    const double *d_slot_omq, const int64_t *d_slot_row, const int64_t *d_slot_key, uint64_t seed, int32_t num_boot,
                    int64_t ld, double *d_out_corr, int32_t *d_w_dump, int32_t kmax_dump, void *stream);
 
+/* mm_boot2d_fast on a replicate RANGE (sequential bootstrap, ht_2d_moments(rng='fast', max_boot=...)): local replicate i in
+ * [0, rep_n) draws from the stream of global replicate rep_lo + i -- (seed, d_slot_key[s], rep_lo + i) -- and is stored in column
+ * 1 + i of row d_slot_row[s]; ld >= 1 + rep_n; d_w_dump (optional) is [slot][k < kmax_dump][i < rep_n].  mm_boot2d_fast is the
+ * case rep_lo = 0, rep_n = num_boot of the same kernel and the same launch, so replicates [rep_lo, rep_lo + rep_n) made later, for
+ * some of the chains, are bit for bit those of a one-shot launch over [0, rep_lo + rep_n).
+ *   - rep_lo >= 0, rep_n >= 1 and rep_lo + rep_n <= 2^31 - 1; n_slots is a multiple of 64.
+ *   - The streams are those of mm_boot1d_fast_range: no replicate range of one chain collides with a range of another chain.
+ *   - A slot with d_slot_row[s] < 0 (or d_slot_K[s] <= 0) writes nothing: that is how the chains of closed tests are skipped
+ *     without a new tile layout.  K == 1 chains run, as in mm_boot2d_fast: every replicate is the observed sample.
+ *   - Column 0, the columns beyond rep_n and the rows of skipped slots are not written.  The rows are trusted: validate them on
+ *     the host.
+ *   - Grid: one wave per (slot, 64 replicates), four waves per block.  Up to 2^22 blocks they are one row of gridDim.x; beyond,
+ *     rows of 2^22 blocks in gridDim.y (at most 65,535, checked), since a grid dimension holds fewer than 2^32 threads.
+ * The 2D path has no refill stage: an invalid replicate is a NaN column that the contraction drops, so the records of the
+ * rounds (mm_contract_stats on each round's plane) fold into exactly the one-shot call's counts. */
+int mm_boot2d_fast_range(const double *d_pk, const double *d_lq, const double *d_v1, const double *d_v2, const double *d_a,
+                         const double *d_b, const int64_t *d_tile_ptr, int64_t n_slots, const int32_t *d_slot_K, const double *d_slot_nobs,
+                         const double *d_slot_omq, const int64_t *d_slot_row, const int64_t *d_slot_key, uint64_t seed, int32_t rep_lo,
+                         int32_t rep_n, int64_t ld, double *d_out_corr, int32_t *d_w_dump, int32_t kmax_dump, void *stream);
+
 /* ---- synthetic data generator (replaces memento/simulate.py:52-89 and :91-115) ----
  * Counter-based: transcriptome count z[cell][gene] ~ NB(mean[gene], size theta[gene]) is a pure function of (seed_z, cell, gene),
  * so nothing dense is ever stored.  One launch per pass, selected by `mode`:

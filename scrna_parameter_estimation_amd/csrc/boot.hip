@@ -898,25 +898,30 @@ __global__ __launch_bounds__(256, MINW) void k_boot2d_replay(const double *__res
 
 // ------------------------------------------------------------------------------------------------
 // 2D FAST mode (rng='fast'): k_boot1d_fast's decomposition with k_boot2d_replay's arithmetic.  One lane = one REPLICATE, one wave
-// = 64 replicates of ONE (pair, group) chain: wave wid = slot * chunks + chunk draws replicates chunk * 64 + lane.  The address of
-// bin k in the six [row][64] planes is wave-uniform (one broadcast load per operand and step, fetched one bin ahead); the lanes hold
-// different remainders, so they may take different samplers at a step.  A chain's critical path is its K draws instead of K x B, and
-// the launch has chains x ceil(B / 64) independent waves.  Replicate r of the chain with key ``slot_key[slot]`` owns the PCG64 stream
-// derived from (seed, key, r) -- the caller's keys number the (pair, group) chains independently of chunking, of the order the pairs
-// are in and of the tile layout, so neither changes a result.  Chains with K >= 1 run (K == 1: every replicate is the observed
-// sample, as in the replay kernel); K <= 0 or row < 0 writes nothing.  Lanes beyond num_boot walk along and store nothing.
-// w_dump (optional): int32 weights [slot][k < kmax_dump][r < num_boot].
+// = 64 replicates of ONE (pair, group) chain: wave wid = slot * chunks + chunk draws the local replicates chunk * 64 + lane.  The
+// address of bin k in the six [row][64] planes is wave-uniform (one broadcast load per operand and step, fetched one bin ahead); the
+// lanes hold different remainders, so they may take different samplers at a step.  A chain's critical path is its K draws instead of
+// K x B, and the launch has chains x ceil(B / 64) independent waves.  Replicate r of the chain with key ``slot_key[slot]`` owns the
+// PCG64 stream derived from (seed, key, r) -- the caller's keys number the (pair, group) chains independently of chunking, of the
+// order the pairs are in and of the tile layout, so neither changes a result.  The launch covers the ``num_boot`` replicates from
+// global replicate ``rep_lo`` on (mm_boot2d_fast: rep_lo = 0): local replicate i draws from the stream of replicate rep_lo + i and is
+// stored in column 1 + i, so a later launch on [rep_lo, rep_lo + n) continues a chain with the replicates a one-shot run would have
+// made.  Chains with K >= 1 run (K == 1: every replicate is the observed sample, as in the replay kernel); K <= 0 or row < 0 writes
+// nothing.  Lanes beyond num_boot walk along and store nothing.  The grid is one row of blocks up to FAST_GRID_X of them and rows
+// of FAST_GRID_X blocks in gridDim.y beyond (mm_boot2d_fast_range); the waves behind the last slot return at once.
+// w_dump (optional): int32 weights [slot][k < kmax_dump][i < num_boot].
 __global__ __launch_bounds__(256) void k_boot2d_fast(const double *__restrict__ pk_, const double *__restrict__ lq_,
                                                      const double *__restrict__ v1_, const double *__restrict__ v2_,
                                                      const double *__restrict__ a, const double *__restrict__ b,
                                                      const int64_t *__restrict__ tile_ptr, int64_t n_slots,
                                                      const int32_t *__restrict__ slot_K, const double *__restrict__ slot_nobs,
                                                      const double *__restrict__ slot_omq, const int64_t *__restrict__ slot_row,
-                                                     const int64_t *__restrict__ slot_key, uint64_t seed, int32_t num_boot,
-                                                     int32_t chunks, int64_t ld, double *__restrict__ out_corr,
+                                                     const int64_t *__restrict__ slot_key, uint64_t seed, int32_t rep_lo,
+                                                     int32_t num_boot, int32_t chunks, int64_t ld, double *__restrict__ out_corr,
                                                      int32_t *__restrict__ w_dump, int32_t kmax_dump) {
   int lane = mm_lane();
-  int64_t wid = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  // (a grid dimension holds fewer than 2^32 threads: the blocks beyond FAST_GRID_X go to gridDim.y)
+  int64_t wid = (((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * blockDim.x + threadIdx.x) >> 6;
   int64_t slot = wid / chunks;
   int chunk = (int)(wid % chunks);
   if (slot >= n_slots) return;
@@ -927,7 +932,8 @@ __global__ __launch_bounds__(256) void k_boot2d_fast(const double *__restrict__ 
   bool mine = r < num_boot;
   int64_t obase = tile_ptr[slot >> 6] * 64 + (slot & 63);
   double nobs = slot_nobs[slot], omq = slot_omq[slot];
-  npyrng::Pcg64 g = fast_stream(seed, (uint64_t)slot_key[slot], r);
+  // global replicate; unsigned, as only a lane beyond num_boot (it stores nothing) can pass 2^31 - 1
+  npyrng::Pcg64 g = fast_stream(seed, (uint64_t)slot_key[slot], (int)((uint32_t)rep_lo + (uint32_t)r));
   int32_t *wd = (w_dump && mine) ? w_dump + (slot * kmax_dump) * (int64_t)num_boot + r : nullptr;
   Sums2D sums;
   int32_t dn = (int32_t)nobs;  // N_g < 2^31 (checked by the host)
@@ -1164,17 +1170,37 @@ int mm_boot2d_fast(const double *d_pk, const double *d_lq, const double *d_v1, c
                    const double *d_b, const int64_t *d_tile_ptr, int64_t n_slots, const int32_t *d_slot_K, const double *d_slot_nobs,
                    const double *d_slot_omq, const int64_t *d_slot_row, const int64_t *d_slot_key, uint64_t seed, int32_t num_boot,
                    int64_t ld, double *d_out_corr, int32_t *d_w_dump, int32_t kmax_dump, void *stream) {
+  return mm_boot2d_fast_range(d_pk, d_lq, d_v1, d_v2, d_a, d_b, d_tile_ptr, n_slots, d_slot_K, d_slot_nobs, d_slot_omq, d_slot_row,
+                              d_slot_key, seed, 0, num_boot, ld, d_out_corr, d_w_dump, kmax_dump, stream);
+}
+
+// The grid of the two rng='fast' kernels for ``blocks`` workgroups.  gridDim.x * 256 threads must stay below 2^32 (a larger launch
+// runs only part of its blocks): up to FAST_GRID_X blocks the grid is one row, as it always was; beyond, rows of FAST_GRID_X
+// blocks, the last one ragged (its surplus waves return at once).
+static int fast_grid(int64_t blocks, dim3 *grid) {
+  const int64_t FAST_GRID_X = 1 << 22;
+  int64_t grid_x = blocks < FAST_GRID_X ? blocks : FAST_GRID_X, grid_y = (blocks + grid_x - 1) / grid_x;
+  MM_ARG(grid_y <= 65535);
+  *grid = dim3((unsigned)grid_x, (unsigned)grid_y);
+  return MM_OK;
+}
+
+int mm_boot2d_fast_range(const double *d_pk, const double *d_lq, const double *d_v1, const double *d_v2, const double *d_a,
+                         const double *d_b, const int64_t *d_tile_ptr, int64_t n_slots, const int32_t *d_slot_K,
+                         const double *d_slot_nobs, const double *d_slot_omq, const int64_t *d_slot_row, const int64_t *d_slot_key,
+                         uint64_t seed, int32_t rep_lo, int32_t rep_n, int64_t ld, double *d_out_corr, int32_t *d_w_dump,
+                         int32_t kmax_dump, void *stream) {
   MM_ARG(d_pk && d_lq && d_v1 && d_v2 && d_a && d_b && d_tile_ptr && d_slot_K && d_slot_nobs && d_slot_omq && d_slot_row && d_slot_key);
-  MM_ARG(d_out_corr && n_slots >= 0 && n_slots % 64 == 0 && num_boot > 0 && ld >= (int64_t)num_boot + 1);
+  MM_ARG(d_out_corr && n_slots >= 0 && n_slots % 64 == 0 && rep_n > 0 && ld >= (int64_t)rep_n + 1);
+  MM_ARG(rep_lo >= 0 && (int64_t)rep_lo + rep_n <= 2147483647LL);
   MM_ARG(!d_w_dump || kmax_dump > 0);
   if (n_slots == 0) return MM_OK;
-  int32_t chunks = (num_boot + 63) / 64;
+  int32_t chunks = (int32_t)(((int64_t)rep_n + 63) / 64);
   int64_t waves = n_slots * chunks;
-  int64_t blocks = (waves + 3) / 4;
-  MM_ARG(blocks < 2147483647LL);
-  hipLaunchKernelGGL(k_boot2d_fast, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, d_pk, d_lq, d_v1, d_v2, d_a, d_b, d_tile_ptr,
-                     n_slots, d_slot_K, d_slot_nobs, d_slot_omq, d_slot_row, d_slot_key, seed, num_boot, chunks, ld, d_out_corr, d_w_dump,
-                     kmax_dump);
+  dim3 grid;
+  if (int rc = fast_grid((waves + 3) / 4, &grid)) return rc;
+  hipLaunchKernelGGL(k_boot2d_fast, grid, dim3(256), 0, (hipStream_t)stream, d_pk, d_lq, d_v1, d_v2, d_a, d_b, d_tile_ptr, n_slots, d_slot_K,
+                     d_slot_nobs, d_slot_omq, d_slot_row, d_slot_key, seed, rep_lo, rep_n, chunks, ld, d_out_corr, d_w_dump, kmax_dump);
   MM_LAUNCH_CHECK();
   return MM_OK;
 }
@@ -1200,13 +1226,9 @@ int mm_boot1d_fast_range(const double *d_pk, const double *d_lq, const double *d
   if (n_slots == 0) return MM_OK;
   int32_t chunks = (int32_t)(((int64_t)rep_n + 63) / 64);
   int64_t waves = n_slots * chunks;
-  int64_t blocks = (waves + 3) / 4;
-  // gridDim.x * 256 threads must stay below 2^32 (a larger launch runs only part of its blocks): up to FAST_GRID_X blocks the grid
-  // is one row, as it always was; beyond, rows of FAST_GRID_X blocks, the last one ragged (its surplus waves return at once)
-  const int64_t FAST_GRID_X = 1 << 22;
-  int64_t grid_x = blocks < FAST_GRID_X ? blocks : FAST_GRID_X, grid_y = (blocks + grid_x - 1) / grid_x;
-  MM_ARG(grid_y <= 65535);
-  hipLaunchKernelGGL(k_boot1d_fast, dim3((unsigned)grid_x, (unsigned)grid_y), dim3(256), 0, (hipStream_t)stream, d_pk, d_lq, d_v, d_a, d_b,
+  dim3 grid;
+  if (int rc = fast_grid((waves + 3) / 4, &grid)) return rc;
+  hipLaunchKernelGGL(k_boot1d_fast, grid, dim3(256), 0, (hipStream_t)stream, d_pk, d_lq, d_v, d_a, d_b,
                      d_tile_ptr, n_slots, d_slot_K, d_slot_nobs, d_slot_omq, d_slot_row, d_slot_key, seed, rep_lo, rep_n, mean_only, chunks, ld,
                      d_out_mean, d_out_var, d_w_dump, kmax_dump);
   MM_LAUNCH_CHECK();

@@ -1414,6 +1414,22 @@ def pair_table_bytes(maxx, genes, col1, col2, n_groups, n_bins):
     return (cap[:, np.asarray(col1, dtype=np.int64)] * cap[:, np.asarray(col2, dtype=np.int64)]).sum(axis=0) * int(n_bins) * 4
 
 
+def contract_plane(plane, ld, B, ng, n_rows, test_row, W, good):
+    """K9/K10 on ONE response plane the caller holds (``plane``: fp64 device tensor, rows [row * ng + group][ld], replicate columns
+    1..B): test t applies the weight row ``W[t]`` to the groups ``good[test_row[t]]`` of row ``test_row[t]`` < ``n_rows``.
+    Returns (coef device tensor [n_tests][ld], stats host [n_tests][8])."""
+    torch = _torch()
+    n_tests = len(test_row)
+    test_row, good = np.asarray(test_row, dtype=np.int32), np.asarray(good, dtype=np.uint8)
+    if good.shape != (n_rows, ng) or (n_tests and (test_row.min() < 0 or test_row.max() >= n_rows)) or plane.numel() < n_rows * ng * ld or ld < B + 1:
+        raise ValueError("contract_plane: tests, good rows and plane do not match")      # (the kernel trusts the rows)
+    coef = empty((max(1, n_tests), ld), torch.float64)
+    stats = empty((max(1, n_tests), 8), torch.float64)
+    d_tp, d_W, d_good = dev(test_row), dev(np.asarray(W, dtype=np.float64)), dev(good)
+    _lib.call("mm_contract_stats", P(plane), P(plane), ld, B, ng, P(d_tp), P(d_W), P(d_good), n_tests, 0, P(coef), P(stats), _stream())
+    return coef, host(stats)[:n_tests]
+
+
 class Bootstrap2D:
     """2D analogue of Bootstrap1D for a list of gene pairs (column slots of a GeneColumns store):
     (x_i, x_j, sf_bin) histograms -> bins -> replay order -> replay bootstrap of the correlation."""
@@ -1475,22 +1491,25 @@ class Bootstrap2D:
         """Test helper (after run(fast=True, dump_weights=True)): the int32 multinomial weights [K][B] of chain q."""
         return host(self.w_dump[int(self.pair_slot[q]), :int(self.K[q]), :])
 
-    def run(self, skip, r1a, r1b, r0, true_corr, pcg_seed=5, target_waves=None, fast=False, fast_seed=0, pair_key=None, dump_weights=False):
+    def run(self, skip, r1a, r1b, r0, true_corr, pcg_seed=5, target_waves=None, fast=False, fast_seed=0, pair_key=None, dump_weights=False,
+            keep_fast=False):
         """All arrays are indexed by q = sorted_pair*n_groups + group (see ``self.order``).  Leaves the
         replicate correlations in self.yc [n_q][B+1] (column 0 = true correlation).
 
         ``fast``: the replicate-parallel kernel (mm_boot2d_fast) on dense 64-wide tiles of the operand planes instead of the replay
         kernels: replicate r of chain q draws from its own PCG64 stream derived from (``fast_seed``, ``pair_key[q]``, r) --
         ``pair_key`` [n_q] int64, default q; keys that do not depend on how the pairs were chunked or ordered make the result
-        independent of both -- and ``pcg_seed`` is ignored.  ``dump_weights`` (fast only): keep the weights for ``weights_of``."""
-        if dump_weights and not fast:
-            raise ValueError("dump_weights needs fast=True")
+        independent of both -- and ``pcg_seed`` is ignored.  ``dump_weights`` (fast only): keep the weights for ``weights_of``.
+        ``keep_fast`` (fast only): keep what a later launch on a replicate range reads (``launch_range``) -- the operand planes, the
+        tile layout, the slot tables, the stream keys and the seed.  The default keeps nothing."""
+        if (dump_weights or keep_fast) and not fast:
+            raise ValueError("dump_weights and keep_fast need fast=True")
         active = (~np.asarray(skip, dtype=bool)) & (self.K >= 1)
         c = self._choose_packing(active, fast, target_waves)
         t = self._lay_out_operands(c, fast)
         self.replay_kernel = None      # diagnostics (tests): the kernel launched
         status, ordered = _order_bins(self, "mm_bins_order2d", (self.d_xi, self.d_xj), ORDER_BIG_CAP_2D, c.order, t, (r1a, r1b, r0))
-        launched = self._launch(c, t, fast, true_corr, pcg_seed, fast_seed, pair_key, dump_weights)
+        launched = self._launch(c, t, fast, true_corr, pcg_seed, fast_seed, pair_key, dump_weights, keep_fast)
         _check_order_status(status, "mm_bins_order2d")
         del ordered, launched      # NB: every device operand must stay referenced until after the call that reads it
         self.active = active
@@ -1529,10 +1548,11 @@ class Bootstrap2D:
             t.ops = [empty((max(1, rows) * 64,), torch.float64) for _ in range(6)]
         return t
 
-    def _launch(self, c, t, fast, true_corr, pcg_seed, fast_seed, pair_key, dump_weights):
+    def _launch(self, c, t, fast, true_corr, pcg_seed, fast_seed, pair_key, dump_weights, keep_fast=False):
         """The replicate rows self.yc and the tile kernel that fills them.  Returns its device operands."""
         torch, s = _torch(), _stream()
         B, ld, n_tiles = self.B, self.ld, c.n_tiles
+        self._fast = None
         self.yc = torch.full((max(1, self.n_q), ld), float("nan"), dtype=torch.float64, device="cuda")
         self.yc[: self.n_q, 0] = dev(np.asarray(true_corr, dtype=np.float64))
         d_slot_K, d_nobs, d_omq, d_slot_pair = dev(t.slot_K), dev(t.nobs), dev(t.omq), dev(t.slot_pair)
@@ -1546,6 +1566,10 @@ class Bootstrap2D:
             _lib.call("mm_boot2d_fast", *map(P, t.ops), P(t.d_tile_ptr), n_tiles * 64, P(d_slot_K), P(d_nobs), P(d_omq), P(d_slot_pair),
                       P(d_slot_key), int(fast_seed) & ((1 << 64) - 1), B, ld, P(self.yc), P(self.w_dump), kmax_dump, s)
             self.replay_kernel = "mm_boot2d_fast"
+            if keep_fast:      # what a later launch on a replicate range reads (launch_range)
+                self._fast = SimpleNamespace(ops=t.ops, d_tile_ptr=t.d_tile_ptr, n_slots=n_tiles * 64, d_slot_K=d_slot_K, d_nobs=d_nobs, d_omq=d_omq,
+                                             pair_slot=t.pair_slot, d_slot_key=d_slot_key, kmax=int(t.tile_k.max()),
+                                             seed=int(fast_seed) & ((1 << 64) - 1))
         elif n_tiles and t.use_rec:
             d_slot_rec = dev(t.slot_rec)
             keep.append(d_slot_rec)
@@ -1557,6 +1581,38 @@ class Bootstrap2D:
                       pcg64_state(pcg_seed), B, ld, P(self.yc), s)
             self.replay_kernel = "mm_boot2d_replay"
         return keep
+
+    def launch_range(self, rep_lo, rep_n, open_q, plane, row_of_q, dump_weights=False):
+        """After ``run(fast=True, keep_fast=True)``: the replicates [rep_lo, rep_lo + rep_n) of the chains ``open_q`` (q = sorted_pair
+        * n_groups + group; mm_boot2d_fast_range on the kept operand planes, tile layout and stream keys; every other slot gets row
+        -1 and writes nothing) into columns 1..rep_n of the rows ``row_of_q`` of the caller's ``plane``, a contiguous fp64 device
+        tensor [rows][ld >= 1 + rep_n]; nothing else of it is written.  Chains of ``open_q`` that did not run (skipped, K < 1) are
+        left out.  Replicate rep_lo + i of a chain is bit for bit the one a one-shot ``run`` over more replicates stores in column
+        1 + rep_lo + i.  ``dump_weights``: keep the int32 weights in ``self.w_dump_range`` [slot][k][i] (slot =
+        ``self.pair_slot[q]``)."""
+        torch, f = _torch(), getattr(self, "_fast", None)
+        if f is None:
+            raise RuntimeError("launch_range needs a preceding run(fast=True, keep_fast=True): nothing else keeps the operands and the streams")
+        rep_lo, rep_n = int(rep_lo), int(rep_n)
+        if rep_lo < 0 or rep_n < 1 or rep_lo + rep_n > 2 ** 31 - 1:
+            raise ValueError("launch_range: need rep_lo >= 0, rep_n >= 1 and rep_lo + rep_n <= 2^31 - 1")
+        if (not torch.is_tensor(plane) or plane.dtype != torch.float64 or not plane.is_cuda or not plane.is_contiguous() or plane.dim() != 2
+                or plane.shape[1] < rep_n + 1):
+            raise ValueError("launch_range: plane must be a contiguous fp64 device tensor [rows][>= 1 + rep_n]")
+        open_q, row_of_q = np.asarray(open_q, dtype=np.int64).reshape(-1), np.asarray(row_of_q, dtype=np.int64).reshape(-1)
+        if len(open_q) != len(row_of_q) or (len(open_q) and (open_q.min() < 0 or open_q.max() >= self.n_q)):
+            raise ValueError("launch_range: open_q / row_of_q do not match the chains")
+        if len(row_of_q) and (row_of_q.min() < 0 or row_of_q.max() >= plane.shape[0]):
+            raise ValueError("launch_range: row out of range")       # (the kernel trusts the rows)
+        slot = f.pair_slot[open_q]
+        slot_row = np.full(f.n_slots, -1, dtype=np.int64)
+        slot_row[slot[slot >= 0]] = row_of_q[slot >= 0]
+        d_slot_row = dev(slot_row)
+        self.w_dump_range = zeros((f.n_slots, f.kmax, rep_n), torch.int32) if dump_weights else None
+        _lib.call("mm_boot2d_fast_range", *map(P, f.ops), P(f.d_tile_ptr), f.n_slots, P(f.d_slot_K), P(f.d_nobs), P(f.d_omq), P(d_slot_row),
+                  P(f.d_slot_key), f.seed, rep_lo, rep_n, plane.shape[1], P(plane), P(self.w_dump_range), f.kmax if dump_weights else 0,
+                  _stream())
+        return d_slot_row      # NB: stays referenced until the caller's next call on the stream
 
     def valid_cols(self, good):
         """hypothesis_test.py:372-373 on the device (see Bootstrap1D.valid_cols)."""
@@ -1570,14 +1626,7 @@ class Bootstrap2D:
 
     def contract(self, test_pair, W, good):
         """K9/K10 on the correlation rows: tests (sorted pair index, weight row)."""
-        torch = _torch()
-        n_tests = len(test_pair)
-        coef = empty((max(1, n_tests), self.ld), torch.float64)
-        stats = empty((max(1, n_tests), 8), torch.float64)
-        d_tp, d_W, d_good = dev(np.asarray(test_pair, dtype=np.int32)), dev(np.asarray(W, dtype=np.float64)), dev(np.asarray(good, dtype=np.uint8))
-        _lib.call("mm_contract_stats", P(self.yc), P(self.yc), self.ld, self.B, self.ng, P(d_tp), P(d_W), P(d_good), n_tests, 0, P(coef),
-                  P(stats), _stream())
-        return coef, host(stats)[:n_tests]
+        return contract_plane(self.yc, self.ld, self.B, self.ng, self.n_pairs, test_pair, W, np.asarray(good).reshape(self.n_pairs, self.ng))
 
     def contrast(self, test_pair, test_grp, ctrl, good):
         """Two-group contrasts of the correlation rows against the control group ``ctrl``, as ``Bootstrap1D.contrast``

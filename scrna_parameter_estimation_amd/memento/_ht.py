@@ -160,7 +160,7 @@ def _mix64(x):
 
 
 def check_sequential(max_boot, min_extreme, num_boot, rng, approx, ci):
-    """The ``max_boot`` / ``min_extreme`` keywords of ``ht_1d_vs_control``; pure, runs before ``adata`` is touched.  -> whether
+    """The ``max_boot`` / ``min_extreme`` keywords of ``ht_1d_vs_control`` and ``ht_2d_moments``; pure, runs before ``adata`` is touched.  -> whether
     the call is sequential (``max_boot`` given)."""
     if max_boot is None:
         return False
@@ -584,9 +584,9 @@ def chunks_2d(st, plan, num_boot):
     st.last_chunk2d = (plan.bounds[-2], plan.bounds[-1]) if plan.P_ else (0, 0)
 
 
-def run_chunk_2d(c, plan, uniforms, rng, fill_seed):
+def run_chunk_2d(c, plan, uniforms, rng, fill_seed, keep_fast=False):
     """Bootstrap the chunk's chains with the hash ``uniforms`` [3][pair x group] of the whole call; -> ``good`` [pair][group] in
-    device pair order."""
+    device pair order.  ``keep_fast`` (rng='fast'): the chunk keeps what ``continue_chunk_2d`` launches from."""
     ng = plan.ng
 
     def to_dev_order(a):
@@ -595,8 +595,59 @@ def run_chunk_2d(c, plan, uniforms, rng, fill_seed):
     r1a, r1b, r0 = uniforms
     c.bs.run(to_dev_order(plan.skip.reshape(-1)), to_dev_order(r1a), to_dev_order(r1b), to_dev_order(r0),
              to_dev_order(np.where(plan.skip, np.nan, plan.true_corr).reshape(-1)), fast=(rng == 'fast'), fast_seed=fill_seed,
-             pair_key=to_dev_order(plan.chain_key))
+             pair_key=to_dev_order(plan.chain_key), keep_fast=keep_fast)
     return c.bs.active.reshape(c.n_ch, ng)
+
+
+def continue_chunk_2d(c, ng, test_pair, W, good, stats, schedule, min_extreme, resampling, n_open):
+    """Rounds 1.. of the sequential bootstrap on an open pair chunk whose round 0 (``run_chunk_2d`` with rng='fast' and
+    ``keep_fast``, then ``bs.contract``) gave the records ``stats`` [test][8] of the tests (``test_pair`` [test] in device pair
+    order, weight rows ``W`` [test][group], ``good`` [pair][group]): the one-plane analogue of ``continue_chunk_1d``.  A test is
+    continued while it is open (``open_tests``).  Round j bootstraps the global replicates [schedule[j - 1], schedule[j]) of the
+    chains of the good groups of the pairs that still have an open test -- every other slot of the chunk's tile layout is skipped
+    -- into a pair-granular plane [open pairs x groups][1 + rep_n] (column 0 copied from the chunk, everything else NaN until
+    the launch writes it), contracts the open tests only, with their own weight rows and ``good`` rows and renumbered pairs, and
+    folds their records (``merge_records``).  There is no refill in 2D: an invalid replicate is a NaN column that the contraction
+    drops, so the counts of a test that is never closed are those of a one-shot call over ``schedule[-1]`` replicates.  The
+    round's plane is allocated once per round and released before the next; together with the coefficient row that
+    mm_contract_stats writes per open test it never holds more bytes than the chunk's replicate rows (a single pair excepted):
+    a round with more takes its open pairs in sub-batches (pairs are independent, and the streams are keyed by chain, so neither
+    this nor the chunking changes a number).  ``n_open`` [round]: the tests open after round j are added to entry j.
+    -> the merged records."""
+    bs, torch = c.bs, engine._torch()
+    test_pair, W, good = np.asarray(test_pair, dtype=np.int64), np.asarray(W, dtype=np.float64), np.asarray(good, dtype=bool)
+    merged = np.array(stats, dtype=np.float64)
+    grp = np.arange(ng)
+    for j in range(1, len(schedule)):
+        is_open = open_tests(merged, min_extreme, resampling)
+        n_open[j - 1] += int(is_open.sum())
+        if not is_open.any():
+            break
+        idx = np.flatnonzero(is_open)
+        rep_lo, rep_n = schedule[j - 1], schedule[j] - schedule[j - 1]
+        ld = 1 + rep_n
+        pairs, per_pair = np.unique(test_pair[idx], return_counts=True)
+        per = int(min(len(pairs), max(1, (bs.n_q * bs.ld) // ((ng + int(per_pair.max())) * ld))))
+        plane = engine.empty((per * ng, ld), torch.float64)
+        new = np.empty((len(idx), 8))
+        for lo in range(0, len(pairs), per):
+            psub = pairs[lo:lo + per]
+            sub = plane[:len(psub) * ng]
+            in_sub = np.isin(test_pair[idx], psub)
+            rows_old = (psub[:, None] * ng + grp).reshape(-1)
+            sub.fill_(float("nan"))
+            sub[:, 0] = bs.yc[engine.dev(rows_old), 0]
+            g_sub = good[psub]
+            rows_new = np.flatnonzero(g_sub.reshape(-1))
+            keep = bs.launch_range(rep_lo, rep_n, rows_old[rows_new], sub, rows_new)
+            coef, new[in_sub] = engine.contract_plane(sub, ld, rep_n, ng, len(psub), np.searchsorted(psub, test_pair[idx[in_sub]]),
+                                                      W[idx[in_sub]], g_sub)
+            del keep, coef
+        del plane, sub      # release-before-allocate: the next round's plane takes this buffer
+        merged[idx] = merge_records([merged[idx], new])
+    else:
+        n_open[len(schedule) - 1] += int(open_tests(merged, min_extreme, resampling).sum())
+    return merged
 
 
 def scatter_pairs(c, plan, dst, src, keep=None):

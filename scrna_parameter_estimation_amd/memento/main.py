@@ -1066,7 +1066,7 @@ def _replay_pair_draws(c, plan, uniforms, trt, tcol, per_gene, num_boot):
 
 
 def ht_2d_moments(adata, covariate, treatment, treatment_for_gene=None, inplace=True, num_boot=10000, verbose=3, num_cpus=1,
-                  max_rows=None, fill_seed=0, strict=False, rng='replay', ci=None, **kwargs):
+                  max_rows=None, fill_seed=0, strict=False, rng='replay', ci=None, *, max_boot=None, min_extreme=10, **kwargs):
     """Bootstrap hypothesis test of correlation differences (reference: memento/main.py:418-520,
     hypothesis_test._ht_2d :303-364).  Same replay semantics as ht_1d_moments.
     ``rng='fast'``: same samplers and replicate arithmetic, but every (pair, group, replicate) has its own counter-derived
@@ -1083,8 +1083,22 @@ def ht_2d_moments(adata, covariate, treatment, treatment_for_gene=None, inplace=
     ``frozenset({name of the pair's first gene})`` -- the key is built from idx_1 twice -- and one number per pair is stored,
     so the list must hold exactly one column (the reference raises ValueError on more); pinned by fixture ``api_tfg2d``.
     ``ci`` as in ``ht_1d_moments``: ``uns['memento']['2d_ht']['corr_ci']`` [pair][2] (NaN for skipped pairs) and ``['ci']``;
-    ``get_2d_ht_result`` then has ``corr_ci_lo, corr_ci_hi``."""
+    ``get_2d_ht_result`` then has ``corr_ci_lo, corr_ci_hi``.
+    ``max_boot`` / ``min_extreme`` (keyword-only; ``max_boot`` needs ``rng='fast'``, ``approx=False``, ``ci=None`` and no
+    ``resample_rep``): the sequential bootstrap of ``ht_1d_vs_control`` on the pair tests.  Round 0 is the plain call -- the same
+    launches, keys and records -- and only the tests whose extreme count is still <= ``min_extreme`` go on, to the cumulative
+    totals ``num_boot``, ``2 num_boot``, ..., ``max_boot`` (``_ht.sequential_schedule``); a round bootstraps only the chains of the
+    good groups of the pairs with an open test (``_ht.continue_chunk_2d``).  The streams are keyed by (``fill_seed``, pair, group,
+    replicate) and the 2D path refills nothing, so a test that is never closed has exactly the valid / extreme counts of the
+    one-shot ``num_boot=max_boot`` call.  ``corr_asl`` is ``(c + 1) / (n + 1)`` over all rounds for every test, with NO tail fit;
+    ``corr_se`` comes from the merged record (``_ht.merge_records``); ``corr_coef`` is untouched.  Adds ``corr_nboot`` [pair] (the
+    valid replicates behind each p-value, 0 where there is no test), ``max_boot`` and ``min_extreme`` to ``uns['memento']['2d_ht']``;
+    ``get_2d_ht_result`` then has a ``corr_nboot`` column.  Nothing here is rank-aware: pair blocks are sharded by the caller."""
     resampling, resample_rep, approx = _ht.check_args(rng, strict, **kwargs)
+    sequential = _ht.check_sequential(max_boot, min_extreme, num_boot, rng, approx, ci)
+    if sequential and resample_rep:
+        raise ValueError("max_boot needs resample_rep=False: its replicate-column assignments are drawn over all columns of one "
+                         "plane, which no round holds")
     probs = _ht.ci_probs(ci)
     if not inplace:
         adata = adata.copy()
@@ -1111,15 +1125,27 @@ def ht_2d_moments(adata, covariate, treatment, treatment_for_gene=None, inplace=
     uniforms = np.zeros((3, plan.P_ * plan.ng)) if replay_rr else _ht.hash_uniforms(~plan.skip.reshape(-1), 3)
     corr_coef, corr_se, corr_asl = (np.full(plan.n_conv, np.nan) for _ in range(3))
     corr_ci = np.full((plan.n_conv, 2), np.nan) if probs is not None else None
+    if sequential:
+        corr_nboot = np.zeros(plan.n_conv, dtype=np.int64)
+        schedule = _ht.sequential_schedule(num_boot, max_boot)
+        st.last_sequential = SimpleNamespace(schedule=schedule, n_open=[0] * len(schedule))   # (diagnostics: tests open after each round)
 
     def run_chunk(c):
         bs = c.bs
         rep_assign = bcol_assign = None
         if replay_rr:
             rep_assign, bcol_assign = _replay_pair_draws(c, plan, uniforms, trt, tcol, per_gene, num_boot)
-        good = _ht.run_chunk_2d(c, plan, uniforms, rng, fill_seed)                 # device order
+        good = _ht.run_chunk_2d(c, plan, uniforms, rng, fill_seed, keep_fast=sequential)   # device order
         d = _ht.pair_design_tables(good, tcol[c.lo:c.hi][c.so], per_gene, cov, trt, Nc_list, resampled=resample_rep)
         coef, stt = bs.contract(d.test_row, d.Wmat, good)
+        if sequential:
+            del coef           # (the rounds' planes may take its buffer)
+            stt = st.last_records2d = _ht.continue_chunk_2d(c, plan.ng, d.test_row, d.Wmat, good, stt, schedule, min_extreme, resampling,
+                                                            st.last_sequential.n_open)
+            for dst, src in ((corr_coef, stt[:, 0]), (corr_se, stt[:, 1]), (corr_asl, _ht.sequential_pvalues(stt, resampling)),
+                             (corr_nboot, stt[:, 2].astype(np.int64))):
+                _ht.scatter_pairs(c, plan, dst, src, keep=good.any(axis=1))
+            return
         if resample_rep and d.rr_test.any():
             col_map, n_valid = _ht.surviving_cols(bs, good, num_boot)             # hypothesis_test.py:372-373
             if n_valid is not None and replay_rr:
@@ -1127,6 +1153,7 @@ def ht_2d_moments(adata, covariate, treatment, treatment_for_gene=None, inplace=
             coef_r, stt_r = bs.contract_resampled(d.test_row, d.tt_mat, good, d.row_mask, d.Mstack, Nc_list, rep=rep_assign,
                                                   bcol=bcol_assign, seed=fill_seed + 17 + c.lo, col_map=col_map, n_valid=n_valid)
             coef, stt = _ht.merge_resampled(coef, stt, coef_r, stt_r, d.rr_test)
+        st.last_records2d = stt                # (diagnostics / tests: the test records of the last pair chunk, device pair order)
         pvals = _asl.asl_from_stats(stt, approx, lambda idx: engine.host(coef[engine.dev(np.asarray(idx, dtype=np.int64))]), num_cpus, resampling)
         for dst, src in ((corr_coef, stt[:, 0]), (corr_se, stt[:, 1]), (corr_asl, pvals)):
             _ht.scatter_pairs(c, plan, dst, src, keep=good.any(axis=1))
@@ -1139,6 +1166,8 @@ def ht_2d_moments(adata, covariate, treatment, treatment_for_gene=None, inplace=
     m['2d_ht'] = {'treatment': treatment, 'covariate': covariate, 'corr_coef': corr_coef, 'corr_se': corr_se, 'corr_asl': corr_asl}
     if probs is not None:
         m['2d_ht']['corr_ci'], m['2d_ht']['ci'] = corr_ci, float(ci)
+    if sequential:
+        m['2d_ht'].update(corr_nboot=corr_nboot, max_boot=int(max_boot), min_extreme=int(min_extreme))
     if treatment_for_gene is not None:
         m['2d_ht']['treatment_for_gene'] = treatment_for_gene                      # main.py:513-514
     if not inplace:
@@ -1466,4 +1495,6 @@ def get_2d_ht_result(adata):
     df['corr_coef'], df['corr_se'], df['corr_pval'] = m['2d_ht']['corr_coef'], m['2d_ht']['corr_se'], m['2d_ht']['corr_asl']
     if 'corr_ci' in m['2d_ht']:                 # ht_2d_moments(ci=...)
         _ci_columns(df, ('corr', m['2d_ht']['corr_ci']))
+    if 'corr_nboot' in m['2d_ht']:              # ht_2d_moments(max_boot=...)
+        df['corr_nboot'] = m['2d_ht']['corr_nboot']
     return df

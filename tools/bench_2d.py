@@ -1,11 +1,34 @@
 """2D sanity / timing run (shape of BASELINE configs[3], scaled): compute_2d_moments + ht_2d_moments for
-n_left x n_right gene pairs.  usage: python tools/bench_2d.py [cells genes n_left n_right num_boot]"""
+n_left x n_right gene pairs.
+--rng fast runs the replicate-parallel bootstrap (mm_boot2d_fast) instead of the replay kernel (the default).
+--max-boot N (with --rng fast) runs the sequential bootstrap, ht_2d_moments(num_boot, max_boot=N, min_extreme=--min-extreme), with
+approx=False, and prints the tests open after every round; --exact runs a plain call with approx=False too (tail fits on the host).
+--repeat N: one warm-up call (allocator, kernel load), then N timed calls, median / min / max; without it ONE call, as before.
+usage: python tools/bench_2d.py [--rng replay|fast] [--max-boot N] [--min-extreme M] [--repeat N] [--exact] [--num-cpus C]
+                                [cells genes n_left n_right num_boot]"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, pandas as pd, torch, scipy.sparse as sp
 import bench
 from scrna_parameter_estimation_amd import AnnDataLite, memento
 
+
+def _opt(name, default, conv=int):
+    if name in sys.argv:
+        i = sys.argv.index(name)
+        v = conv(sys.argv[i + 1])
+        del sys.argv[i:i + 2]
+        return v
+    return default
+
+
+rng_mode, max_boot, min_extreme = _opt("--rng", "replay", str), _opt("--max-boot", None), _opt("--min-extreme", 10)
+repeat, num_cpus = _opt("--repeat", 0), _opt("--num-cpus", 8)
+exact = "--exact" in sys.argv
+if exact:
+    sys.argv.remove("--exact")
+if rng_mode not in ("replay", "fast"):
+    sys.exit("--rng must be replay or fast")
 torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", 0)) % max(1, torch.cuda.device_count()))
 cells, genes, nl, nr, B = [int(x) for x in sys.argv[1:6]] if len(sys.argv) > 5 else (100_000, 4000, 60, 60, 500)
 cfg = dict(cells=cells, genes=genes, density=0.08)
@@ -32,14 +55,35 @@ trt = pd.DataFrame({"cond": gdf["cond"].astype(float)}, index=gdf.index)
 torch.cuda.synchronize(); t0 = time.time()
 memento.compute_2d_moments(adata, pairs)
 torch.cuda.synchronize(); t1 = time.time()
-np.random.seed(0)
-memento.ht_2d_moments(adata, covariate=cov, treatment=trt, num_boot=B, num_cpus=8, verbose=0, resampling="bootstrap", approx=True)
-torch.cuda.synchronize(); t2 = time.time()
-ht = adata.uns["memento"]["2d_ht"]
-bs = adata.uns["memento"]["_hip"].last_bootstrap2d
-print(f"pairs={len(pairs)} compute_2d={t1-t0:.3f}s ht_2d={t2-t1:.3f}s -> {len(pairs)/(t2-t0):.1f} pair-tests/s; K mean {bs.K.mean():.0f} max {bs.K.max()}; finite p {np.isfinite(ht['corr_asl']).mean():.3f}")
-from scrna_parameter_estimation_amd import engine
+kw = dict(approx=not (exact or max_boot is not None))
+if rng_mode != "replay":
+    kw["rng"] = rng_mode
+if max_boot is not None:
+    kw.update(max_boot=max_boot, min_extreme=min_extreme)
+print(f"ht_2d_moments(num_boot={B}, num_cpus={num_cpus}, {', '.join(f'{k}={v!r}' for k, v in kw.items())})", flush=True)
 st = adata.uns["memento"]["_hip"]
+times = []
+for r in range(repeat + 1 if repeat else 1):                      # with --repeat, run 0 is the warm-up
+    np.random.seed(0)
+    torch.cuda.synchronize(); t2 = time.time()
+    memento.ht_2d_moments(adata, covariate=cov, treatment=trt, num_boot=B, num_cpus=num_cpus, verbose=0, resampling="bootstrap", **kw)
+    torch.cuda.synchronize(); t3 = time.time()
+    times.append(t3 - t2)
+    if repeat:
+        print(f"  run {r}{' (warm-up)' if r == 0 else ''}: {t3 - t2:.3f}s", flush=True)
+timed = times[1:] or times
+t_ht = float(np.median(timed))
+ht = adata.uns["memento"]["2d_ht"]
+bs = st.last_bootstrap2d
+if repeat:
+    print(f"ht_2d median of {len(timed)} runs {t_ht:.3f}s (min {min(timed):.3f} max {max(timed):.3f})")
+p = ht["corr_asl"]
+print(f"pairs={len(pairs)} compute_2d={t1-t0:.3f}s ht_2d={t_ht:.3f}s -> {len(pairs)/(t_ht+t1-t0):.1f} pair-tests/s; K mean {bs.K.mean():.0f} max {bs.K.max()}; finite p {np.isfinite(p).mean():.3f}; "
+      f"p < 1/{B + 1}: {int((p[np.isfinite(p)] < 1 / (B + 1)).sum())}")
+if max_boot is not None:
+    print(f"sequential: schedule {st.last_sequential.schedule}, tests open after each round {st.last_sequential.n_open}; "
+          f"corr_nboot == max_boot: {int((ht['corr_nboot'] == max_boot).sum())}")
+from scrna_parameter_estimation_amd import engine
 # algorithmic bytes of the pair kernels: every pair reads its partner column's entries (4 B each) in every block
 name_col = {n: i for i, n in enumerate(names)}
 nnz_gene = st.blocks.blk_cnt.astype(np.int64).sum(axis=0)[st.gene_idx]
