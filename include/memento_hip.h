@@ -609,7 +609,30 @@ int mm_boot2d_fast_range(const double *d_pk, const double *d_lq, const double *d
  * (Cholesky factor of the correlation matrix x white noise from mm_std_normal: a library GEMM on the caller's side); then
  * nb = nbinom.ppf(Phi(score)) replaces the own NB draw, and with d_cell_size != NULL (needs d_raw_totals from a mode-3 pass)
  * z = rint(nb / raw_total[cell] * cell_size[cell]) (simulate.py:86-89).  d_gauss == NULL: independent branch (:66-68).
- * Draws are NOT numpy's (different generators): statistical equivalence only. */
+ * Draws are NOT numpy's (different generators): statistical equivalence only.
+ * The stream keys (restated in numpy in tests/_simulate_ref.py).  mix() is the splitmix64 output function without the increment
+ * (x = (x ^ x >> 30) * 0xBF58476D1CE4E5B9; x = (x ^ x >> 27) * 0x94D049BB133111EB; x ^ x >> 31), all arithmetic is uint64.
+ * A stream is the state s0 = make(seed, a, b) = mix(seed ^ mix(a * 0x9E3779B97F4A7C15 + 0x632BE59BD9B4E019) ^ mix(b + 0xD1B54A32D192ED03));
+ * its n-th uniform (n = 1, 2, ...) is ((mix(s0 + n * 0x9E3779B97F4A7C15) >> 11) + 0.5) / 2^53.  Three families:
+ *   - the NB draw of (cell, gene):  make(seed_z, cell, gene), gene a non-negative int32, so b < 2^31;
+ *   - the capture stream of a cell: make(seed_capture, cell, 2^32 + 0x5EED), consumed gene by gene in ascending order;
+ *   - element i of mm_std_normal:   make(seed, i, 2^33 + 0x6A55), one Box-Muller pair, the cosine branch.
+ * mix is a bijection, so for one (seed, a) two different b are two different streams: the tags of the last two families sit
+ * in the high word of b, where no gene index reaches, and seed_z == seed_capture == seed is as good as any other choice.
+ * Sentinels: a gene with mean <= 0 or NaN is all zero and consumes no draw; nothing outside [0, n_cells) of d_totals,
+ * d_row_nnz, d_raw_totals and outside [d_row_ptr[0], d_row_ptr[n_cells]) of the CSR arrays is written; n_cells == 0 launches
+ * nothing.
+ * The copula quantile: the smallest k with CDF(k) >= Phi(score) in double, Phi(score) = erfc(-score / sqrt 2) / 2, by summing
+ * the pmf upwards (compensated) from max(0, floor(mean - 9 sd)) until the bound on the remaining tail falls below 2^-54: no
+ * finite score is cut short.  The first term is p^theta, or above 0 the binomial saddle-point form (Loader 2000), which has
+ * no difference of large lgamma values in it.  Domain: the result is exact up to ties (Phi(score) within rounding of a CDF
+ * step; then one off) for mean <= 1e4, theta in [0.01, 1e5] and scores in [-6.5, 6.5], which
+ * tests/test_gpu_simulate_kernels.py checks against extended-precision sums, the excuse being the routine's own rounding
+ * distance.  Nothing in the routine changes beyond that domain, but nothing is checked there; the rounding of the recurrence
+ * grows with the number of terms between the start and the answer (~9 sd).  A score of +inf (Phi == 1, every score from 8.3)
+ * returns the k at which the running sum rounds to 1 or the tail bound is reached, whichever comes first; -inf (every score
+ * below -38.5) and NaN return the start of the sum.  The loop is bounded by the geometric tail (ratio mean / (mean + theta)):
+ * at (1e4, 0.01) ~4e7 terms for a lane that holds a score of 8.3 or more. */
 int mm_simulate(const double *d_mean, const double *d_theta, int32_t n_genes, int64_t n_cells, const double *d_qs, uint64_t seed_z,
                 uint64_t seed_capture, int32_t process, int32_t mode, int64_t *d_totals, int64_t *d_row_nnz, const int64_t *d_row_ptr,
                 int32_t *d_out_indices, float *d_out_data, const float *d_gauss, const double *d_cell_size, int64_t *d_raw_totals,

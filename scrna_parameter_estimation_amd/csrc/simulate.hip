@@ -14,7 +14,7 @@
 // nb_cg = nbinom.ppf(Phi(y_cg)) and z_cg = round(nb_cg / sum_g nb_cg * cell_size_c), again regenerated in every pass.
 // Draw-level parity with numpy/scipy is NOT a goal (different generators): "parity unpinned", validated statistically
 // (moment recovery through the estimators, tests/test_gpu_simulate.py) -- the reference's own acceptance style
-// (analysis/simulation/estimator_validation.ipynb).
+// (analysis/simulation/estimator_validation.ipynb) -- and law by law against the exact pmfs (tests/test_gpu_simulate_kernels.py).
 #include "mm_common.h"
 #include <math.h>
 
@@ -32,6 +32,11 @@ __device__ __forceinline__ uint64_t mix(uint64_t x) {  // splitmix64 finaliser
 __device__ __forceinline__ Rng make(uint64_t seed, uint64_t a, uint64_t b) {
   return Rng{mix(seed ^ mix(a * 0x9E3779B97F4A7C15ull + 0x632BE59BD9B4E019ull) ^ mix(b + 0xD1B54A32D192ED03ull))};
 }
+// Stream keys (include/memento_hip.h states the scheme).  A stream is make(seed, a, b): the NB draw of (cell, gene) has
+// b = gene, a non-negative int32, so b < 2^31.  The other two families carry a tag in the high word of b, which no gene
+// index can take: mix() is a bijection, so for one (seed, a) different b are different streams, whatever the seeds.
+constexpr uint64_t TAG_CAPTURE = (1ull << 32) | 0x5EEDull;   // capture stream of a cell: make(seed_capture, cell, TAG_CAPTURE)
+constexpr uint64_t TAG_NORMAL = (2ull << 32) | 0x6A55ull;    // mm_std_normal element i: make(seed, i, TAG_NORMAL)
 __device__ __forceinline__ double uniform(Rng &g) {  // (0, 1)
   g.s += 0x9E3779B97F4A7C15ull;
   return ((double)(mix(g.s) >> 11) + 0.5) * (1.0 / 9007199254740992.0);
@@ -90,21 +95,68 @@ __device__ __forceinline__ int64_t neg_binomial(uint64_t seed, int64_t cell, int
   return poisson(g, lam);
 }
 
-// Quantile of NB(mean mu, size theta) at Phi(y): the smallest k with CDF(k) >= u (scipy.stats.nbinom.ppf).  The pmf is summed
-// upwards from k0 = max(0, mean - 9 sd) (the mass below k0 is < 1e-17) with the recurrence pmf(k+1) = pmf(k) (k + theta) / (k + 1) q.
+// Saddle-point pieces of the start term below (Loader 2000, "Fast and accurate computation of binomial probabilities"):
+// stirlerr(n) = log n! - log(sqrt(2 pi n) (n / e)^n), and the deviance bd0(x, m) = x log(x / m) + m - x, each small and
+// computed without the cancellation of a difference of lgamma values.
+__device__ double stirlerr(double n) {
+  if (n > 15.0) {
+    double nn = n * n;
+    return (1.0 / 12.0 - (1.0 / 360.0 - (1.0 / 1260.0 - (1.0 / 1680.0 - (1.0 / 1188.0) / nn) / nn) / nn) / nn) / n;
+  }
+  return lgamma(n + 1.0) - (n + 0.5) * log(n) + n - 0.91893853320467274178;   // log sqrt(2 pi)
+}
+__device__ double bd0(double x, double m) {
+  if (fabs(x - m) < 0.1 * (x + m)) {
+    double v = (x - m) / (x + m), s = (x - m) * v, ej = 2.0 * x * v;
+    v *= v;
+    for (int j = 1; j < 1000; j++) {
+      ej *= v;
+      double s1 = s + ej / (double)(2 * j + 1);
+      if (s1 == s) return s1;
+      s = s1;
+    }
+    return s;
+  }
+  return x * log(x / m) + m - x;
+}
+
+// Quantile of NB(mean mu, size theta) at u = Phi(y): the smallest k with CDF(k) >= u (scipy.stats.nbinom.ppf).  The pmf is summed
+// upwards from k0 = max(0, mean - 9 sd) (the mass below k0 is < 1e-17) with the recurrence pmf(k+1) = pmf(k) r_k,
+// r_k = (k + theta) / (k + 1) q; the running sum is compensated (two-sum), so its error does not grow with the number of terms
+// (a theta = 0.02 gene needs ~1e5 of them at a score of 6.5, where one CDF step is 1e-14).
+// Start term: pmf(0) = p^theta; for k0 > 0 (theta > 81) the binomial saddle-point form
+//   pmf(k) = theta / (theta + k) * sqrt(n / (2 pi theta k)) exp(stirlerr(n) - stirlerr(theta) - stirlerr(k) - bd0(theta, n p) - bd0(k, n q)),
+// n = k + theta, whose terms are of the size of log pmf(k0) ~ 40.  (lgamma(k0 + theta) - lgamma(theta) - lgamma(k0 + 1) + ...
+// has terms of 1e6 at (1e4, 1e5): their rounding, 1e-10 of every pmf, is several CDF steps at a score of 6.)
+// Stop: the mass beyond k is at most pmf(k) R / (1 - R), R = max(r_k, q) < 1 (r_k falls to q for theta >= 1 and rises to q
+// for theta < 1).  Once that bound is below 2^-54 no u < 1 of a double (1 - u >= 2^-53) can lie beyond k, so the sum ends
+// there: no score is cut short, and the loop is bounded by the geometric tail.  u == 1 (score >= 8.3, +inf) returns the k at
+// which the running sum rounds to 1 or that bound is reached, whichever comes first.  u == 0 (score <= -38.5, -inf) and a NaN
+// score return k0.
+// Exact up to ties (u within rounding of a CDF step: then one off); checked for mu <= 1e4, theta in [0.01, 1e5], scores to 6.5.
 __device__ int64_t nb_quantile(double y, double mu, double theta) {
   if (!(mu > 0.0)) return 0;
   double u = 0.5 * erfc(-y * 0.70710678118654752440);
   double p = theta / (theta + mu), q = mu / (theta + mu);
   double sd = sqrt(mu + mu * mu / theta);
   double k0 = floor(fmax(0.0, mu - 9.0 * sd));
-  double lp = lgamma(k0 + theta) - lgamma(theta) - lgamma(k0 + 1.0) + theta * log(p) + k0 * log(q);
-  double pmf = exp(lp), cum = pmf, k = k0;
-  double kmax = mu + 40.0 * sd + 60.0;
-  while (cum < u && k < kmax) {
-    pmf *= (k + theta) / (k + 1.0) * q;
+  double pmf;
+  if (k0 > 0.0) {
+    double n = k0 + theta;
+    double lp = stirlerr(n) - stirlerr(theta) - stirlerr(k0) - bd0(theta, n * p) - bd0(k0, n * q);
+    pmf = theta / n * sqrt(n / (6.28318530717958647692 * theta * k0)) * exp(lp);
+  } else {
+    pmf = exp(theta * log(p));
+  }
+  double cum = pmf, comp = 0.0, k = k0;
+  while (cum + comp < u) {
+    double r = (k + theta) / (k + 1.0) * q, rmax = fmax(r, q);
+    if (pmf * rmax < 0x1p-54 * (1.0 - rmax)) break;
+    pmf *= r;
     k += 1.0;
-    cum += pmf;
+    double t = cum + pmf, bb = t - cum;                  // two-sum: t + e == cum + pmf exactly
+    comp += (cum - (t - bb)) + (pmf - bb);
+    cum = t;
   }
   return (int64_t)k;
 }
@@ -119,7 +171,7 @@ __device__ __forceinline__ int64_t molecules(uint64_t seed, int64_t cell, int32_
 }
 
 __device__ __forceinline__ double normal_at(uint64_t seed, int64_t i) {
-  Rng g = make(seed, (uint64_t)i, 0x6A55ull);
+  Rng g = make(seed, (uint64_t)i, TAG_NORMAL);
   return normal(g);
 }
 
@@ -158,7 +210,7 @@ __global__ __launch_bounds__(256) void k_simulate(const double *__restrict__ mu,
     s_rem = (int64_t)rint(q * (double)t_rem);  // np.round: half to even (simulate.py:107)
     if (s_rem > t_rem) s_rem = t_rem;
   }
-  sim::Rng cap = sim::make(seed_c, (uint64_t)cell, 0x5EEDull);  // one capture stream per cell (the urn draw is sequential)
+  sim::Rng cap = sim::make(seed_c, (uint64_t)cell, sim::TAG_CAPTURE);  // one capture stream per cell (the urn draw is sequential)
   int64_t k = 0, base = mode == 2 ? row_ptr[cell] : 0;
   for (int32_t g = 0; g < n_genes; g++) {
     int64_t z = sim::molecules(seed_z, cell, g, n_cells, mu[g], theta[g], gauss, scale);
