@@ -596,6 +596,23 @@ int mm_boot2d_fast_range(const double *d_pk, const double *d_lq, const double *d
                          const double *d_slot_omq, const int64_t *d_slot_row, const int64_t *d_slot_key, uint64_t seed, int32_t rep_lo,
                          int32_t rep_n, int64_t ld, double *d_out_corr, int32_t *d_w_dump, int32_t kmax_dump, void *stream);
 
+/* mm_boot2d_fast_range over a LIST of slots (sequential bootstrap of ht_2d_vs_control_sequential(rng='fast', max_boot=...)): the launch has
+ * one wave per (listed slot, 64 replicates) -- wave w takes slot d_slot_list[w / chunks], chunks = ceil(rep_n / 64) -- instead of
+ * one per slot of the whole tile layout, so a round's grid is sized by the chains it continues, not by the chunk.  Once the slot
+ * is known it is the same kernel body: the stream (seed, d_slot_key[s], rep_lo + i), the operands and the store to column 1 + i
+ * of row d_slot_row[s] are those of mm_boot2d_fast_range, and a listed slot gets bit for bit the replicates that launch gives it.
+ *   - There is no weight dump.  rep_lo, rep_n, ld and n_slots are checked as in mm_boot2d_fast_range.
+ *   - n_list >= 0; d_slot_list (int64 [n_list], device) may be NULL only when n_list == 0, which returns MM_OK without a launch.
+ *   - The list is trusted: every entry must be a slot of the layout, 0 <= s < n_slots; validate it on the host.  A listed slot
+ *     with d_slot_K[s] <= 0 or d_slot_row[s] < 0 writes nothing; a slot that is not listed is never read, whatever its row.
+ *   - A slot listed twice is written twice with the same values (two waves store identical cells); the engine never does that:
+ *     its lists are ascending and unique.
+ *   - Grid: n_list x chunks waves, four per block, laid out as in mm_boot2d_fast_range (fewer than 2^32 threads per dimension). */
+int mm_boot2d_fast_slots(const double *d_pk, const double *d_lq, const double *d_v1, const double *d_v2, const double *d_a,
+                         const double *d_b, const int64_t *d_tile_ptr, int64_t n_slots, const int32_t *d_slot_K, const double *d_slot_nobs,
+                         const double *d_slot_omq, const int64_t *d_slot_row, const int64_t *d_slot_key, uint64_t seed, int32_t rep_lo,
+                         int32_t rep_n, int64_t ld, double *d_out_corr, const int64_t *d_slot_list, int64_t n_list, void *stream);
+
 /* ---- synthetic data generator (replaces memento/simulate.py:52-89 and :91-115) ----
  * Counter-based: transcriptome count z[cell][gene] ~ NB(mean[gene], size theta[gene]) is a pure function of (seed_z, cell, gene),
  * so nothing dense is ever stored.  One launch per pass, selected by `mode`:

@@ -108,6 +108,8 @@ _SIGS = {
                        ctypes.c_int),
     "mm_boot2d_fast_range": ([c_void_p] * 7 + [c_int64] + [c_void_p] * 5 + [c_uint64, c_int32, c_int32, c_int64, c_void_p, c_void_p, c_int32,
                                                                             c_void_p], ctypes.c_int),
+    "mm_boot2d_fast_slots": ([c_void_p] * 7 + [c_int64] + [c_void_p] * 5 + [c_uint64, c_int32, c_int32, c_int64, c_void_p, c_void_p, c_int64,
+                                                                            c_void_p], ctypes.c_int),
     "mm_simulate": ([c_void_p, c_void_p, c_int32, c_int64, c_void_p, c_uint64, c_uint64, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
                      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p], ctypes.c_int),
     "mm_std_normal": ([c_uint64, c_int64, c_void_p, c_void_p], ctypes.c_int),

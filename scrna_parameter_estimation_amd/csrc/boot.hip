@@ -910,20 +910,31 @@ __global__ __launch_bounds__(256, MINW) void k_boot2d_replay(const double *__res
 // nothing.  Lanes beyond num_boot walk along and store nothing.  The grid is one row of blocks up to FAST_GRID_X of them and rows
 // of FAST_GRID_X blocks in gridDim.y beyond (mm_boot2d_fast_range); the waves behind the last slot return at once.
 // w_dump (optional): int32 weights [slot][k < kmax_dump][i < num_boot].
-__global__ __launch_bounds__(256) void k_boot2d_fast(const double *__restrict__ pk_, const double *__restrict__ lq_,
-                                                     const double *__restrict__ v1_, const double *__restrict__ v2_,
-                                                     const double *__restrict__ a, const double *__restrict__ b,
-                                                     const int64_t *__restrict__ tile_ptr, int64_t n_slots,
-                                                     const int32_t *__restrict__ slot_K, const double *__restrict__ slot_nobs,
-                                                     const double *__restrict__ slot_omq, const int64_t *__restrict__ slot_row,
-                                                     const int64_t *__restrict__ slot_key, uint64_t seed, int32_t rep_lo,
-                                                     int32_t num_boot, int32_t chunks, int64_t ld, double *__restrict__ out_corr,
-                                                     int32_t *__restrict__ w_dump, int32_t kmax_dump) {
+//
+// LISTED (k_boot2d_fast_slots, mm_boot2d_fast_slots): the launch covers the ``n_list`` slots of ``slot_list`` instead of the whole
+// tile layout -- wave wid takes slot_list[wid / chunks] -- and everything from there on is the same body, so a listed slot gets bit
+// for bit the replicates that the launch over the layout gives it.  The list is trusted (a slot outside the layout is passed over).
+template <bool LISTED>
+__device__ __forceinline__ void boot2d_fast_body(const double *__restrict__ pk_, const double *__restrict__ lq_,
+                                                 const double *__restrict__ v1_, const double *__restrict__ v2_,
+                                                 const double *__restrict__ a, const double *__restrict__ b,
+                                                 const int64_t *__restrict__ tile_ptr, int64_t n_slots,
+                                                 const int32_t *__restrict__ slot_K, const double *__restrict__ slot_nobs,
+                                                 const double *__restrict__ slot_omq, const int64_t *__restrict__ slot_row,
+                                                 const int64_t *__restrict__ slot_key, uint64_t seed, int32_t rep_lo,
+                                                 int32_t num_boot, int32_t chunks, int64_t ld, double *__restrict__ out_corr,
+                                                 int32_t *__restrict__ w_dump, int32_t kmax_dump,
+                                                 const int64_t *__restrict__ slot_list, int64_t n_list) {
   int lane = mm_lane();
   // (a grid dimension holds fewer than 2^32 threads: the blocks beyond FAST_GRID_X go to gridDim.y)
   int64_t wid = (((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * blockDim.x + threadIdx.x) >> 6;
   int64_t slot = wid / chunks;
   int chunk = (int)(wid % chunks);
+  if (LISTED) {
+    if (slot >= n_list) return;
+    slot = slot_list[slot];
+    if (slot < 0) return;
+  }
   if (slot >= n_slots) return;
   int K = slot_K[slot];
   int64_t row = slot_row[slot];
@@ -953,6 +964,33 @@ __global__ __launch_bounds__(256) void k_boot2d_fast(const double *__restrict__ 
     c_pk = n_pk; c_lq = n_lq; c_x1 = n_x1; c_x2 = n_x2; c_a = n_a; c_b = n_b;
   }
   if (mine) out_corr[row * ld + 1 + r] = close_replicate_2d(sums, nobs);
+}
+
+__global__ __launch_bounds__(256) void k_boot2d_fast(const double *__restrict__ pk_, const double *__restrict__ lq_,
+                                                     const double *__restrict__ v1_, const double *__restrict__ v2_,
+                                                     const double *__restrict__ a, const double *__restrict__ b,
+                                                     const int64_t *__restrict__ tile_ptr, int64_t n_slots,
+                                                     const int32_t *__restrict__ slot_K, const double *__restrict__ slot_nobs,
+                                                     const double *__restrict__ slot_omq, const int64_t *__restrict__ slot_row,
+                                                     const int64_t *__restrict__ slot_key, uint64_t seed, int32_t rep_lo,
+                                                     int32_t num_boot, int32_t chunks, int64_t ld, double *__restrict__ out_corr,
+                                                     int32_t *__restrict__ w_dump, int32_t kmax_dump) {
+  boot2d_fast_body<false>(pk_, lq_, v1_, v2_, a, b, tile_ptr, n_slots, slot_K, slot_nobs, slot_omq, slot_row, slot_key, seed, rep_lo,
+                          num_boot, chunks, ld, out_corr, w_dump, kmax_dump, nullptr, 0);
+}
+
+// The body over a list of slots, without a weight dump (mm_boot2d_fast_slots).
+__global__ __launch_bounds__(256) void k_boot2d_fast_slots(const double *__restrict__ pk_, const double *__restrict__ lq_,
+                                                           const double *__restrict__ v1_, const double *__restrict__ v2_,
+                                                           const double *__restrict__ a, const double *__restrict__ b,
+                                                           const int64_t *__restrict__ tile_ptr, int64_t n_slots,
+                                                           const int32_t *__restrict__ slot_K, const double *__restrict__ slot_nobs,
+                                                           const double *__restrict__ slot_omq, const int64_t *__restrict__ slot_row,
+                                                           const int64_t *__restrict__ slot_key, uint64_t seed, int32_t rep_lo,
+                                                           int32_t num_boot, int32_t chunks, int64_t ld, double *__restrict__ out_corr,
+                                                           const int64_t *__restrict__ slot_list, int64_t n_list) {
+  boot2d_fast_body<true>(pk_, lq_, v1_, v2_, a, b, tile_ptr, n_slots, slot_K, slot_nobs, slot_omq, slot_row, slot_key, seed, rep_lo,
+                         num_boot, chunks, ld, out_corr, nullptr, 0, slot_list, n_list);
 }
 
 // mm_debug_inversion_ladder: the guarded fp32 inversion search of thread i's (U, n, p) through both forms of its ladder -- form 0 the
@@ -1201,6 +1239,28 @@ int mm_boot2d_fast_range(const double *d_pk, const double *d_lq, const double *d
   if (int rc = fast_grid((waves + 3) / 4, &grid)) return rc;
   hipLaunchKernelGGL(k_boot2d_fast, grid, dim3(256), 0, (hipStream_t)stream, d_pk, d_lq, d_v1, d_v2, d_a, d_b, d_tile_ptr, n_slots, d_slot_K,
                      d_slot_nobs, d_slot_omq, d_slot_row, d_slot_key, seed, rep_lo, rep_n, chunks, ld, d_out_corr, d_w_dump, kmax_dump);
+  MM_LAUNCH_CHECK();
+  return MM_OK;
+}
+
+int mm_boot2d_fast_slots(const double *d_pk, const double *d_lq, const double *d_v1, const double *d_v2, const double *d_a,
+                         const double *d_b, const int64_t *d_tile_ptr, int64_t n_slots, const int32_t *d_slot_K,
+                         const double *d_slot_nobs, const double *d_slot_omq, const int64_t *d_slot_row, const int64_t *d_slot_key,
+                         uint64_t seed, int32_t rep_lo, int32_t rep_n, int64_t ld, double *d_out_corr, const int64_t *d_slot_list,
+                         int64_t n_list, void *stream) {
+  MM_ARG(d_pk && d_lq && d_v1 && d_v2 && d_a && d_b && d_tile_ptr && d_slot_K && d_slot_nobs && d_slot_omq && d_slot_row && d_slot_key);
+  MM_ARG(d_out_corr && n_slots >= 0 && n_slots % 64 == 0 && rep_n > 0 && ld >= (int64_t)rep_n + 1);
+  MM_ARG(rep_lo >= 0 && (int64_t)rep_lo + rep_n <= 2147483647LL);
+  MM_ARG(n_list >= 0 && (d_slot_list || n_list == 0));
+  if (n_list == 0 || n_slots == 0) return MM_OK;
+  int32_t chunks = (int32_t)(((int64_t)rep_n + 63) / 64);
+  MM_ARG(n_list <= INT64_MAX / chunks);
+  int64_t waves = n_list * chunks;
+  dim3 grid;
+  if (int rc = fast_grid((waves + 3) / 4, &grid)) return rc;
+  hipLaunchKernelGGL(k_boot2d_fast_slots, grid, dim3(256), 0, (hipStream_t)stream, d_pk, d_lq, d_v1, d_v2, d_a, d_b, d_tile_ptr, n_slots,
+                     d_slot_K, d_slot_nobs, d_slot_omq, d_slot_row, d_slot_key, seed, rep_lo, rep_n, chunks, ld, d_out_corr, d_slot_list,
+                     n_list);
   MM_LAUNCH_CHECK();
   return MM_OK;
 }

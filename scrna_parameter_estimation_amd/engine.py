@@ -1590,9 +1590,23 @@ class Bootstrap2D:
         left out.  Replicate rep_lo + i of a chain is bit for bit the one a one-shot ``run`` over more replicates stores in column
         1 + rep_lo + i.  ``dump_weights``: keep the int32 weights in ``self.w_dump_range`` [slot][k][i] (slot =
         ``self.pair_slot[q]``)."""
+        return self._launch_range(rep_lo, rep_n, open_q, plane, row_of_q, dump_weights, False)
+
+    def launch_listed(self, rep_lo, rep_n, open_q, plane, row_of_q, dump_weights=False):
+        """``launch_range`` with a grid over the chains it is given: the launch covers only the slots of ``open_q``
+        (mm_boot2d_fast_slots on their ascending, unique list: len(list) x ceil(rep_n / 64) waves instead of one wave per slot of
+        the layout and 64 replicates) and only their entries of the slot-row table are written -- a table the chunk keeps from its
+        first listed launch on, whose other entries no listed launch reads.  Same checks, and the cells written are those of
+        ``launch_range``, bit for bit.  There is no weight dump: ``dump_weights`` raises.  Returns the device arrays the launch
+        reads, to be kept like ``launch_range``'s."""
+        return self._launch_range(rep_lo, rep_n, open_q, plane, row_of_q, dump_weights, True)
+
+    def _launch_range(self, rep_lo, rep_n, open_q, plane, row_of_q, dump_weights, listed):
         torch, f = _torch(), getattr(self, "_fast", None)
         if f is None:
             raise RuntimeError("launch_range needs a preceding run(fast=True, keep_fast=True): nothing else keeps the operands and the streams")
+        if listed and dump_weights:
+            raise ValueError("launch_listed has no weight dump")
         rep_lo, rep_n = int(rep_lo), int(rep_n)
         if rep_lo < 0 or rep_n < 1 or rep_lo + rep_n > 2 ** 31 - 1:
             raise ValueError("launch_range: need rep_lo >= 0, rep_n >= 1 and rep_lo + rep_n <= 2^31 - 1")
@@ -1605,6 +1619,22 @@ class Bootstrap2D:
         if len(row_of_q) and (row_of_q.min() < 0 or row_of_q.max() >= plane.shape[0]):
             raise ValueError("launch_range: row out of range")       # (the kernel trusts the rows)
         slot = f.pair_slot[open_q]
+        if listed:
+            has = slot >= 0
+            by_slot = np.argsort(slot[has], kind="stable")
+            slots, rows = slot[has][by_slot].astype(np.int64), row_of_q[has][by_slot]
+            last = np.append(slots[1:] != slots[:-1], True)[:len(slots)]      # a chain given twice: its last row, as in the default launch
+            slots, rows = slots[last], rows[last]
+            if len(slots) and (slots[0] < 0 or slots[-1] >= f.n_slots):
+                raise ValueError("launch_range: slot out of range")       # (the kernel trusts the list)
+            if getattr(f, "d_slot_row", None) is None:
+                f.d_slot_row = torch.full((max(1, f.n_slots),), -1, dtype=torch.int64, device="cuda")
+            d_list, d_rows = _up(slots), _up(rows)
+            if len(slots):
+                f.d_slot_row[d_list] = d_rows
+            _lib.call("mm_boot2d_fast_slots", *map(P, f.ops), P(f.d_tile_ptr), f.n_slots, P(f.d_slot_K), P(f.d_nobs), P(f.d_omq),
+                      P(f.d_slot_row), P(f.d_slot_key), f.seed, rep_lo, rep_n, plane.shape[1], P(plane), P(d_list), len(slots), _stream())
+            return d_list, d_rows      # NB: stay referenced until the caller's next call on the stream
         slot_row = np.full(f.n_slots, -1, dtype=np.int64)
         slot_row[slot[slot >= 0]] = row_of_q[slot >= 0]
         d_slot_row = dev(slot_row)

@@ -160,8 +160,8 @@ def _mix64(x):
 
 
 def check_sequential(max_boot, min_extreme, num_boot, rng, approx, ci):
-    """The ``max_boot`` / ``min_extreme`` keywords of ``ht_1d_vs_control`` and ``ht_2d_moments``; pure, runs before ``adata`` is touched.  -> whether
-    the call is sequential (``max_boot`` given)."""
+    """The ``max_boot`` / ``min_extreme`` keywords of ``ht_1d_vs_control``, ``ht_2d_moments`` and ``ht_2d_vs_control_sequential``; pure, runs before
+    ``adata`` is touched.  -> whether the call is sequential (``max_boot`` given)."""
     if max_boot is None:
         return False
 
@@ -614,40 +614,155 @@ def continue_chunk_2d(c, ng, test_pair, W, good, stats, schedule, min_extreme, r
     a round with more takes its open pairs in sub-batches (pairs are independent, and the streams are keyed by chain, so neither
     this nor the chunking changes a number).  ``n_open`` [round]: the tests open after round j are added to entry j.
     -> the merged records."""
-    bs, torch = c.bs, engine._torch()
+    bs = c.bs
     test_pair, W, good = np.asarray(test_pair, dtype=np.int64), np.asarray(W, dtype=np.float64), np.asarray(good, dtype=bool)
-    merged = np.array(stats, dtype=np.float64)
     grp = np.arange(ng)
+
+    def batches(j, idx, ld):
+        pairs, per_pair = np.unique(test_pair[idx], return_counts=True)
+        per = int(min(len(pairs), max(1, (bs.n_q * bs.ld) // ((ng + int(per_pair.max())) * ld))))
+        subs = [pairs[lo:lo + per] for lo in range(0, len(pairs), per)]
+        return per * ng, [(np.flatnonzero(np.isin(test_pair[idx], psub)), psub) for psub in subs]
+
+    def run(plane, rep_lo, rep_n, tests, psub):
+        ld = 1 + rep_n
+        sub = plane[:len(psub) * ng]
+        rows_old = (psub[:, None] * ng + grp).reshape(-1)
+        sub.fill_(float("nan"))
+        sub[:, 0] = bs.yc[engine.dev(rows_old), 0]
+        g_sub = good[psub]
+        rows_new = np.flatnonzero(g_sub.reshape(-1))
+        keep = bs.launch_range(rep_lo, rep_n, rows_old[rows_new], sub, rows_new)
+        coef, new = engine.contract_plane(sub, ld, rep_n, ng, len(psub), np.searchsorted(psub, test_pair[tests]), W[tests], g_sub)
+        del keep, coef
+        return new
+
+    return _rounds_2d(stats, schedule, min_extreme, resampling, n_open, batches, run)
+
+
+def _rounds_2d(stats, schedule, min_extreme, resampling, n_open, batches, run, on_round=None):
+    """The round loop of the sequential 2D bootstrap, shared by its drivers (``continue_chunk_2d``, ``continue_chunk_2d_designs``):
+    before round j >= 1 the tests still open (``open_tests`` on the merged records) are counted into ``n_open[j - 1]``; none open
+    ends the rounds.  ``batches(j, idx, ld)`` -> (rows of the round's plane, [(positions into ``idx``, job)]) says how the open tests
+    ``idx`` are taken, ``run(plane, rep_lo, rep_n, tests, job)`` -> records [len(tests)][8] bootstraps and contracts one sub-batch
+    on the leading rows of ``plane`` [rows][1 + rep_n], which is allocated once per round and released before the next
+    (release-before-allocate); the round's records are folded by ``merge_records``.  ``on_round(j, is_open)`` sees every mask.
+    -> the merged records."""
+    torch = engine._torch()
+    merged = np.array(stats, dtype=np.float64)
     for j in range(1, len(schedule)):
         is_open = open_tests(merged, min_extreme, resampling)
         n_open[j - 1] += int(is_open.sum())
+        if on_round is not None:
+            on_round(j, is_open)
         if not is_open.any():
             break
         idx = np.flatnonzero(is_open)
         rep_lo, rep_n = schedule[j - 1], schedule[j] - schedule[j - 1]
-        ld = 1 + rep_n
-        pairs, per_pair = np.unique(test_pair[idx], return_counts=True)
-        per = int(min(len(pairs), max(1, (bs.n_q * bs.ld) // ((ng + int(per_pair.max())) * ld))))
-        plane = engine.empty((per * ng, ld), torch.float64)
+        n_rows, subs = batches(j, idx, 1 + rep_n)
+        plane = engine.empty((n_rows, 1 + rep_n), torch.float64)
         new = np.empty((len(idx), 8))
-        for lo in range(0, len(pairs), per):
-            psub = pairs[lo:lo + per]
-            sub = plane[:len(psub) * ng]
-            in_sub = np.isin(test_pair[idx], psub)
-            rows_old = (psub[:, None] * ng + grp).reshape(-1)
-            sub.fill_(float("nan"))
-            sub[:, 0] = bs.yc[engine.dev(rows_old), 0]
-            g_sub = good[psub]
-            rows_new = np.flatnonzero(g_sub.reshape(-1))
-            keep = bs.launch_range(rep_lo, rep_n, rows_old[rows_new], sub, rows_new)
-            coef, new[in_sub] = engine.contract_plane(sub, ld, rep_n, ng, len(psub), np.searchsorted(psub, test_pair[idx[in_sub]]),
-                                                      W[idx[in_sub]], g_sub)
-            del keep, coef
-        del plane, sub      # release-before-allocate: the next round's plane takes this buffer
+        for pos, job in subs:
+            new[pos] = run(plane, rep_lo, rep_n, idx[pos], job)
+        del plane      # release-before-allocate: the next round's plane takes this buffer
         merged[idx] = merge_records([merged[idx], new])
     else:
         n_open[len(schedule) - 1] += int(open_tests(merged, min_extreme, resampling).sum())
     return merged
+
+
+def design_round_tables(test_pair, test_design, design_ptr, design_grp, design_w, ng):
+    """What a round of ``continue_chunk_2d_designs`` launches and contracts for the given (open) tests -- ``test_pair`` [test],
+    ``test_design`` [test] into the CSR tables (``design_ptr``, ``design_grp``, ``design_w``) -- as plain arrays; pure numpy.
+    -> ``chains``: the distinct q = pair * ng + group over the entries of the tests' designs, ascending (``_design_chains``): row i
+    of the round's compact plane is chain ``chains[i]``; ``ptr`` [test + 1], ``rows``, ``w``: one design PER TEST, whose entries
+    are those of the test's shared design in the same order, weights unchanged, the group replaced by the chain's plane row."""
+    design_ptr, design_grp, design_w = np.asarray(design_ptr, dtype=np.int64), np.asarray(design_grp, dtype=np.int64), np.asarray(design_w, dtype=np.float64)
+    test_pair, test_design = np.asarray(test_pair, dtype=np.int64).reshape(-1), np.asarray(test_design, dtype=np.int64).reshape(-1)
+    lo, cnt = design_ptr[test_design], np.diff(design_ptr)[test_design]
+    ptr = np.concatenate([[0], np.cumsum(cnt)]).astype(np.int64)
+    pos = np.repeat(lo - ptr[:-1], cnt) + np.arange(int(ptr[-1]))
+    q = np.repeat(test_pair, cnt) * ng + design_grp[pos]
+    chains, rows = np.unique(q, return_inverse=True)
+    return chains, ptr, np.asarray(rows, dtype=np.int64).reshape(-1), design_w[pos]
+
+
+def design_batches(test_pair, test_design, design_ptr, design_grp, ng, max_chains):
+    """Cut the given tests, in their order, into contiguous runs [(lo, hi)] whose designs read at most ``max_chains`` distinct
+    chains each (a single test that reads more is a run of its own), taking as many tests per run as fit; pure numpy.  The tests
+    of a driver are pair-major, so a pair's control chains are usually shared within one run."""
+    n = len(test_pair)
+    chains, ptr, rows, _ = design_round_tables(test_pair, test_design, design_ptr, design_grp, np.zeros(len(design_grp)), ng)
+    if len(chains) <= max_chains or n <= 1:
+        return [(0, n)] if n else []
+    test_of = np.repeat(np.arange(n), np.diff(ptr))
+    # prev[e]: the test of the previous entry on the same chain (-1: none); entry e adds a chain to a run from s on iff prev[e] < s
+    by_row = np.argsort(rows, kind="stable")
+    prev = np.full(len(rows), -1, dtype=np.int64)
+    same = rows[by_row][1:] == rows[by_row][:-1]
+    prev[by_row[1:][same]] = test_of[by_row[:-1][same]]
+    runs, s = [], 0
+    while s < n:
+        e0 = int(ptr[s])
+        seen = np.cumsum(prev[e0:] < s)                                # distinct chains of the entries e0..e
+        per_test = seen[ptr[s + 1:] - e0 - 1] if len(seen) else np.zeros(0, dtype=np.int64)
+        per_test = np.where(np.diff(ptr)[s:] > 0, per_test, 0)          # (an empty design reads nothing)
+        per_test = np.maximum.accumulate(per_test)
+        hi = s + max(1, int(np.searchsorted(per_test, max_chains, side="right")))
+        runs.append((s, hi))
+        s = hi
+    return runs
+
+
+def continue_chunk_2d_designs(c, ng, test_pair, test_design, tables, stats, schedule, min_extreme, resampling, n_open, n_chains=None,
+                              open_mask=None, budget=None):
+    """``continue_chunk_2d`` for tests given as (pair, design id) over CSR design tables ``tables`` = (design_ptr, design_grp,
+    design_w): the rounds of ``ht_2d_vs_control_sequential(max_boot=...)``, on an open pair chunk whose round 0 (``run_chunk_2d`` with
+    rng='fast' and ``keep_fast``, then ``bs.contrast`` / ``bs.contrast_design``) gave the records ``stats`` [test][8] of the tests
+    (``test_pair`` [test] in device pair order, pair-major).  Same round loop (``_rounds_2d``); what differs is the granularity.
+    Round j bootstraps exactly the chains that an open test's design reads -- the guide's groups and the control's, not every
+    group of the pair -- into a COMPACT plane [chain][1 + rep_n], one row per chain (``design_round_tables``; column 0 copied
+    from the chunk, everything else NaN until the launch writes it), by ONE ``bs.launch_listed``, whose grid is sized by
+    those chains and not by the chunk's tile layout.  A chain that did not run in round 0 is left out by the launch; its columns
+    are dropped by the contraction, as in the one-shot call.  The open tests are contracted by mm_contrast_design1_stats with the
+    compact plane as ONE row block of ``len(chains)`` groups and one design per test (the shared design's entries in the same
+    order and with the same weights, the group replaced by the plane row), so every coefficient is the same sum in the same order
+    as in round 0 and the counts of a test that never closes are those of the one-shot call over ``schedule[-1]`` replicates.
+    ``budget`` (doubles; default the chunk's own replicate rows, ``bs.n_q * bs.ld``): a round whose plane would be larger takes
+    its open tests in sub-batches, contiguous runs in pair-major order (``design_batches``); the streams are keyed by chain, so
+    neither this nor the chunking changes a number (a chain shared by two runs is bootstrapped in both, to the same values).
+    ``n_open`` [round] as in ``continue_chunk_2d``; diagnostics: ``n_chains`` [round]: the distinct chains that the open tests of
+    round j read are added to entry j; ``open_mask`` [round]: entry j is set to the open mask [test] before round j.
+    -> the merged records."""
+    bs = c.bs
+    design_ptr, design_grp, design_w = (np.asarray(a) for a in tables)
+    test_pair, test_design = np.asarray(test_pair, dtype=np.int64), np.asarray(test_design, dtype=np.int64)
+    budget = bs.n_q * bs.ld if budget is None else int(budget)
+
+    def on_round(j, is_open):
+        if open_mask is not None:
+            open_mask[j] = is_open.copy()
+
+    def batches(j, idx, ld):
+        runs = design_batches(test_pair[idx], test_design[idx], design_ptr, design_grp, ng, max(1, budget // ld))
+        jobs = [design_round_tables(test_pair[idx[lo:hi]], test_design[idx[lo:hi]], design_ptr, design_grp, design_w, ng) for lo, hi in runs]
+        if n_chains is not None:
+            n_chains[j] += len(jobs[0][0]) if len(jobs) == 1 else len(_design_chains(test_pair[idx], test_design[idx], design_ptr, design_grp, ng))
+        return max(1, max(len(job[0]) for job in jobs)), [(np.arange(lo, hi), job) for (lo, hi), job in zip(runs, jobs)]
+
+    def run(plane, rep_lo, rep_n, tests, job):
+        chains, ptr, rows, w = job
+        sub = plane[:max(1, len(chains))]
+        sub.fill_(float("nan"))
+        if len(chains):
+            sub[:len(chains), 0] = bs.yc[engine.dev(chains), 0]
+        keep = bs.launch_listed(rep_lo, rep_n, chains, sub, np.arange(len(chains)))
+        (new,), _ = engine._contrast_design([sub], 1 + rep_n, rep_n, max(1, len(chains)), 1, np.zeros(len(tests), dtype=np.int32),
+                                            np.arange(len(tests)), ptr, rows, w)
+        del keep
+        return new
+
+    return _rounds_2d(stats, schedule, min_extreme, resampling, n_open, batches, run, on_round)
 
 
 def scatter_pairs(c, plan, dst, src, keep=None):

@@ -1196,25 +1196,75 @@ def ht_2d_vs_control(adata, control, num_boot=10000, num_cpus=1, fill_seed=0, ma
 
     ``ci`` as in ``ht_1d_vs_control``: adds the columns ``corr_ci_lo, corr_ci_hi`` and ``corr_ci`` [test][2] and ``ci`` to ``uns``.
 
+    The sequential bootstrap of these tests (``max_boot``) is ``ht_2d_vs_control_sequential``, of which this call is the case
+    without ``max_boot``: the parameter list of this one is pinned.
+
+    Returns a DataFrame (gene_1, gene_2, group, corr_coef, corr_se, corr_pval), pair-major, one row per (requested pair,
+    tested guide), and stores the arrays in ``uns['memento']['2d_ht_vs_control']``."""
+    return ht_2d_vs_control_sequential(adata, control, num_boot, num_cpus, fill_seed, max_rows, approx, resampling, rng,
+                                       treatment_col=treatment_col, ci=ci)
+
+
+def ht_2d_vs_control_sequential(adata, control, num_boot=10000, num_cpus=1, fill_seed=0, max_rows=None, approx=False,
+                                resampling='bootstrap', rng='replay', *, treatment_col=None, ci=None, max_boot=None, min_extreme=10):
+    """``ht_2d_vs_control`` with the sequential bootstrap: the same parameters, tests, result and ``uns`` entry
+    (``'2d_ht_vs_control'``), and two more keywords; without ``max_boot`` it IS that call.
+
+    ``max_boot`` / ``min_extreme`` (keyword-only; ``max_boot`` needs ``rng='fast'``, ``approx=False``, ``ci=None``): the sequential
+    bootstrap of ``ht_1d_vs_control`` on the (pair, guide) tests.  Round 0 is the plain call -- the same launches, keys and records
+    -- and only the tests whose extreme count is still <= ``min_extreme`` go on, to the cumulative totals ``num_boot``,
+    ``2 num_boot``, ..., ``max_boot`` (``_ht.sequential_schedule``).  A round bootstraps exactly the chains that an open test's
+    design reads (the guide's groups and the control's, not every group of the pair) into a compact plane of one row per chain,
+    with a launch over the list of those chains (mm_boot2d_fast_slots), and contracts the open tests only
+    (``_ht.continue_chunk_2d_designs``).  The streams are keyed by (``fill_seed``, pair, group, replicate) and the 2D path refills
+    nothing, so a test that is never closed has exactly the valid / extreme counts of the one-shot ``num_boot=max_boot`` call,
+    whatever ``max_rows`` is.  ``corr_pval`` is ``(c + 1) / (n + 1)`` over all rounds for every test, with NO tail fit; ``corr_se``
+    comes from the merged record (``_ht.merge_records``); ``corr_coef`` is untouched.  Adds the column ``corr_nboot`` (the valid
+    replicates behind each p-value, 0 where there is no test) and ``corr_nboot``, ``max_boot``, ``min_extreme`` to ``uns``.
+
     Returns a DataFrame (gene_1, gene_2, group, corr_coef, corr_se, corr_pval), pair-major, one row per (requested pair,
     tested guide), and stores the arrays in ``uns['memento']['2d_ht_vs_control']``."""
     _ht.check_args(rng, resampling=resampling)
+    sequential = _ht.check_sequential(max_boot, min_extreme, num_boot, rng, approx, ci)
     probs = _ht.ci_probs(ci)
     m = adata.uns['memento']
     st = m['_hip']
-    st.last_bootstrap2d = None                 # (free the previous call's replicate rows before this call allocates its own)
+    st.last_bootstrap2d = None                # (free the previous call's replicate rows before this call allocates its own)
     tested, designs, (ctrl, others), meta = _vs_control_plan(m, control, treatment_col)
     n_t = len(tested)
     plan = _ht.pair_plan(m, st, num_boot, max_rows)
     uniforms = _ht.hash_uniforms(~plan.skip.reshape(-1), 3)
     out = {k: np.full((plan.n_conv, n_t), np.nan) for k in ('corr_coef', 'corr_se', 'corr_asl')}
     corr_ci = np.full((plan.n_conv, n_t * 2), np.nan) if probs is not None else None
+    if sequential:
+        out['corr_nboot'] = np.zeros((plan.n_conv, n_t), dtype=np.int64)
+        schedule = _ht.sequential_schedule(num_boot, max_boot)
+        # (diagnostics: tests open after each round; chains bootstrapped per round; the last chunk's open mask before each round)
+        seq = st.last_sequential = SimpleNamespace(schedule=schedule, n_open=[0] * len(schedule), n_chains=[0] * len(schedule), open_mask=None)
+        two_group = _ht._TwoGroupDesigns(plan.ng, ctrl) if designs is None else None
 
     def run_chunk(c):
-        good = _ht.run_chunk_2d(c, plan, uniforms, rng, fill_seed)                 # device order
+        good = _ht.run_chunk_2d(c, plan, uniforms, rng, fill_seed, keep_fast=sequential)   # device order
         test_pair = np.repeat(np.arange(c.n_ch), n_t)     # pair-major: a pair's control rows stay in L2 for its consecutive guides
+        test_design = None if designs is None else designs.tests(good)
         stt, rows = (c.bs.contrast(test_pair, np.tile(others, c.n_ch), ctrl, good) if designs is None
-                     else c.bs.contrast_design(test_pair, designs.tests(good), *designs.tables()))
+                     else c.bs.contrast_design(test_pair, test_design, *designs.tables()))
+        if sequential:
+            del rows
+            if designs is None:      # (the designs ``bs.contrast`` builds are those of _TwoGroupDesigns)
+                test_design = two_group.tests(good)
+            seq.n_chains[0] += int(c.bs.active.sum())
+            seq.open_mask = [np.ones(len(test_pair), dtype=bool)] + [None] * (len(schedule) - 1)
+            stt = st.last_records2d = _ht.continue_chunk_2d_designs(
+                c, plan.ng, test_pair, test_design, (two_group if designs is None else designs).tables(), stt, schedule, min_extreme,
+                resampling, seq.n_open, seq.n_chains, seq.open_mask)
+            with np.errstate(invalid="ignore"):
+                nboot = np.where(np.isnan(stt[:, 0]) | np.isnan(stt[:, 2]), 0, stt[:, 2]).astype(np.int64)
+            for key, src in (('corr_coef', stt[:, 0]), ('corr_se', stt[:, 1]), ('corr_asl', _ht.sequential_pvalues(stt, resampling)),
+                             ('corr_nboot', nboot)):
+                _ht.scatter_pairs(c, plan, out[key], src)
+            return
+        st.last_records2d = stt                # (diagnostics / tests: the test records of the last pair chunk, device pair order)
         pvals = _asl.asl_from_stats(stt, approx, rows, num_cpus, resampling)
         for key, src in (('corr_coef', stt[:, 0]), ('corr_se', stt[:, 1]), ('corr_asl', pvals)):
             _ht.scatter_pairs(c, plan, out[key], src)
@@ -1227,6 +1277,8 @@ def ht_2d_vs_control(adata, control, num_boot=10000, num_cpus=1, fill_seed=0, ma
     m['2d_ht_vs_control'] = dict(out, **meta)
     if probs is not None:
         m['2d_ht_vs_control'].update(corr_ci=corr_ci.reshape(-1, 2), ci=float(ci))
+    if sequential:
+        m['2d_ht_vs_control'].update(max_boot=int(max_boot), min_extreme=int(min_extreme))
     n_conv = plan.n_conv
     pairs = list(m['2d_moments']['gene_pairs'])
     df = pd.DataFrame({'gene_1': np.repeat([a for a, _ in pairs], n_t), 'gene_2': np.repeat([b for _, b in pairs], n_t),
@@ -1234,6 +1286,8 @@ def ht_2d_vs_control(adata, control, num_boot=10000, num_cpus=1, fill_seed=0, ma
     df['corr_coef'], df['corr_se'], df['corr_pval'] = out['corr_coef'], out['corr_se'], out['corr_asl']
     if probs is not None:
         _ci_columns(df, ('corr', m['2d_ht_vs_control']['corr_ci']))
+    if sequential:
+        df['corr_nboot'] = out['corr_nboot']
     return df
 
 
