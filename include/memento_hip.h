@@ -290,9 +290,15 @@ int mm_boot1d_async(const double *d_ops, const int64_t *d_ch_base, const int32_t
  * number of slots in the tile layout written by mm_bins_order (64 * n_tiles); d_slot_K[s] < 2 or d_slot_row[s] < 0 = nothing is
  * written.  Replicate r of slot s owns the PCG64 stream derived from (seed, d_slot_key[s], r) -- d_slot_row[s] addresses the output
  * row only: keys that number the chains independently of gene chunking, sharding and layout make the result independent of all
- * three.  Same sampler code and moment arithmetic as the replay kernel, different random numbers: statistically equivalent to
- * the reference, not draw-for-draw identical.  d_w_dump (optional, NULL in production): int32 weights
- * [slot][k < kmax_dump][r < num_boot]. */
+ * three.  The stream rule is part of the contract (restated in numpy in tests/_fast_ref.py): with mix64 the splitmix64 output
+ * function, key = (uint64_t)d_slot_key[s] and everything mod 2^64,
+ *     h = mix64(seed ^ mix64(key * 0x100000001B3 + r))
+ *     state = (mix64(h), mix64(h + 1))     increment = (mix64(h + 2), mix64(h + 3) | 1)          (high word, low word)
+ * is a plain PCG64 (the XSL-RR 128/64 generator of numpy), and the weights of replicate r are, draw for draw, what numpy's
+ * Generator(PCG64 set to that state and increment).multinomial(n, multiplicities / n) returns.  Same sampler code and moment
+ * arithmetic as the replay kernel: the draws are not those of the reference's single stream PCG64(seed) -- the results are
+ * statistically equivalent to the reference's -- but they are numpy's own on the stated per-replicate stream.
+ * d_w_dump (optional, NULL in production): int32 weights [slot][k < kmax_dump][r < num_boot]. */
 int mm_boot1d_fast(const double *d_pk, const double *d_lq, const double *d_v, const double *d_a, const double *d_b,
                    const int64_t *d_tile_ptr, int64_t n_slots, const int32_t *d_slot_K, const double *d_slot_nobs,
                    const double *d_slot_omq, const int64_t *d_slot_row, const int64_t *d_slot_key, uint64_t seed, int32_t num_boot,
@@ -305,9 +311,9 @@ int mm_boot1d_fast(const double *d_pk, const double *d_lq, const double *d_v, co
  * rep_lo = 0, rep_n = num_boot of the same kernel, so replicates [rep_lo, rep_lo + rep_n) made later, for some of the chains,
  * are bit for bit those of a one-shot launch over [0, rep_lo + rep_n).
  *   - rep_lo >= 0, rep_n >= 1 and rep_lo + rep_n <= 2^31 - 1.
- *   - The stream seed is a function of key * 0x100000001B3 + r (mod 2^64): distinct (key, r) with 0 <= r < 0x100000001B3, the key
- *     multiplier, and keys below 2^64 / 0x100000001B3 give distinct values, so no replicate range of one chain collides with a
- *     range of another chain.
+ *   - The stream seed is a function of key * 0x100000001B3 + r (mod 2^64): distinct (key, r) with 0 <= r < 2^31 (below the key
+ *     multiplier 0x100000001B3) and 0 <= key < 2^64 / 0x100000001B3 (= 2^24 - 1 at most; the sum does not wrap there) give distinct
+ *     values, so no replicate range of one chain collides with a range of another chain.
  *   - A slot with d_slot_row[s] < 0 (or d_slot_K[s] < 2) writes nothing, as in mm_boot1d_fast: that is how the chains of closed
  *     tests are skipped without a new tile layout.
  *   - Column 0, the columns beyond rep_n and the rows of skipped slots are not written.
@@ -569,8 +575,13 @@ int mm_boot2d_replay_rec(const double *d_recs, const int64_t *d_slot_rec, int64_
  * from the six [row][64] operand planes mm_bins_order2d writes for plain tile slots (n_slots = 64 * n_tiles, slot s = 64 * tile +
  * lane; d_slot_K[s] <= 0 or d_slot_row[s] < 0 = unused).  Replicate r of slot s owns the PCG64 stream derived from
  * (seed, d_slot_key[s], r): keys that number the chains independently of chunking and layout make the result independent of both.
- * Same samplers and replicate arithmetic as mm_boot2d_replay, different random numbers: statistically equivalent to the
- * reference, not draw-for-draw identical.  d_w_dump (optional, NULL in production): int32 weights [slot][k < kmax_dump][r < num_boot]. */
+ * The stream rule is mm_boot1d_fast's and part of the contract (restated in numpy in tests/_fast_ref.py):
+ *     h = mix64(seed ^ mix64(key * 0x100000001B3 + r))
+ *     state = (mix64(h), mix64(h + 1))     increment = (mix64(h + 2), mix64(h + 3) | 1)          (high word, low word)
+ * a plain PCG64, on which the weights of replicate r are numpy's Generator.multinomial(n, multiplicities / n) draw for draw.
+ * Same samplers and replicate arithmetic as mm_boot2d_replay: the draws are not those of the reference's single stream -- the
+ * results are statistically equivalent to the reference's -- but they are numpy's own on the stated per-replicate stream.
+ * d_w_dump (optional, NULL in production): int32 weights [slot][k < kmax_dump][r < num_boot]. */
 int mm_boot2d_fast(const double *d_pk, const double *d_lq, const double *d_v1, const double *d_v2, const double *d_a,
                    const double *d_b, const int64_t *d_tile_ptr, int64_t n_slots, const int32_t *d_slot_K, const double *d_slot_nobs,
                    const double *d_slot_omq, const int64_t *d_slot_row, const int64_t *d_slot_key, uint64_t seed, int32_t num_boot,

@@ -669,8 +669,8 @@ __global__ __launch_bounds__(256) void k_boot_fill_log(double *__restrict__ mean
 // one wave = 64 replicates of ONE (gene, group) pair.  Every lane of a wave walks the same bins, so the
 // operands are wave-uniform, lanes take the same sampler (inversion or BTPE) at each step, and pairs x
 // replicates give the chip millions of independent chains.  Replicate r of the chain with key ``slot_key[slot]`` owns the
-// PCG64 stream derived from (seed, key, r) -- NOT numpy's single stream: results are statistically equivalent
-// to the reference (same algorithm, different random numbers), not draw-for-draw identical.  The caller's keys number the
+// PCG64 stream derived from (seed, key, r) (fast_stream) -- NOT the reference's single stream: results are statistically equivalent
+// to the reference, and draw for draw numpy's multinomial on that stream (tests/_fast_ref.py).  The caller's keys number the
 // (gene, group) chains independently of gene chunking, of sharding and of the tile layout, so none of them changes a result;
 // ``slot_row`` addresses the output row only.  The launch covers the ``num_boot`` replicates from global replicate ``rep_lo`` on
 // (mm_boot1d_fast: rep_lo = 0): local replicate i draws from the stream of replicate rep_lo + i and is stored in column 1 + i, so a

@@ -131,6 +131,17 @@ def menu():
 MENU_NAMES = ("k2", "k3_flip", "six_ones", "k64", "k65", "long600", "btpe12", "huge", "tail_tiny")
 
 
+def adhoc_chain(name, mult):
+    """A chain outside the menu, for ``layout``: the multiplicities as given, counts 0, 1, 2, ... and the size factors of SF8 in
+    turn (arbitrary operands for tests that compare weights)."""
+    mult = np.asarray(mult, dtype=np.int64)
+    K = len(mult)
+    sf_bin = np.arange(K) % len(SF8)
+    x = np.arange(K, dtype=np.int64)
+    return SimpleNamespace(name=name, mult=mult, K=K, N=int(mult.sum()), sf_bin=sf_bin, x=x, v=x.astype(np.float64), sf=SF8[sf_bin],
+                           r1=0.5, r0=0.5, q=Q2[0])
+
+
 def one_bin_chain():
     """The K == 1 chain of tile 4: every replicate of it is NaN (bootstrap.py:97-98)."""
     return SimpleNamespace(name="one_bin", mult=np.array([777], dtype=np.int64), K=1, N=777, sf_bin=np.array([2]), x=np.array([4]),
@@ -163,7 +174,8 @@ def full_tiles(with_long_twin=True, first=True):
 
 def layout(tiles, extra_rows=7, kmax_pad=3):
     """Host tables of a launch over ``tiles``: a list whose items are {lane: (kind, chain name)} (a tile) or a chain name (a tile
-    that is a chain of the record form: mm_chain_tiles).  Every chain's operands are written twice, into the five [rows][64]
+    that is a chain of the record form: mm_chain_tiles).  In a tile an ad-hoc chain (``adhoc_chain``) may stand in place of a
+    menu chain's name.  Every chain's operands are written twice, into the five [rows][64]
     planes and as 8-double records; cells nobody owns hold harmless finite operands (pk 0.25, v 1e6).  Rows are a permutation of
     the row owners plus ``extra_rows`` rows nothing addresses."""
     m = menu()
@@ -175,7 +187,7 @@ def layout(tiles, extra_rows=7, kmax_pad=3):
             continue
         for lane in sorted(tile):
             kind, name = tile[lane]
-            ch = m[name] if name else (one_bin_chain() if kind == "k1" else None)
+            ch = (m[name] if isinstance(name, str) else name) if name is not None else (one_bin_chain() if kind == "k1" else None)
             ents.append(SimpleNamespace(tile=t, lane=lane, slot=t * 64 + lane, kind=kind, chain=ch))
     owners = [e for e in ents if e.kind != "norow"]
     n_rows = len(owners) + extra_rows

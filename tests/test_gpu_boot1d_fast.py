@@ -5,10 +5,12 @@ Bootstrap1D.run(fast=True, chain_keys=...), and ht_1d_moments / ht_1d_vs_control
 The kernel problem follows test_gpu_boot2d_fast: groups of 17,003 (three count blocks) / 8,192 / 300 / 6 cells plus ungrouped
 cells, 150 genes, 30 size-factor bins, the 6-cell group in one size-factor bin (chains with K == 1), two highly expressed genes
 (chains of several hundred bins), a never-expressed gene (one bin per occupied size-factor bin), a gene expressed in one group
-only and a gene that is a copy of another (equal operands).  The fast streams are not numpy's, so nothing is compared draw for
-draw: the kernel's arithmetic is checked against the oracle's formulas in extended precision on the kernel's OWN dumped weights,
-the weights against the multinomial law, and the keys against the promise that they -- not the rows, the chunks or the shards --
-decide the numbers.
+only and a gene that is a copy of another (equal operands).  Replicate r of the chain with key k draws from the PCG64 stream
+fast_state(fill_seed, k, r) of tests/_fast_ref.py, so the dumped weights of the really ingested chains are compared draw for draw
+with numpy's own multinomial on that stream (part (e); the kernel on synthetic planes: tests/test_gpu_fast_draws.py).  Beside that
+the kernel's arithmetic is checked against the oracle's formulas in extended precision on the kernel's OWN dumped weights, the
+weights against the multinomial law (a guard of the statistics should the stream rule ever be changed on purpose), and the keys
+against the promise that they -- not the rows, the chunks or the shards -- decide the numbers.
 """
 
 import os
@@ -330,6 +332,58 @@ def test_chain_keys_not_rows_decide_the_numbers(eng, prob, dev_blocks):
         assert keyed or n_diff >= 3
     with pytest.raises(ValueError):
         _run(whole, chain_keys=np.arange(n - 1))
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# (e) the engine's weights are numpy's, draw for draw, on the stated streams
+# ------------------------------------------------------------------------------------------------------------------------
+
+
+def test_engine_weights_are_numpys_on_the_stated_streams(eng, orc, prob, dev_blocks):
+    """Bootstrap1D.run(fast=True, dump_weights=True) on the chains of KEY_GENES, B = 130, with the default keys (the row numbers)
+    under fill_seed 3 and with chain_keys (2^40 and a negative key among them) under fill_seed 0xDEADBEEF12345678: weights_of(p)
+    of EVERY active chain equals fast_weights(bins of p in replay order, fill_seed, key of p, arange(B)).  Then launch_range on
+    [64, 134) and on the last 70 replicates below 2^31 - 1, a third of the chains closed: w_dump_range equals fast_weights on
+    rep_lo + arange(rep_n), and the closed chains dump nothing."""
+    from _fast_ref import fast_weights
+
+    torch = eng._torch()
+    B, ng = 130, prob.ng
+    bt = _boot(eng, prob, dev_blocks, KEY_GENES, B)
+    bs = bt.bs
+    n = bs.n_pairs
+    custom = 7000 + 11 * np.arange(n, dtype=np.int64)
+    custom[0], custom[1], custom[2] = 2 ** 40, -3, 0
+    bins, checked = {}, 0
+    for keys, seed in ((None, 3), (custom, 0xDEADBEEF12345678)):
+        _run(bt, fill_seed=seed, chain_keys=keys)
+        key_of = np.arange(n) if keys is None else keys
+        act = np.flatnonzero(bs.active)
+        assert len(act) >= 30 and (bs.K[act] >= 50).sum() >= 6 and {0, 1, 2} <= set(act.tolist())
+        for p in act:
+            if p not in bins:
+                bins[p] = _chain_bins(eng, orc, prob, bt, p)[0][3].astype(np.int64)
+            np.testing.assert_array_equal(bs.weights_of(p), fast_weights(bins[p], seed, int(key_of[p]), np.arange(B)),
+                                          err_msg=f"chain {p} (K = {bs.K[p]}), key {key_of[p]}, seed {seed:#x}")
+            checked += bins[p].size * B
+    closed = np.arange(n) % 3 == 1
+    open_pairs = np.flatnonzero(~closed)
+    for rep_lo, rep_n in ((64, 70), (2 ** 31 - 1 - 70, 70)):
+        planes = [torch.full((n, rep_n + 1), float("nan"), dtype=torch.float64, device="cuda") for _ in range(2)]
+        keep = bs.launch_range(rep_lo, rep_n, open_pairs, planes, open_pairs, dump_weights=True)
+        wr = eng.host(bs.w_dump_range)
+        del keep
+        for p in np.flatnonzero(bs.active):
+            K, slot = int(bs.K[p]), int(bs.tile_slot[p])
+            if closed[p]:
+                assert (wr[slot] == 0).all(), p
+                continue
+            want = fast_weights(bins[p], seed, int(custom[p]), rep_lo + np.arange(rep_n))
+            np.testing.assert_array_equal(wr[slot, :K], want, err_msg=f"chain {p}, replicates from {rep_lo}")
+            if rep_lo == 64:
+                np.testing.assert_array_equal(want[:, :B - 64], bs.weights_of(p)[:, 64:])
+            checked += want.size
+    print(f"\n{checked} weights of really ingested chains equal numpy's on the fast streams")
 
 
 # ------------------------------------------------------------------------------------------------------------------------

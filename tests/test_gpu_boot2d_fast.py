@@ -5,9 +5,12 @@ ht_2d_moments / ht_2d_vs_control(rng='fast').
 The kernel problem follows test_gpu_kernels_2d: groups of 17,003 (three count blocks) / 8,192 / 300 / 6 cells, 150 genes, the
 6-cell group in one size-factor bin (chains with K == 1), and a pair list with two highly expressed genes (chains of thousands
 of bins, ordered on the host), a never-expressed gene (zero variance: the 5.0 sentinel), a duplicated pair and a pair with its
-reverse.  The fast streams are not numpy's, so nothing is compared draw for draw: the kernel's arithmetic is checked against the
-oracle's formulas on the kernel's OWN dumped weights, the weights against the multinomial law, and the API against the replay
-mode (the parent's kernel, the yardstick) at the Monte-Carlo error of two independent bootstraps.
+reverse.  Replicate r of the chain with key k draws from the PCG64 stream fast_state(fast_seed, k, r) of tests/_fast_ref.py, so the
+dumped weights of the really ingested chains are compared draw for draw with numpy's own multinomial on that stream (part 2b; the
+kernels on synthetic planes: tests/test_gpu_fast_draws.py).  Beside that the kernel's arithmetic is checked against the oracle's
+formulas on the kernel's OWN dumped weights, the weights against the multinomial law (a guard of the statistics should the stream
+rule ever be changed on purpose), and the API against the replay mode (the parent's kernel, the yardstick) at the Monte-Carlo
+error of two independent bootstraps.
 """
 
 import contextlib
@@ -232,6 +235,64 @@ def test_weights_are_multinomial_and_streams_distinct(eng, orc, prob, dev_cols):
             n_twins += 1
     assert n_twins == 6
     assert z_max < 5, z_max
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# 2b. the engine's weights are numpy's, draw for draw, on the stated streams
+# ------------------------------------------------------------------------------------------------------------------------
+
+
+def test_engine_weights_are_numpys_on_the_stated_streams(eng, orc, prob, dev_cols):
+    """Bootstrap2D.run(fast=True, dump_weights=True, keep_fast=True) on the chains of Z_PAIRS, B = 130, with the default keys (q)
+    under fast_seed 3 and with pair_key (2^40 and a negative key among them) under fast_seed 0xDEADBEEF12345678: weights_of(q) of
+    EVERY active chain equals fast_weights(bins of q in replay order, fast_seed, key of q, arange(B)).  Then launch_range on
+    [64, 134) and on the last 70 replicates below 2^31 - 1, a third of the chains closed: w_dump_range equals fast_weights on
+    rep_lo + arange(rep_n), the closed chains dump nothing, and launch_listed (which has no dump) writes launch_range's plane."""
+    from _fast_ref import fast_weights
+
+    torch = eng._torch()
+    B = 130
+    bt = _boot(eng, orc, prob, dev_cols, Z_PAIRS, B, 78)
+    bs = bt.bs
+    n = bs.n_q
+    custom = 7000 + 11 * np.arange(n, dtype=np.int64)
+    custom[0], custom[1], custom[2] = 2 ** 40, -3, 0
+    bins, checked = {}, 0
+    for keys, seed in ((None, 3), (custom, 0xDEADBEEF12345678)):
+        bs.run(bt.skip, bt.ra, bt.rb, bt.r0, bt.true_corr, fast=True, fast_seed=seed, pair_key=keys, dump_weights=True, keep_fast=True)
+        key_of = np.arange(n) if keys is None else keys
+        act = np.flatnonzero(bs.active)
+        assert len(act) >= 3 * len(Z_PAIRS) and (bs.K[act] >= 50).sum() >= 10 and {0, 1, 2} <= set(act.tolist())
+        for q in act:
+            if q not in bins:
+                bins[q] = np.asarray(_chain_bins(orc, prob, bt, q)[0][4]).astype(np.int64)
+            assert len(bins[q]) == bs.K[q]
+            np.testing.assert_array_equal(bs.weights_of(q), fast_weights(bins[q], seed, int(key_of[q]), np.arange(B)),
+                                          err_msg=f"chain {q} (K = {bs.K[q]}), key {key_of[q]}, seed {seed:#x}")
+            checked += bins[q].size * B
+    closed = np.arange(n) % 3 == 1
+    open_q = np.flatnonzero(~closed)
+    for rep_lo, rep_n in ((64, 70), (2 ** 31 - 1 - 70, 70)):
+        plane = torch.full((n, rep_n + 1), float("nan"), dtype=torch.float64, device="cuda")
+        keep = bs.launch_range(rep_lo, rep_n, open_q, plane, open_q, dump_weights=True)
+        wr = eng.host(bs.w_dump_range)
+        del keep
+        for q in np.flatnonzero(bs.active):
+            K, slot = int(bs.K[q]), int(bs.pair_slot[q])
+            if closed[q]:
+                assert (wr[slot] == 0).all(), q
+                continue
+            want = fast_weights(bins[q], seed, int(custom[q]), rep_lo + np.arange(rep_n))
+            np.testing.assert_array_equal(wr[slot, :K], want, err_msg=f"chain {q}, replicates from {rep_lo}")
+            if rep_lo == 64:
+                np.testing.assert_array_equal(want[:, :B - 64], bs.weights_of(q)[:, 64:])
+            checked += want.size
+        listed = torch.full((n, rep_n + 1), float("nan"), dtype=torch.float64, device="cuda")
+        keep = bs.launch_listed(rep_lo, rep_n, open_q, listed, open_q)
+        np.testing.assert_array_equal(eng.host(listed.view(torch.int64)), eng.host(plane.view(torch.int64)))
+        assert np.isfinite(eng.host(plane)[open_q[bs.active[open_q]], 1:]).all()
+        del keep
+    print(f"\n{checked} weights of really ingested chains equal numpy's on the fast streams")
 
 
 # ------------------------------------------------------------------------------------------------------------------------
