@@ -395,6 +395,30 @@ int mm_cross_resampled(const double *d_yt, int64_t ld, int32_t num_boot, int32_t
                        const double *d_tt, const uint8_t *d_good, const double *d_Nc, const int16_t *d_rep, const int32_t *d_bcol,
                        const int32_t *d_col_map, const int32_t *d_n_valid, uint64_t seed, int64_t n_tests, double *d_coef,
                        double *d_stats, void *stream);
+/* mm_cross_resampled with a KEY per gene: d_gene_key [n_genes] (int64) replaces g in the draw rule above,
+ *   h = mix(seed ^ mix((key << 32) ^ (i << 24) ^ c)),
+ * so that the draws of a gene do not depend on the slot it has in a chunk of genes (keys below 2^32 stay apart); NULL = the slot,
+ * which is mm_cross_resampled itself. */
+int mm_cross_resampled_keyed(const double *d_yt, int64_t ld, int32_t num_boot, int32_t n_groups, const int32_t *d_test_gene,
+                             const double *d_tt, const uint8_t *d_good, const double *d_Nc, const int16_t *d_rep, const int32_t *d_bcol,
+                             const int32_t *d_col_map, const int32_t *d_n_valid, const int64_t *d_gene_key, uint64_t seed,
+                             int64_t n_tests, double *d_coef, double *d_stats, void *stream);
+/* mm_cross_resampled_block: the records of mm_cross_resampled_keyed for tests that arrive GENE-MAJOR (many cis SNPs per gene:
+ * analysis/lupus/run_memento.py:84-109), without the coefficient rows.  The tests of gene slot g are the rows
+ * [d_gene_ptr[g], d_gene_ptr[g + 1]) of d_tt [n_tests][n_groups]; d_gene_ptr [n_genes + 1] is a CSR pointer over the n_tests tests and
+ * max_gene_tests >= the largest number of tests of a gene (it sizes the launch: tests of a gene beyond it would get no record).
+ * Everything else -- d_good, d_Nc, d_rep / d_bcol (or NULL: device draws), d_col_map / d_n_valid, d_gene_key (or NULL: the slot),
+ * the draw rule with the key, the degenerate-column rule -- is as in mm_cross_resampled_keyed, and for every (test, column) the
+ * operations and their order are that kernel's: d_stats [n_tests][8] equals the record it writes for the same test, gene and key.
+ * A workgroup takes 8 consecutive tests of one gene and obtains every draw of a column once for all of them; nothing
+ * per replicate is stored (the record's second pass computes the coefficients again), so the call's memory is the records.  The
+ * rows of the few tests that need them come from mm_cross_resampled_keyed on that subset.  A gene without tests costs nothing; a
+ * gene without a good group, or with fewer than two surviving columns, gives NaN records.  LDS: 76 bytes per group (n_groups <= 860).
+ * The tables are trusted: validate them on the host (engine.cross_resampled_block). */
+int mm_cross_resampled_block(const double *d_yt, int64_t ld, int32_t num_boot, int32_t n_groups, const int32_t *d_gene_ptr,
+                             int64_t n_genes, int32_t max_gene_tests, const double *d_tt, const uint8_t *d_good, const double *d_Nc,
+                             const int16_t *d_rep, const int32_t *d_bcol, const int32_t *d_col_map, const int32_t *d_n_valid,
+                             const int64_t *d_gene_key, uint64_t seed, int64_t n_tests, double *d_stats, void *stream);
 
 /* ---- guide-vs-control contrasts: sparse weight rows over the replicate groups ------------------------------------
  * test t: coef_c = sum_p design_w[p] * y[test_gene[t], design_grp[p]][c] over p in [design_ptr[d], design_ptr[d + 1]),

@@ -264,6 +264,7 @@ __global__ __launch_bounds__(K9_THREADS) void k_cross_resampled(const double *__
                                                                 const uint8_t *__restrict__ good, const double *__restrict__ Nc,
                                                                 const int16_t *__restrict__ rep, const int32_t *__restrict__ bcol,
                                                                 const int32_t *__restrict__ col_map, const int32_t *__restrict__ n_valid,
+                                                                const int64_t *__restrict__ gene_key /* NULL: the gene's slot */,
                                                                 uint64_t seed, double *__restrict__ coef, double *__restrict__ stats) {
   extern __shared__ double sm[];
   double *tts = sm;                               // [ng]
@@ -299,6 +300,7 @@ __global__ __launch_bounds__(K9_THREADS) void k_cross_resampled(const double *__
   // surviving replicate columns (hypothesis_test.py:249-254): nb resampled columns, indices through col_map
   const int32_t *cm = col_map ? col_map + (int64_t)gene * (num_boot + 1) : nullptr;
   const int nb = n_valid ? n_valid[gene] - 1 : num_boot;
+  const uint64_t gk = gene_key ? (uint64_t)gene_key[gene] : (uint64_t)gene;
   if (nb < 1) {    // nothing (or only one column) survives: the reference returns NaNs ("skipped") or has no null at all
     for (int c = threadIdx.x; c <= num_boot; c += K9_THREADS) crow[c] = NAN;
     write_nan_record(st[0]);
@@ -313,7 +315,7 @@ __global__ __launch_bounds__(K9_THREADS) void k_cross_resampled(const double *__
       if (c == 0) { r = i; bb = 0; }
       else if (rg) { r = rg[(int64_t)i * num_boot + c]; bb = bg[(int64_t)i * num_boot + c]; }
       else {
-        uint64_t h = rr_mix(seed ^ rr_mix(((uint64_t)gene << 32) ^ ((uint64_t)i << 24) ^ (uint64_t)c));
+        uint64_t h = rr_mix(seed ^ rr_mix((gk << 32) ^ ((uint64_t)i << 24) ^ (uint64_t)c));
         r = (int)(h % (uint64_t)n);
         bb = (int)(rr_mix(h) % (uint64_t)nb) + 1;
       }
@@ -331,7 +333,7 @@ __global__ __launch_bounds__(K9_THREADS) void k_cross_resampled(const double *__
       if (c == 0) { r = i; bb = 0; }
       else if (rg) { r = rg[(int64_t)i * num_boot + c]; bb = bg[(int64_t)i * num_boot + c]; }
       else {
-        uint64_t h = rr_mix(seed ^ rr_mix(((uint64_t)gene << 32) ^ ((uint64_t)i << 24) ^ (uint64_t)c));
+        uint64_t h = rr_mix(seed ^ rr_mix((gk << 32) ^ ((uint64_t)i << 24) ^ (uint64_t)c));
         r = (int)(h % (uint64_t)n);
         bb = (int)(rr_mix(h) % (uint64_t)nb) + 1;
       }
@@ -353,6 +355,175 @@ __global__ __launch_bounds__(K9_THREADS) void k_cross_resampled(const double *__
     return val == val;
   };
   fill_records<1, true>(coef_at, nb, crow, st, red);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Step 2, gene-major (ht_1d_eqtl: hundreds of cis SNPs per gene, analysis/lupus/run_memento.py:84-109): the tests arrive as a CSR
+// gene_ptr over tt, and one workgroup takes a TILE of XB_TT consecutive tests of one gene.  The draws (rep, bcol) of a column
+// depend on the gene, not on the test, so a thread obtains each draw of its column once per pass -- table or hash, col_map,
+// glist, the yt read, the weight -- and applies it to all XB_TT tests, whose accumulators it keeps in registers; the tile's tt
+// rows sit in LDS test-minor, so that a draw reads XB_TT consecutive doubles.  For every (test, column) the operations and their
+// order over i are those of k_cross_resampled, so with the same key the coefficient is that kernel's bit for bit; the columns go
+// to the threads and the partial sums through wg_reduce as in fill_records, so the whole record is.  Nothing per replicate is
+// stored: pass B of the record computes the coefficients again, and mm_cross_resampled on a subset gives the rows of the few
+// tests that need them.
+// XB_TT = 8: the record's pass B keeps 3 doubles and 2 counts per test (c0, mean, sq; ext, raw) next to the 4 doubles of a
+// coefficient's second pass (mA, ss, num, amax): 16 VGPRs per test, 128 for the tile, which with the operands in flight stays
+// inside the 256 registers at which two waves share a SIMD; 16 tests would need the whole file for one wave.  LDS: (XB_TT + 1.5) * 8 B per group, 19 KB at 250 donors.
+#define XB_TT 8
+
+// fill_records with ONE VALIDITY PER PLANE: plane k of ``coef_at(c, v)`` is valid at column c when v[k] is not NaN (a column can
+// be degenerate for one SNP and not for its neighbour).  Nothing is stored; the records of the first n_used planes are written.
+// Column order per thread and reduction order are those of fill_records.
+template <int NP, class F>
+__device__ __forceinline__ void fill_records_each(F coef_at, int n_cols, double *(&st)[NP], int n_used, double *red) {
+  double v[NP], sum[NP], lo[NP], hi[NP], cnt[NP];
+  for (int k = 0; k < NP; k++) { sum[k] = 0.0; cnt[k] = 0.0; lo[k] = INFINITY; hi[k] = -INFINITY; }
+  for (int c = threadIdx.x; c < n_cols; c += K9_THREADS) {
+    coef_at(c, v);
+    for (int k = 0; k < NP; k++) {
+      if (v[k] == v[k]) {
+        lo[k] = fmin(lo[k], v[k]); hi[k] = fmax(hi[k], v[k]);
+        if (c > 0) { sum[k] += v[k]; cnt[k] += 1.0; }
+      }
+    }
+  }
+  for (int k = 0; k < NP; k++) cnt[k] = wg_sum(cnt[k], red);
+  for (int k = 0; k < NP; k++) sum[k] = wg_sum(sum[k], red);
+  for (int k = 0; k < NP; k++) { lo[k] = wg_min(lo[k], red); hi[k] = wg_max(hi[k], red); }
+  double c0[NP], mean[NP], sq[NP];
+  int ext[NP], raw[NP];      // (counts: exact either way, and half the registers)
+  coef_at(0, c0);
+  for (int k = 0; k < NP; k++) {
+    mean[k] = cnt[k] > 0 ? sum[k] / cnt[k] : NAN;
+    sq[k] = 0.0;
+    ext[k] = raw[k] = 0;
+  }
+  for (int c = 1 + threadIdx.x; c < n_cols; c += K9_THREADS) {
+    coef_at(c, v);
+    for (int k = 0; k < NP; k++) {
+      if (v[k] == v[k]) {
+        double d = v[k] - mean[k];
+        sq[k] += d * d;
+        double nul = v[k] - c0[k], a0 = fabs(c0[k]);
+        if (nul > a0 || nul < -a0) ext[k]++;
+        if (v[k] > a0 || v[k] < -a0) raw[k]++;
+      }
+    }
+  }
+  for (int k = 0; k < NP; k++) sq[k] = wg_sum(sq[k], red);
+  double n_ext[NP], n_raw[NP];
+  for (int k = 0; k < NP; k++) n_ext[k] = wg_sum((double)ext[k], red);
+  for (int k = 0; k < NP; k++) n_raw[k] = wg_sum((double)raw[k], red);
+  if (threadIdx.x == 0) {
+    for (int k = 0; k < NP; k++) {
+      if (k >= n_used) break;
+      double *s = st[k];
+      s[0] = c0[k];
+      s[1] = cnt[k] > 0 ? sqrt(sq[k] / cnt[k]) : NAN;
+      s[2] = cnt[k];
+      s[3] = n_ext[k];
+      s[4] = mean[k] - c0[k];
+      s[5] = (lo[k] == hi[k]) ? 1.0 : 0.0;
+      s[6] = n_raw[k];
+      s[7] = hi[k] - lo[k];
+    }
+  }
+}
+
+__global__ __launch_bounds__(K9_THREADS, 2) void k_cross_resampled_block(
+    const double *__restrict__ yt, int64_t ld, int32_t num_boot, int32_t n_groups, int32_t tiles_per_gene,
+    const int32_t *__restrict__ gene_ptr /* [n_genes + 1] CSR over the tests */,
+    const double *__restrict__ tt /* [n_tests][ng] residualised treatment */, const uint8_t *__restrict__ good,
+    const double *__restrict__ Nc, const int16_t *__restrict__ rep, const int32_t *__restrict__ bcol,
+    const int32_t *__restrict__ col_map, const int32_t *__restrict__ n_valid, const int64_t *__restrict__ gene_key, uint64_t seed,
+    double *__restrict__ stats) {
+  extern __shared__ double sm[];
+  double *tts = sm;                                        // [ng][XB_TT], test-minor
+  double *ncs = sm + (size_t)XB_TT * n_groups;             // [ng]
+  int32_t *glist = (int32_t *)(ncs + n_groups);            // [ng] indices of good groups
+  __shared__ double red[K9_THREADS / 64];
+  __shared__ int n_good_s;
+  const int gene = (int)(blockIdx.x / (unsigned)tiles_per_gene);
+  const int64_t t0 = (int64_t)gene_ptr[gene] + (int64_t)(blockIdx.x % (unsigned)tiles_per_gene) * XB_TT;
+  const int64_t t1 = gene_ptr[gene + 1];
+  if (t0 >= t1) return;                                    // (uniform over the workgroup) a gene without tests, or past its last tile
+  const int nt = (int)(t1 - t0 < XB_TT ? t1 - t0 : XB_TT);  // the gene's last tile may be partial: its other slots compute on zeros
+  const uint8_t *gd = good + (int64_t)gene * n_groups;
+  if (threadIdx.x == 0) {
+    int ng = 0;
+    for (int j = 0; j < n_groups; j++)
+      if (gd[j]) glist[ng++] = j;
+    n_good_s = ng;
+  }
+  for (int j = threadIdx.x; j < n_groups; j += K9_THREADS) {
+    for (int k = 0; k < XB_TT; k++) tts[(size_t)j * XB_TT + k] = k < nt ? tt[(t0 + k) * n_groups + j] : 0.0;
+    ncs[j] = Nc[j];
+  }
+  __syncthreads();
+  const int n = n_good_s;
+  double *st[XB_TT];
+  for (int k = 0; k < XB_TT; k++) st[k] = stats + (t0 + (k < nt ? k : 0)) * 8;
+  const int64_t row_base = (int64_t)gene * n_groups;
+  const int nb = n_valid ? n_valid[gene] - 1 : num_boot;
+  if (n == 0 || nb < 1) {
+    for (int k = 0; k < nt; k++) write_nan_record(st[k]);
+    return;
+  }
+  const int16_t *rg = rep ? rep + (int64_t)gene * n_groups * num_boot : nullptr;
+  const int32_t *bg = bcol ? bcol + (int64_t)gene * n_groups * num_boot : nullptr;
+  const int32_t *cm = col_map ? col_map + (int64_t)gene * (num_boot + 1) : nullptr;
+  const uint64_t gk = gene_key ? (uint64_t)gene_key[gene] : (uint64_t)gene;
+  // row i of column c: the drawn group (index into yt / ncs / tts) and the response there
+  auto draw = [&](int i, int c, int &j, double &y) {
+    int r, bb;
+    if (c == 0) { r = i; bb = 0; }
+    else if (rg) { r = rg[(int64_t)i * num_boot + c]; bb = bg[(int64_t)i * num_boot + c]; }
+    else {
+      uint64_t h = rr_mix(seed ^ rr_mix((gk << 32) ^ ((uint64_t)i << 24) ^ (uint64_t)c));
+      r = (int)(h % (uint64_t)n);
+      bb = (int)(rr_mix(h) % (uint64_t)nb) + 1;
+    }
+    if (cm) bb = cm[bb];
+    j = glist[r];
+    y = yt[(row_base + j) * ld + bb];
+  };
+  auto coef_at = [&](int c, double(&v)[XB_TT]) {
+    double sw = 0.0, swy = 0.0, swa[XB_TT], amax[XB_TT];
+    for (int k = 0; k < XB_TT; k++) swa[k] = amax[k] = 0.0;
+    for (int i = 0; i < n; i++) {
+      int j;
+      double y;
+      draw(i, c, j, y);
+      double w = ncs[j];
+      const double *a = tts + (size_t)j * XB_TT;
+      sw += w; swy += w * y;
+      for (int k = 0; k < XB_TT; k++) {
+        swa[k] += w * a[k];
+        amax[k] = fmax(amax[k], fabs(a[k]));
+      }
+    }
+    double mB = swy / sw, ss[XB_TT], num[XB_TT];
+    for (int k = 0; k < XB_TT; k++) { swa[k] = swa[k] / sw; ss[k] = num[k] = 0.0; }      // swa is mA from here on
+    for (int i = 0; i < n; i++) {
+      int j;
+      double y;
+      draw(i, c, j, y);
+      double w = ncs[j], dy = y - mB;
+      const double *a = tts + (size_t)j * XB_TT;
+      for (int k = 0; k < XB_TT; k++) {
+        double da = a[k] - swa[k];
+        ss[k] += da * da * w;
+        num[k] += (da * w) * dy;
+      }
+    }
+    for (int k = 0; k < XB_TT; k++) {      // the degenerate-column rule of k_cross_resampled
+      double val = num[k] / sw / (ss[k] / sw);
+      if (ss[k] / sw <= 1e-24 * amax[k] * amax[k]) val = NAN;
+      v[k] = val;
+    }
+  };
+  fill_records_each<XB_TT>(coef_at, nb, st, nt, red);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1052,17 +1223,55 @@ int mm_residualize(const double *d_src, double *d_dst, int64_t ld, int32_t n_col
   return MM_OK;
 }
 
+static int cross_resampled_args(const double *d_yt, int64_t ld, int32_t num_boot, int32_t n_groups, const void *d_tests, const double *d_tt,
+                                const uint8_t *d_good, const double *d_Nc, const int16_t *d_rep, const int32_t *d_bcol,
+                                const int32_t *d_col_map, const int32_t *d_n_valid, int64_t n_tests, const double *d_stats) {
+  MM_ARG(d_yt && d_tests && d_tt && d_good && d_Nc && d_stats);
+  MM_ARG(n_tests >= 0 && n_tests < 2147483647LL && n_groups > 0 && n_groups <= 32767 && num_boot > 1 && ld >= (int64_t)num_boot + 1);
+  MM_ARG(((d_rep == nullptr) == (d_bcol == nullptr)) && ((d_col_map == nullptr) == (d_n_valid == nullptr)));
+  return MM_OK;
+}
+
+int mm_cross_resampled_keyed(const double *d_yt, int64_t ld, int32_t num_boot, int32_t n_groups, const int32_t *d_test_gene,
+                             const double *d_tt, const uint8_t *d_good, const double *d_Nc, const int16_t *d_rep, const int32_t *d_bcol,
+                             const int32_t *d_col_map, const int32_t *d_n_valid, const int64_t *d_gene_key, uint64_t seed,
+                             int64_t n_tests, double *d_coef, double *d_stats, void *stream) {
+  int rc = cross_resampled_args(d_yt, ld, num_boot, n_groups, d_test_gene, d_tt, d_good, d_Nc, d_rep, d_bcol, d_col_map, d_n_valid, n_tests,
+                                d_stats);
+  if (rc != MM_OK) return rc;
+  MM_ARG(d_coef);
+  if (n_tests == 0) return MM_OK;
+  size_t shm = (size_t)n_groups * 20 + 8;
+  hipLaunchKernelGGL(k_cross_resampled, dim3((unsigned)n_tests), dim3(K9_THREADS), shm, (hipStream_t)stream, d_yt, ld, num_boot, n_groups,
+                     d_test_gene, d_tt, d_good, d_Nc, d_rep, d_bcol, d_col_map, d_n_valid, d_gene_key, seed, d_coef, d_stats);
+  MM_LAUNCH_CHECK();
+  return MM_OK;
+}
+
 int mm_cross_resampled(const double *d_yt, int64_t ld, int32_t num_boot, int32_t n_groups, const int32_t *d_test_gene,
                        const double *d_tt, const uint8_t *d_good, const double *d_Nc, const int16_t *d_rep, const int32_t *d_bcol,
                        const int32_t *d_col_map, const int32_t *d_n_valid, uint64_t seed, int64_t n_tests, double *d_coef,
                        double *d_stats, void *stream) {
-  MM_ARG(d_yt && d_test_gene && d_tt && d_good && d_Nc && d_coef && d_stats);
-  MM_ARG(n_tests >= 0 && n_tests < 2147483647LL && n_groups > 0 && n_groups <= 32767 && num_boot > 1 && ld >= (int64_t)num_boot + 1);
-  MM_ARG(((d_rep == nullptr) == (d_bcol == nullptr)) && ((d_col_map == nullptr) == (d_n_valid == nullptr)));
-  if (n_tests == 0) return MM_OK;
-  size_t shm = (size_t)n_groups * 20 + 8;
-  hipLaunchKernelGGL(k_cross_resampled, dim3((unsigned)n_tests), dim3(K9_THREADS), shm, (hipStream_t)stream, d_yt, ld, num_boot, n_groups,
-                     d_test_gene, d_tt, d_good, d_Nc, d_rep, d_bcol, d_col_map, d_n_valid, seed, d_coef, d_stats);
+  return mm_cross_resampled_keyed(d_yt, ld, num_boot, n_groups, d_test_gene, d_tt, d_good, d_Nc, d_rep, d_bcol, d_col_map, d_n_valid,
+                                  nullptr, seed, n_tests, d_coef, d_stats, stream);
+}
+
+int mm_cross_resampled_block(const double *d_yt, int64_t ld, int32_t num_boot, int32_t n_groups, const int32_t *d_gene_ptr,
+                             int64_t n_genes, int32_t max_gene_tests, const double *d_tt, const uint8_t *d_good, const double *d_Nc,
+                             const int16_t *d_rep, const int32_t *d_bcol, const int32_t *d_col_map, const int32_t *d_n_valid,
+                             const int64_t *d_gene_key, uint64_t seed, int64_t n_tests, double *d_stats, void *stream) {
+  int rc = cross_resampled_args(d_yt, ld, num_boot, n_groups, d_gene_ptr, d_tt, d_good, d_Nc, d_rep, d_bcol, d_col_map, d_n_valid, n_tests,
+                                d_stats);
+  if (rc != MM_OK) return rc;
+  MM_ARG(n_genes >= 0 && max_gene_tests >= 0 && (int64_t)max_gene_tests <= n_tests);
+  if (n_tests == 0 || n_genes == 0 || max_gene_tests == 0) return MM_OK;
+  int32_t tiles = (max_gene_tests + XB_TT - 1) / XB_TT;
+  MM_ARG(n_genes * tiles < 2147483647LL);
+  size_t shm = (size_t)n_groups * (XB_TT * 8 + 12) + 8;
+  MM_ARG(shm <= 64 * 1024);
+  hipLaunchKernelGGL(k_cross_resampled_block, dim3((unsigned)(n_genes * tiles)), dim3(K9_THREADS), shm, (hipStream_t)stream, d_yt, ld,
+                     num_boot, n_groups, tiles, d_gene_ptr, d_tt, d_good, d_Nc, d_rep, d_bcol, d_col_map, d_n_valid, d_gene_key, seed,
+                     d_stats);
   MM_LAUNCH_CHECK();
   return MM_OK;
 }

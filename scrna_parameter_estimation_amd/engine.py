@@ -1116,6 +1116,19 @@ class Bootstrap1D:
         return _contract_resampled(self.yv if which else self.ym, self.ld, self.B, self.ng, self.n_tested, test_gene, tt, good, gene_mask,
                                    M, Nc, rep, bcol, seed, col_map, n_valid)
 
+    def cross_resampled_block(self, gene_ptr, tt, good, gene_mask, M, Nc, rep=None, bcol=None, seed=0, col_map=None, n_valid=None,
+                              gene_key=None):
+        """resample_rep=True for tests that arrive gene-major (mm_cross_resampled_block): the tests of gene slot g are the rows
+        ``gene_ptr[g]:gene_ptr[g + 1]`` of ``tt`` [n_tests][n_groups]; everything else as ``contract_resampled``, and ``gene_key``
+        [n_genes] keys the device draws of a gene (None: its slot).  Each plane is residualised into ONE plane-sized scratch in
+        turn; no coefficient row is stored.  Returns (stats_mean, stats_var) host arrays [n_tests][8] -- the records
+        ``contract_resampled`` gives for the same tests -- and ``rows(which, idx, to_host=True, out=None)``, the contract of
+        ``contrast_design``'s closure: the coefficient rows of the tests ``idx`` on plane ``which``, from the per-test kernel on
+        that subset with the same draws (mm_cross_resampled_keyed).  The closure holds the scratch."""
+        (st_m, st_v), rows = _cross_resampled_block([self.ym, self.yv], self.ld, self.B, self.ng, self.n_tested, gene_ptr, tt, good, gene_mask,
+                                                    M, Nc, rep, bcol, seed, col_map, n_valid, gene_key)
+        return st_m, st_v, rows
+
 
 def _rows_out(out, n, ld):
     """Where a ``rows`` closure writes ``n`` coefficient rows: a fresh tensor, or the caller's scratch ``out`` [>= n][ld] (fp64,
@@ -1343,6 +1356,99 @@ def _contract_resampled(src, ld, B, ng, n_genes, test_gene, tt, good, gene_mask,
     _lib.call("mm_cross_resampled", P(yt), ld, B, ng, P(d_tg), P(d_tt), P(d_good), P(d_nc), P(d_rep), P(d_bcol),
               P(col_map if n_valid is not None else None), P(d_nv), int(seed) & ((1 << 64) - 1), n_tests, P(coef), P(stats), s)
     return coef, host(stats)[:n_tests]
+
+
+CROSS_BLOCK_TT = 8            # tests of one gene that a workgroup of mm_cross_resampled_block takes together (contract.hip: XB_TT)
+CROSS_BLOCK_MAX_GROUPS = 860  # 76 bytes of LDS per group, 64 KB a workgroup
+
+
+def _block_tables(B, ng, n_genes,gene_ptr, tt, good, gene_mask, M, Nc, rep, bcol, n_valid, gene_key):
+    """The tables of mm_cross_resampled_block, coerced and checked on the host (the kernel trusts them): ``gene_ptr`` a CSR pointer
+    over the rows of ``tt`` [n_tests][ng], one entry per gene slot; ``good`` [n_genes][ng]; ``gene_mask`` [n_genes] into ``M``
+    [n_masks][ng][ng]; ``n_valid`` [n_genes] in 0..B + 1; ``rep`` / ``bcol`` [n_genes][ng][B] with, in the rows i < n of a gene with n
+    good groups and the columns 1..nb - 1 the kernel reads, 0 <= rep < n and 1 <= bcol <= nb (nb = n_valid - 1, or B);
+    ``gene_key`` [n_genes] >= 0."""
+    gene_ptr = np.asarray(gene_ptr, dtype=np.int64).reshape(-1)
+    tt = np.ascontiguousarray(tt, dtype=np.float64)
+    good = np.ascontiguousarray(np.asarray(good, dtype=bool), dtype=np.uint8)
+    gene_mask, M, Nc = np.asarray(gene_mask, dtype=np.int32), np.asarray(M, dtype=np.float64), np.asarray(Nc, dtype=np.float64)
+    what = "cross_resampled_block"
+    if ng > CROSS_BLOCK_MAX_GROUPS:
+        raise NotImplementedError(f"cross_resampled_block with more than {CROSS_BLOCK_MAX_GROUPS} groups")
+    if len(gene_ptr) != n_genes + 1 or gene_ptr[0] != 0 or (np.diff(gene_ptr) < 0).any() or tt.ndim != 2 or gene_ptr[-1] != len(tt):
+        raise ValueError(f"{what}: gene_ptr is not a CSR pointer over the rows of tt, one entry per gene")
+    if len(tt) >= 2 ** 31 - 1 or (len(tt) and tt.shape[1] != ng) or good.shape != (n_genes, ng) or Nc.shape != (ng,):
+        raise ValueError(f"{what}: tt, good and Nc do not match the groups")
+    if gene_mask.shape != (n_genes,) or M.ndim != 3 or M.shape[1:] != (ng, ng) or (n_genes and (gene_mask.min() < 0 or gene_mask.max() >= len(M))):
+        raise ValueError(f"{what}: gene_mask does not index M [n_masks][n_groups][n_groups]")
+    nb = np.full(n_genes, B, dtype=np.int64)
+    if n_valid is not None:
+        n_valid = np.asarray(n_valid, dtype=np.int32)
+        if n_valid.shape != (n_genes,) or (n_genes and (n_valid.min() < 0 or n_valid.max() > B + 1)):
+            raise ValueError(f"{what}: n_valid must hold 0..num_boot + 1 for every gene")
+        nb = n_valid.astype(np.int64) - 1
+    if (rep is None) != (bcol is None):
+        raise ValueError(f"{what}: rep and bcol come together")
+    if rep is not None:
+        rep, bcol = np.ascontiguousarray(rep, dtype=np.int16), np.ascontiguousarray(bcol, dtype=np.int32)
+        if rep.shape != (n_genes, ng, B) or bcol.shape != rep.shape:
+            raise ValueError(f"{what}: rep / bcol must be [n_genes][n_groups][num_boot]")
+        n_good = good.sum(axis=1)
+        for g in np.flatnonzero((n_good > 0) & (nb >= 2) & (np.diff(gene_ptr) > 0)):
+            r, b = rep[g, :n_good[g], 1:nb[g]], bcol[g, :n_good[g], 1:nb[g]]
+            if r.min() < 0 or r.max() >= n_good[g] or b.min() < 1 or b.max() > nb[g]:
+                raise ValueError(f"{what}: rep / bcol of gene {g} leave its good groups / surviving columns")
+    if gene_key is not None:
+        gene_key = np.asarray(gene_key, dtype=np.int64)
+        if gene_key.shape != (n_genes,) or (n_genes and gene_key.min() < 0):
+            raise ValueError(f"{what}: gene_key must hold one non-negative key per gene")
+    return gene_ptr.astype(np.int32), tt, good, gene_mask, M, Nc, rep, bcol, n_valid, gene_key
+
+
+def _cross_resampled_block(planes, ld, B, ng, n_genes, gene_ptr, tt, good, gene_mask, M, Nc, rep, bcol, seed, col_map, n_valid, gene_key):
+    """``Bootstrap1D.cross_resampled_block``: the records of every plane of ``planes`` and the ``rows`` closure."""
+    torch = _torch()
+    s = _stream()
+    gene_ptr, tt, good, gene_mask, M, Nc, rep, bcol, n_valid, gene_key = _block_tables(B, ng, n_genes, gene_ptr, tt, good, gene_mask, M, Nc,
+                                                                                      rep, bcol, n_valid, gene_key)
+    n_tests = len(tt)
+    if n_valid is not None and (col_map is None or col_map.dtype != torch.int32 or col_map.numel() < n_genes * (B + 1)):
+        raise ValueError("cross_resampled_block: col_map must be the int32 device tensor [n_genes][num_boot + 1] of valid_cols")
+    seed = int(seed) & ((1 << 64) - 1)
+    test_gene = np.repeat(np.arange(n_genes, dtype=np.int32), np.diff(gene_ptr))
+    max_tests = int(np.diff(gene_ptr).max()) if n_genes else 0
+    yt = torch.empty_like(planes[0])               # the ONE plane-sized scratch: the residualised rows of plane ``held[0]``
+    held = [None]
+    d_gm, d_M, d_ptr, d_tt, d_good, d_nc = dev(gene_mask), _up(M.reshape(-1)), dev(gene_ptr), _up(tt.reshape(-1)), _up(good.reshape(-1)), dev(Nc)
+    d_rep, d_bcol = (dev(rep), dev(bcol)) if rep is not None else (None, None)
+    d_nv = dev(n_valid) if n_valid is not None else None
+    d_cm = col_map if n_valid is not None else None
+    d_key = _up(gene_key) if gene_key is not None else None
+
+    def residualise(which):
+        if held[0] != which and n_genes:
+            _lib.call("mm_residualize", P(planes[which]), P(yt), ld, ld, ng, n_genes, P(d_gm), P(d_M), _stream())
+        held[0] = which
+
+    stats = []
+    for which in range(len(planes)):
+        residualise(which)
+        st = empty((max(1, n_tests), 8), torch.float64)
+        _lib.call("mm_cross_resampled_block", P(yt), ld, B, ng, P(d_ptr), n_genes, max_tests, P(d_tt), P(d_good), P(d_nc), P(d_rep), P(d_bcol),
+                  P(d_cm), P(d_nv), P(d_key), seed, n_tests, P(st), s)
+        stats.append(host(st)[:n_tests])
+
+    def rows(which, idx, to_host=True, out=None):
+        idx = np.asarray(idx, dtype=np.int64)
+        out = _rows_out(out, len(idx), ld)
+        residualise(int(which))
+        a, b = _up(test_gene[idx]), _up(tt[idx].reshape(-1))
+        scrap = empty((max(1, len(idx)), 8), torch.float64)
+        _lib.call("mm_cross_resampled_keyed", P(yt), ld, B, ng, P(a), P(b), P(d_good), P(d_nc), P(d_rep), P(d_bcol), P(d_cm), P(d_nv), P(d_key),
+                  seed, len(idx), P(out), P(scrap), _stream())
+        return host(out)[: len(idx)] if to_host else out[: len(idx)]
+
+    return stats, rows
 
 
 # =================================================================================================

@@ -371,6 +371,108 @@ def design_tables(good, cols, cov, trt, Nc, resampled=False, rr_cols=None, first
     return d
 
 
+def eqtl_gene_columns(genotypes, gene_snp_pairs, names):
+    """The cis SNPs of every kept gene (``ht_1d_eqtl``): a tuple of positions among the columns of ``genotypes`` per name of
+    ``names``, in the gene's list order; a kept gene that is not listed has none.  ``gene_snp_pairs``: a dict gene -> list of
+    genotype columns (the reference's ``treatment_for_gene``), or a two-column frame (gene, snp), whose rows keep their order
+    within a gene.  Genes outside ``names`` are ignored (``gene_columns``); a SNP that is not a genotype column raises ValueError."""
+    pos = {c: j for j, c in enumerate(genotypes.columns)}
+    if isinstance(gene_snp_pairs, dict):
+        lists = {g: list(v) for g, v in gene_snp_pairs.items()}
+    else:
+        if getattr(gene_snp_pairs, 'shape', (0, 0))[1:] != (2,):
+            raise ValueError("gene_snp_pairs must be a dict gene -> SNP columns or a two-column frame (gene, snp)")
+        lists = {}
+        for g, s in zip(gene_snp_pairs.iloc[:, 0], gene_snp_pairs.iloc[:, 1]):
+            lists.setdefault(g, []).append(s)
+    out = []
+    for n in names:
+        snps = lists.get(n, ())
+        missing = [s for s in snps if s not in pos]
+        if missing:
+            raise ValueError(f"gene {n!r}: {missing[0]!r} is not a column of genotypes")
+        out.append(tuple(pos[s] for s in snps))
+    return out
+
+
+def eqtl_tables(good, cols, cov, trt, Nc, resampled=False):
+    """``design_tables`` for tests that arrive gene-major with a SNP list of its own per gene (``ht_1d_eqtl``): row ``k`` of ``good``
+    is tested on the treatment columns ``cols[k]`` (a tuple, possibly empty), and ``gene_ptr`` [rows + 1] is the CSR pointer of
+    its tests.  ``Wmat``, ``tt_mat`` and ``rr_test`` come from the same calls as in ``design_tables`` (``design.weight_rows`` /
+    ``design.residual_parts`` on the gene's whole column list: bit-equal rows), but ``Mstack`` holds ONE residual maker per
+    distinct good mask -- it depends on the mask, the covariates and ``Nc`` alone -- where ``design_tables``, whose cache key
+    includes the columns, would keep one per gene."""
+    good = np.asarray(good, dtype=bool)
+    n_rows, ng = good.shape
+    w_cache, r_cache, m_index = {}, {}, {}
+    counts, w_rows, tt_rows, Ms, rr = [], [], [], [], []
+    row_mask = np.zeros(n_rows, dtype=np.int32)
+    for k in range(n_rows):
+        mask, ck = good[k].tobytes(), tuple(cols[k])
+        counts.append(len(ck))
+        if resampled and mask not in m_index:
+            m_index[mask] = len(Ms)
+            Ms.append(_design.residual_parts(cov, np.zeros((ng, 1)), Nc, good[k])[0])      # (M does not read the treatment)
+        if resampled:
+            row_mask[k] = m_index[mask]
+        if not ck:
+            continue
+        key = (mask, ck)
+        if key not in w_cache:
+            w_cache[key] = _design.weight_rows(cov, _take(trt, ck), Nc, good[k])
+        w_rows.append(w_cache[key])
+        if not resampled:
+            continue
+        if key not in r_cache:
+            t = _take(trt, ck)
+            allones = (t[good[k]] == 1).mean() == 1 if good[k].any() else True
+            r_cache[key] = (_design.residual_parts(cov, t, Nc, good[k])[1], not allones)
+        ttg, resample = r_cache[key]
+        tt_rows.append(ttg)
+        rr.extend([resample] * len(ttg))
+    gene_ptr = np.concatenate([[0], np.cumsum(counts, dtype=np.int64)]).astype(np.int64)
+    d = SimpleNamespace(gene_ptr=gene_ptr, test_row=np.repeat(np.arange(n_rows, dtype=np.int64), counts), tt_mat=None, Mstack=None,
+                        row_mask=None, rr_test=None, Wmat=np.concatenate(w_rows, axis=0) if w_rows else np.zeros((0, ng)))
+    if resampled:
+        d.tt_mat = np.concatenate(tt_rows, axis=0) if tt_rows else np.zeros((0, ng))
+        d.Mstack = np.stack(Ms) if Ms else np.zeros((0, ng, ng))
+        d.row_mask, d.rr_test = row_mask, np.asarray(rr, dtype=bool)
+    return d
+
+
+def weight_row_designs(test_row, Wmat, good):
+    """The weight rows of plain tests as the CSR designs of ``contrast_design``: design t lists the good groups of row block
+    ``test_row[t]`` in ascending order (zero weights included: they take part in the validity of a column) with the weights
+    ``Wmat[t]`` there -- the sum ``k_contract_stats`` forms, term for term.  A row block without a good group gives the empty design
+    (the NaN record).  -> (test_design, design_ptr, design_grp, design_w)."""
+    good = np.asarray(good, dtype=bool)
+    sel = good[test_row] if len(test_row) else np.zeros((0, good.shape[1]), dtype=bool)
+    t_idx, grp = np.nonzero(sel)                       # row-major: test by test, groups ascending
+    design_ptr = np.concatenate([[0], np.cumsum(sel.sum(axis=1), dtype=np.int64)])
+    return np.arange(len(test_row), dtype=np.int32), design_ptr, grp.astype(np.int32), np.asarray(Wmat, dtype=np.float64)[t_idx, grp]
+
+
+def sliced_rows(parts, idx, ld, scratch_bytes=None):
+    """Host coefficient rows [len(idx)][ld] of the tests ``idx`` whose rows are not stored, for ``asl.asl_from_stats``: ``parts`` is a
+    list of (member, local, rows) -- test t belongs to the part with ``member[t]``, where it is test ``local[t]`` of the closure
+    ``rows(idx, to_host=False, out=scratch)`` -- and every part produces its rows a slice at a time into ONE device scratch of
+    at most ``scratch_bytes`` (default ``CI_SCRATCH_BYTES``; never less than one row), as ``sliced_intervals`` does."""
+    if scratch_bytes is None:
+        scratch_bytes = CI_SCRATCH_BYTES
+    idx = np.asarray(idx, dtype=np.int64)
+    out = np.full((len(idx), ld), np.nan)
+    if not len(idx):
+        return out
+    per = int(min(len(idx), max(1, int(scratch_bytes) // (8 * ld))))
+    scratch = engine.empty((per, ld), engine._torch().float64)
+    for member, local, rows in parts:
+        mine = np.flatnonzero(member[idx])
+        for lo in range(0, len(mine), per):
+            sl = mine[lo:lo + per]
+            out[sl] = engine.host(rows(local[idx[sl]], to_host=False, out=scratch))
+    return out
+
+
 def pair_design_tables(good, tcol, per_gene, cov, trt, Nc, resampled=False):
     """``design_tables`` for gene pairs: one test per pair, on treatment column ``tcol[k]``.  ``per_gene`` = the call has a
     ``treatment_for_gene``.  Without one, the weight row is that of column 0 but the residual parts and the all-ones verdict are

@@ -817,6 +817,112 @@ def ht_1d_joint(adata, treatment, covariate=None, num_boot=10000, rng='replay', 
                          'dv_stat': out['var_stat'], 'dv_pval': out['var_asl']})
 
 
+def ht_1d_eqtl(adata, genotypes, gene_snp_pairs, covariate=None, num_boot=5000, num_cpus=1, rng='replay', fill_seed=0, max_rows=None,
+               approx=False, resampling='bootstrap', resample_rep=False, **not_offered):
+    """cis-eQTL scan: every kept gene against its own list of SNPs, hundreds per gene (the reference's largest analysis,
+    analysis/lupus/run_memento.py:29-52, :84-109: one group per donor, ``treatment_for_gene``, ``resample_rep=True``).
+
+    ``genotypes``: DataFrame [groups][SNPs] in the group order of ``uns['memento']['groups']`` (what ``treatment`` is to
+    ``ht_1d_moments``); ``gene_snp_pairs``: a dict gene -> list of genotype columns (what ``treatment_for_gene`` is), or a
+    two-column frame (gene, snp).  Genes that are not kept are ignored, a kept gene without a list has no test, an unknown SNP
+    raises ValueError.  ``covariate``: DataFrame / array [groups][C], or None.
+
+    The tests are those of ``ht_1d_moments(adata, covariate, genotypes, treatment_for_gene=..., ...)`` -- the same bootstrap
+    (``rng``, ``fill_seed``, ``max_rows``, the hash uniforms from the global ``np.random`` stream, the same stream keys), the same
+    designs, coefficients bit for bit in a one-chunk call -- but no coefficient row is stored per test: the device memory of the
+    call grows with tests x groups, not with tests x replicates.  The resampled tests (``resample_rep=True``, treatment not all
+    ones) run gene-major (mm_cross_resampled_block: a gene's draws are made once per tile of 8 SNPs, not once per SNP), the plain
+    tests as design contrasts (``contrast_design``); the few rows that the tail fits of ``approx=False`` read are produced on
+    demand in slices of a bounded scratch.  The device draws of ``resample_rep`` are keyed by the gene's position among the kept
+    genes, so -- unlike ``ht_1d_moments`` there -- the result does not depend on ``max_rows``.
+
+    Not offered: ``strict``, ``ci``, ``max_boot``, ``treatment_for_gene`` (TypeError), and a gene-sharded run (NotImplementedError).
+
+    Returns a DataFrame (gene, snp, de_coef, de_se, de_pval, dv_coef, dv_se, dv_pval), gene-major over the kept genes, each gene's
+    SNPs in its list order; the arrays go to ``uns['memento']['1d_ht_eqtl']``."""
+    if not_offered:
+        raise TypeError(f"ht_1d_eqtl does not offer {sorted(not_offered)[0]!r}")
+    _ht.check_args(rng, resampling=resampling)
+    resample_rep, approx = bool(resample_rep), bool(approx)
+    m = adata.uns['memento']
+    st = m['_hip']
+    comm = getattr(st, 'comm', None)
+    if comm is not None and comm.world > 1:
+        raise NotImplementedError("ht_1d_eqtl on a gene-sharded run: the results are not gathered across ranks")
+    mv = _ht.moments_view(m)
+    ng = mv.ng
+    names = _var_names(adata)
+    G_all = len(st.gene_idx)
+    if not isinstance(genotypes, pd.DataFrame) or len(genotypes) != ng:
+        raise ValueError(f"genotypes must be a DataFrame with one row per group ({ng})")
+    trt_all = np.asarray(genotypes.values, dtype=np.float64)
+    cov = np.ones((ng, 0)) if covariate is None else np.asarray(getattr(covariate, 'values', covariate), dtype=np.float64).reshape(ng, -1)
+    gene_cols = _ht.eqtl_gene_columns(genotypes, gene_snp_pairs, names[:G_all])
+    snp_names = np.asarray(genotypes.columns, dtype=object)
+    if st.sf_bin is None:
+        raise NotImplementedError("more than 255 size-factor bins")
+    fill_pos = (np.asarray(st.shard, dtype=np.int64)[st.gene_idx] if getattr(st, 'shard', None) is not None
+                else np.asarray(st.gene_idx, dtype=np.int64))
+    cols = {k: [] for k in ('mean_coef', 'mean_se', 'mean_asl', 'var_coef', 'var_se', 'var_asl')}
+
+    def run_chunk(c):
+        g0, g1, G, bs = c.g0, c.g1, c.G, c.bs
+        keys = (fill_pos[g0:g1, None] * ng + np.arange(ng)[None, :]).reshape(-1)          # the stream keys of ht_1d_moments
+        good, n_inv = _ht.run_chunk_1d(c, mv, rng, fill_seed, keys, np.arange(g0 * ng, g1 * ng, dtype=np.int64))
+        refilled = ((n_inv > 0).any(axis=1) & ~c.skip).reshape(G, ng).any(axis=1)
+        rs = st.refill_stats
+        rs['chains'] += int(((~c.skip) & (bs.K >= 2)).sum())
+        rs['chains_refilled'] += int(((n_inv > 0).any(axis=1) & ~c.skip).sum())
+        rs['genes'] += G
+        rs['genes_refilled'] += int(refilled.sum())
+        rs['gene_refilled'][g0:g1] = refilled
+        d = _ht.eqtl_tables(good, gene_cols[g0:g1], cov, trt_all, mv.Nc_list, resampled=resample_rep)
+        n_tests = len(d.test_row)
+        no_group = ~good[d.test_row].any(axis=1)
+        is_rr = d.rr_test if resample_rep else np.zeros(n_tests, dtype=bool)
+        rr_idx, pl_idx = np.flatnonzero(is_rr), np.flatnonzero(~is_rr)
+        local = np.zeros(n_tests, dtype=np.int64)                 # a test's number inside its part
+        local[rr_idx], local[pl_idx] = np.arange(len(rr_idx)), np.arange(len(pl_idx))
+        stats = [np.full((n_tests, 8), np.nan), np.full((n_tests, 8), np.nan)]
+        parts = []
+        if len(pl_idx):                                           # plain tests: the weight rows as design contrasts, records only
+            st_m, st_v, rows_pl = bs.contrast_design(d.test_row[pl_idx], *_ht.weight_row_designs(d.test_row[pl_idx], d.Wmat[pl_idx], good))
+            stats[0][pl_idx], stats[1][pl_idx] = st_m, st_v
+            parts.append((~is_rr, rows_pl))
+        if len(rr_idx):                                           # resampled tests: gene-major, keyed by the gene's position
+            col_map, n_valid = _ht.surviving_cols(bs, good, num_boot)                                     # hypothesis_test.py:249-251
+            rr_ptr = np.concatenate([[0], np.cumsum(np.bincount(d.test_row[rr_idx], minlength=G))])
+            st_m, st_v, rows_rr = bs.cross_resampled_block(rr_ptr, d.tt_mat[rr_idx], good, d.row_mask, d.Mstack, mv.Nc_list,
+                                                           seed=fill_seed + 17, col_map=col_map, n_valid=n_valid,
+                                                           gene_key=np.arange(g0, g1, dtype=np.int64))
+            stats[0][rr_idx], stats[1][rr_idx] = st_m, st_v
+            parts.append((is_rr, rows_rr))
+        for which, tag in ((0, 'mean'), (1, 'var')):
+            stt = stats[which]
+            fetch = lambda idx, w=which: _ht.sliced_rows([(mem, local, functools.partial(r, w)) for mem, r in parts], idx, bs.ld)
+            p = _asl.asl_from_stats(stt, approx, fetch, num_cpus, resampling)
+            c0, se = stt[:, 0].copy(), stt[:, 1].copy()
+            c0[no_group], se[no_group], p[no_group] = np.nan, np.nan, np.nan                              # hypothesis_test.py:203-204
+            cols[tag + '_coef'].append(c0)
+            cols[tag + '_se'].append(se)
+            cols[tag + '_asl'].append(p)
+
+    st.refill_stats = dict(chains=0, chains_refilled=0, genes=0, genes_refilled=0, gene_refilled=np.zeros(G_all, dtype=bool))
+    st.last_bootstrap = None                   # (see ht_1d_moments: free the previous call's replicate rows first)
+    if max_rows is None:
+        max_rows = engine.auto_max_rows(num_boot + 1, arrays=2)
+    for c in _ht.chunks_1d(st, mv, num_boot, max(1, int(max_rows) // max(1, ng))):
+        run_chunk(c)
+    out = {k: (np.concatenate(v) if v else np.zeros(0)) for k, v in cols.items()}
+    n_snps = np.array([len(k) for k in gene_cols], dtype=np.int64)
+    flat = np.array([j for k in gene_cols for j in k], dtype=np.int64)
+    df = pd.DataFrame({'gene': np.repeat(np.asarray(names[:G_all], dtype=object), n_snps), 'snp': snp_names[flat]})
+    m['1d_ht_eqtl'] = dict(out, gene=df['gene'].values, snp=df['snp'].values)
+    df['de_coef'], df['de_se'], df['de_pval'] = out['mean_coef'], out['mean_se'], out['mean_asl']
+    df['dv_coef'], df['dv_se'], df['dv_pval'] = out['var_coef'], out['var_se'], out['var_asl']
+    return df
+
+
 def _posthoc_plan(m, treatment_col, control):
     """What ``ht_1d_posthoc`` tests: (``_ht.PosthocDesigns``, the level names).  Without ``treatment_col`` a level is a group
     (``control``: a group label or index); with it, a value of that label column (``control``: such a value, compared as a string)."""

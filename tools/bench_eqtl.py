@@ -1,0 +1,104 @@
+"""Time ``ht_1d_eqtl`` next to the equivalent ``ht_1d_moments(treatment_for_gene=..., resample_rep=True, approx=True)`` on a synthetic
+donor shape (one group per donor, a list of cis SNPs per gene): wall time of every repetition after the warm-up, median and
+spread, and the peak device memory of each call above what was allocated before it.  One JSON line per call and one with the
+ratio.  The two calls are fed the same inputs and the same ``np.random`` seed; in a one-chunk run their coefficients are compared.
+
+    python tools/bench_eqtl.py --groups 120 --genes 256 --snps 256 --num-boot 3000 --reps 5 --warmup 1
+"""
+
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import pandas as pd
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--groups", type=int, default=120)
+    ap.add_argument("--genes", type=int, default=256, help="genes of the synthetic matrix (the kept ones are fewer)")
+    ap.add_argument("--snps", type=int, default=256, help="cis SNPs per gene")
+    ap.add_argument("--pool", type=int, default=4096, help="genotype columns the lists are drawn from")
+    ap.add_argument("--cells-per-group", type=int, default=150)
+    ap.add_argument("--density", type=float, default=0.35)
+    ap.add_argument("--num-boot", type=int, default=3000)
+    ap.add_argument("--rng", default="fast")
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--parent-max-rows", type=int, default=None, help="max_rows of the ht_1d_moments call (default: its own choice)")
+    ap.add_argument("--max-rows", type=int, default=None, help="max_rows of the ht_1d_eqtl call")
+    ap.add_argument("--skip-parent", action="store_true")
+    args = ap.parse_args()
+
+    import torch
+
+    from scrna_parameter_estimation_amd import memento
+    from scrna_parameter_estimation_amd.synth import synth_adata
+
+    adata = synth_adata(args.groups * args.cells_per_group, args.genes, args.density, 1, args.groups, seed=7, dtype=np.float32)
+    memento.setup_memento(adata, q_column="q")
+    memento.create_groups(adata, label_columns=["rep"])
+    memento.compute_1d_moments(adata, min_perc_group=0.7)
+    gdf = memento.get_groups(adata)
+    st = adata.uns["memento"]["_hip"]
+    names = [g for g in memento.main._var_names(adata)[:len(st.gene_idx)]]
+    rng = np.random.default_rng(1)
+    cov = pd.DataFrame({"age": rng.normal(size=len(gdf)), "sex": rng.integers(0, 2, size=len(gdf)).astype(float)}, index=gdf.index)
+    geno = pd.DataFrame(rng.integers(0, 3, size=(len(gdf), args.pool)).astype(float), columns=[f"rs{j}" for j in range(args.pool)],
+                        index=gdf.index)
+    pairs = {g: [f"rs{j}" for j in rng.choice(args.pool, size=args.snps, replace=False)] for g in names}
+    n_tests = len(names) * args.snps
+    ld = args.num_boot + 1
+    shape = dict(groups=len(gdf), kept_genes=len(names), snps_per_gene=args.snps, n_tests=n_tests, num_boot=args.num_boot, rng=args.rng,
+                 plane_bytes=len(names) * len(gdf) * ld * 8, rows_bytes=n_tests * ld * 8, device=torch.cuda.get_device_name(0))
+    print(json.dumps(dict(shape=shape)), flush=True)
+
+    def eqtl():
+        return memento.ht_1d_eqtl(adata, geno, pairs, covariate=cov, num_boot=args.num_boot, rng=args.rng, fill_seed=3, approx=True,
+                                  resample_rep=True, max_rows=args.max_rows)
+
+    def parent():
+        memento.ht_1d_moments(adata, covariate=cov, treatment=geno, treatment_for_gene=pairs, num_boot=args.num_boot, verbose=0,
+                              rng=args.rng, fill_seed=3, approx=True, resample_rep=True, resampling="bootstrap",
+                              max_rows=args.parent_max_rows)
+        return memento.get_1d_ht_result(adata)
+
+    results, frames = {}, {}
+    for name, fn in (("ht_1d_eqtl", eqtl),) + (() if args.skip_parent else (("ht_1d_moments", parent),)):
+        times, peak = [], 0
+        for rep in range(args.warmup + args.reps):
+            st.last_bootstrap = None
+            torch.cuda.synchronize()
+            torch.cuda.reset_peak_memory_stats()
+            before = torch.cuda.memory_allocated()
+            np.random.seed(5)
+            t0 = time.perf_counter()
+            frames[name] = fn()
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t0
+            if rep >= args.warmup:
+                times.append(dt)
+                peak = max(peak, torch.cuda.max_memory_allocated() - before)
+        t = np.array(times)
+        results[name] = dict(call=name, seconds=[round(x, 4) for x in times], median_s=round(float(np.median(t)), 4),
+                             min_s=round(float(t.min()), 4), max_s=round(float(t.max()), 4), peak_device_bytes=int(peak),
+                             chunk_genes=int(st.last_chunk[1] - st.last_chunk[0]),
+                             max_rows=args.max_rows if name == "ht_1d_eqtl" else args.parent_max_rows)
+        print(json.dumps(results[name]), flush=True)
+    if len(results) == 2:
+        a, b = frames["ht_1d_eqtl"], frames["ht_1d_moments"]
+        one_chunk = all(r["chunk_genes"] == len(names) for r in results.values())
+        same = bool(one_chunk and np.array_equal(a["de_coef"].values, b["de_coef"].values, equal_nan=True)
+                    and np.array_equal(a["dv_coef"].values, b["dv_coef"].values, equal_nan=True))
+        print(json.dumps(dict(speedup_median=round(results["ht_1d_moments"]["median_s"] / results["ht_1d_eqtl"]["median_s"], 3),
+                              peak_ratio=round(results["ht_1d_moments"]["peak_device_bytes"] / max(1, results["ht_1d_eqtl"]["peak_device_bytes"]), 3),
+                              one_chunk=one_chunk, coefficients_equal=same if one_chunk else None)), flush=True)
+
+
+if __name__ == "__main__":
+    main()
