@@ -419,6 +419,30 @@ int mm_cross_resampled_block(const double *d_yt, int64_t ld, int32_t num_boot, i
                              int64_t n_genes, int32_t max_gene_tests, const double *d_tt, const uint8_t *d_good, const double *d_Nc,
                              const int16_t *d_rep, const int32_t *d_bcol, const int32_t *d_col_map, const int32_t *d_n_valid,
                              const int64_t *d_gene_key, uint64_t seed, int64_t n_tests, double *d_stats, void *stream);
+/* mm_cross_resampled_family: single-step max-T over the resampled tests of every gene, on ONE response plane -- the family of gene
+ * slot g is its tests [d_gene_ptr[g], d_gene_ptr[g + 1]), whose replicate slot c is one joint draw because the draws are keyed by
+ * the gene.  The tables are those of mm_cross_resampled_block (max_gene_tests is checked and otherwise unused); d_stats [n_tests][8]
+ * are the records that call wrote for this plane, of which only coef0 = d_stats[t][0] is read, and d_scale [n_tests] is 1 / se, or 0
+ * for a member without a test (engine.family_scale of the records).  The resampled row of a gene has the slots 0..nb - 1, nb =
+ * d_n_valid[g] - 1 (num_boot without d_n_valid): slot 0 is the observed coefficient, 1..nb - 1 the replicates of the record.
+ *   member j is INCLUDED when scale_j is finite and > 0 and coef0_j is finite;  t0_j = |coef0_j| * scale_j, NaN if not;
+ *   slot c >= 1 is FAMILY-VALID when the coefficient of every included member is not NaN there (the degenerate-column rule of
+ *   mm_cross_resampled, member by member);  M[c] = max_j |coef_j[c] - coef0_j| * scale_j over the included members, j ascending;
+ *   n_adj_j = #{family-valid c : M[c] > t0_j}  (NaN on either side is not counted).
+ * Every coefficient comes from the operations of mm_cross_resampled_keyed in their order (the tile routine of the block kernel),
+ * so M equals that rule applied in numpy to the rows mm_cross_resampled_keyed returns, bit for bit.
+ * Outputs: d_maxrow [n_genes][ld] = M (NaN at slot 0, at invalid slots and at nb..num_boot; cells past num_boot are not written);
+ * d_adj [n_tests][2] = (t0, n_adj), (NaN, 0) for a member that is not included; d_fam [n_genes][2] = (n_valid_family, n_included).
+ * A gene without tests, without a good group, with nb < 1 or without an included member gives an all-NaN row, (0, 0) and (NaN, 0).
+ * Two kernels: (gene, slab of ``slab`` slots) workgroups in which a thread owns a slot and walks the gene's tiles of 8 tests,
+ * evaluating each (test, slot) once, then one workgroup per gene for the counts.  slab = 0: the default (256); no output depends
+ * on it.  LDS: 76 bytes per group + 128 (n_groups <= 860).  The tables are trusted: validate them on the host
+ * (engine.cross_resampled_block). */
+int mm_cross_resampled_family(const double *d_yt, int64_t ld, int32_t num_boot, int32_t n_groups, const int32_t *d_gene_ptr,
+                              int64_t n_genes, int32_t max_gene_tests, const double *d_tt, const uint8_t *d_good, const double *d_Nc,
+                              const int16_t *d_rep, const int32_t *d_bcol, const int32_t *d_col_map, const int32_t *d_n_valid,
+                              const int64_t *d_gene_key, uint64_t seed, int64_t n_tests, const double *d_stats, const double *d_scale,
+                              int32_t slab, double *d_maxrow, double *d_adj, double *d_fam, void *stream);
 
 /* ---- guide-vs-control contrasts: sparse weight rows over the replicate groups ------------------------------------
  * test t: coef_c = sum_p design_w[p] * y[test_gene[t], design_grp[p]][c] over p in [design_ptr[d], design_ptr[d + 1]),

@@ -431,6 +431,71 @@ __device__ __forceinline__ void fill_records_each(F coef_at, int n_cols, double 
   }
 }
 
+// The coefficients of ONE TILE of XB_TT tests of a gene at replicate column c, shared by the record kernel
+// (k_cross_resampled_block) and the family kernel (k_cross_family_max): for every (test, column) the operations of k_cross_resampled
+// in its order.  tts [ng][XB_TT] test-minor, ncs [ng] and glist [n] are in LDS; rg / bg / cm (or NULL) are the gene's own tables.
+struct CrossTile {
+  const double *__restrict__ yt;
+  int64_t ld;
+  int32_t num_boot;
+  const double *tts, *ncs;
+  const int32_t *glist;
+  int n, nb;
+  int64_t row_base;
+  const int16_t *__restrict__ rg;
+  const int32_t *__restrict__ bg, *__restrict__ cm;
+  uint64_t gk, seed;
+  // row i of column c: the drawn group (index into yt / ncs / tts) and the response there
+  __device__ __forceinline__ void draw(int i, int c, int &j, double &y) const {
+    int r, bb;
+    if (c == 0) { r = i; bb = 0; }
+    else if (rg) { r = rg[(int64_t)i * num_boot + c]; bb = bg[(int64_t)i * num_boot + c]; }
+    else {
+      uint64_t h = rr_mix(seed ^ rr_mix((gk << 32) ^ ((uint64_t)i << 24) ^ (uint64_t)c));
+      r = (int)(h % (uint64_t)n);
+      bb = (int)(rr_mix(h) % (uint64_t)nb) + 1;
+    }
+    if (cm) bb = cm[bb];
+    j = glist[r];
+    y = yt[(row_base + j) * ld + bb];
+  }
+  __device__ __forceinline__ void coef_at(int c, double (&v)[XB_TT]) const {
+    double sw = 0.0, swy = 0.0, swa[XB_TT], amax[XB_TT];
+    for (int k = 0; k < XB_TT; k++) swa[k] = amax[k] = 0.0;
+    for (int i = 0; i < n; i++) {
+      int j;
+      double y;
+      draw(i, c, j, y);
+      double w = ncs[j];
+      const double *a = tts + (size_t)j * XB_TT;
+      sw += w; swy += w * y;
+      for (int k = 0; k < XB_TT; k++) {
+        swa[k] += w * a[k];
+        amax[k] = fmax(amax[k], fabs(a[k]));
+      }
+    }
+    double mB = swy / sw, ss[XB_TT], num[XB_TT];
+    for (int k = 0; k < XB_TT; k++) { swa[k] = swa[k] / sw; ss[k] = num[k] = 0.0; }      // swa is mA from here on
+    for (int i = 0; i < n; i++) {
+      int j;
+      double y;
+      draw(i, c, j, y);
+      double w = ncs[j], dy = y - mB;
+      const double *a = tts + (size_t)j * XB_TT;
+      for (int k = 0; k < XB_TT; k++) {
+        double da = a[k] - swa[k];
+        ss[k] += da * da * w;
+        num[k] += (da * w) * dy;
+      }
+    }
+    for (int k = 0; k < XB_TT; k++) {      // the degenerate-column rule of k_cross_resampled
+      double val = num[k] / sw / (ss[k] / sw);
+      if (ss[k] / sw <= 1e-24 * amax[k] * amax[k]) val = NAN;
+      v[k] = val;
+    }
+  }
+};
+
 __global__ __launch_bounds__(K9_THREADS, 2) void k_cross_resampled_block(
     const double *__restrict__ yt, int64_t ld, int32_t num_boot, int32_t n_groups, int32_t tiles_per_gene,
     const int32_t *__restrict__ gene_ptr /* [n_genes + 1] CSR over the tests */,
@@ -474,55 +539,8 @@ __global__ __launch_bounds__(K9_THREADS, 2) void k_cross_resampled_block(
   const int32_t *bg = bcol ? bcol + (int64_t)gene * n_groups * num_boot : nullptr;
   const int32_t *cm = col_map ? col_map + (int64_t)gene * (num_boot + 1) : nullptr;
   const uint64_t gk = gene_key ? (uint64_t)gene_key[gene] : (uint64_t)gene;
-  // row i of column c: the drawn group (index into yt / ncs / tts) and the response there
-  auto draw = [&](int i, int c, int &j, double &y) {
-    int r, bb;
-    if (c == 0) { r = i; bb = 0; }
-    else if (rg) { r = rg[(int64_t)i * num_boot + c]; bb = bg[(int64_t)i * num_boot + c]; }
-    else {
-      uint64_t h = rr_mix(seed ^ rr_mix((gk << 32) ^ ((uint64_t)i << 24) ^ (uint64_t)c));
-      r = (int)(h % (uint64_t)n);
-      bb = (int)(rr_mix(h) % (uint64_t)nb) + 1;
-    }
-    if (cm) bb = cm[bb];
-    j = glist[r];
-    y = yt[(row_base + j) * ld + bb];
-  };
-  auto coef_at = [&](int c, double(&v)[XB_TT]) {
-    double sw = 0.0, swy = 0.0, swa[XB_TT], amax[XB_TT];
-    for (int k = 0; k < XB_TT; k++) swa[k] = amax[k] = 0.0;
-    for (int i = 0; i < n; i++) {
-      int j;
-      double y;
-      draw(i, c, j, y);
-      double w = ncs[j];
-      const double *a = tts + (size_t)j * XB_TT;
-      sw += w; swy += w * y;
-      for (int k = 0; k < XB_TT; k++) {
-        swa[k] += w * a[k];
-        amax[k] = fmax(amax[k], fabs(a[k]));
-      }
-    }
-    double mB = swy / sw, ss[XB_TT], num[XB_TT];
-    for (int k = 0; k < XB_TT; k++) { swa[k] = swa[k] / sw; ss[k] = num[k] = 0.0; }      // swa is mA from here on
-    for (int i = 0; i < n; i++) {
-      int j;
-      double y;
-      draw(i, c, j, y);
-      double w = ncs[j], dy = y - mB;
-      const double *a = tts + (size_t)j * XB_TT;
-      for (int k = 0; k < XB_TT; k++) {
-        double da = a[k] - swa[k];
-        ss[k] += da * da * w;
-        num[k] += (da * w) * dy;
-      }
-    }
-    for (int k = 0; k < XB_TT; k++) {      // the degenerate-column rule of k_cross_resampled
-      double val = num[k] / sw / (ss[k] / sw);
-      if (ss[k] / sw <= 1e-24 * amax[k] * amax[k]) val = NAN;
-      v[k] = val;
-    }
-  };
+  const CrossTile tile{yt, ld, num_boot, tts, ncs, glist, n, nb, row_base, rg, bg, cm, gk, seed};
+  auto coef_at = [&](int c, double(&v)[XB_TT]) { tile.coef_at(c, v); };
   fill_records_each<XB_TT>(coef_at, nb, st, nt, red);
 }
 
@@ -791,6 +809,153 @@ __global__ __launch_bounds__(K9_THREADS) void k_family_maxt1(const double *__res
   const double *const yp[1] = {y};
   family_maxt<1>(yp, ld, num_boot, n_groups, m > 0 ? test_row[t0] : 0, t0, m, test_design, design_ptr, design_grp, design_w, scale, stage_cap,
                  maxrow + f * ld, adj + (int64_t)t0 * 2, fam + f * 2, sm, red);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Single-step max-T over the resampled tests of a GENE (ht_1d_eqtl(adjust=True)): family_maxt's rule on the resampled row, whose
+// slots 0..nb - 1 are what fill_records sees in k_cross_resampled_block (slot 0 observed, 1..nb - 1 the replicates).  The draws of
+// slot c are keyed by the gene, so slot c of all its tests is one joint draw.  With coef0_j = stats[j][0] (the block kernel's
+// record: coef_at(0) bit for bit) and scale_j from the host (1 / se, 0 for no test), member j is INCLUDED when scale_j is finite and
+// > 0 and coef0_j is finite; slot c >= 1 is family-valid when no included member is NaN there (the degenerate-column rule, member by
+// member), and there  M[c] = max_j |coef_j[c] - coef0_j| * scale_j  over the included members, j ascending.
+//
+// k_cross_family_max: one workgroup per (gene, slab of ``slab`` slots).  A thread owns a slot and walks the gene's tiles of XB_TT
+// tests: every tile is staged as in the block kernel, with (coef0, effective scale) beside it, and evaluated by CrossTile::coef_at
+// ONCE per (test, slot); the running maximum and the verdict stay in registers.  A tile without an included member is skipped (the
+// partial last tile's unused slots have scale 0: never members).  Writes maxrow[gene][c] for c <= num_boot: NaN at slot 0, at
+// invalid slots and at nb..num_boot, and everywhere for a gene without tests, without a good group, with nb < 1 or without an
+// included member.  Nothing depends on ``slab``.  LDS: 76 bytes per group + 128.
+// XF_SLAB = one round of the workgroup: at 3000 replicates a gene is 12 workgroups, so that a chunk of 263 genes fills the 256 CUs
+// several times over where one workgroup per gene would leave one each (a choice, not a measurement).
+#define XF_SLAB K9_THREADS
+__global__ __launch_bounds__(K9_THREADS) void k_cross_family_max(
+    const double *__restrict__ yt, int64_t ld, int32_t num_boot, int32_t n_groups, int32_t slabs, int32_t slab,
+    const int32_t *__restrict__ gene_ptr, const double *__restrict__ tt, const uint8_t *__restrict__ good, const double *__restrict__ Nc,
+    const int16_t *__restrict__ rep, const int32_t *__restrict__ bcol, const int32_t *__restrict__ col_map,
+    const int32_t *__restrict__ n_valid, const int64_t *__restrict__ gene_key, uint64_t seed, const double *__restrict__ stats,
+    const double *__restrict__ scale, double *__restrict__ maxrow) {
+  extern __shared__ double sm[];
+  double *tts = sm;                                        // [ng][XB_TT], test-minor
+  double *ncs = sm + (size_t)XB_TT * n_groups;             // [ng]
+  double *c0s = ncs + n_groups, *scs = c0s + XB_TT;        // [XB_TT] coef0 and the effective scale (0: not a member) of the tile
+  int32_t *glist = (int32_t *)(scs + XB_TT);               // [ng] indices of good groups
+  __shared__ int n_good_s;
+  const int gene = (int)(blockIdx.x / (unsigned)slabs);
+  const int64_t c_lo = (int64_t)(blockIdx.x % (unsigned)slabs) * slab;
+  const int64_t c_hi = c_lo + slab < (int64_t)num_boot + 1 ? c_lo + slab : (int64_t)num_boot + 1;
+  const int64_t t_lo = gene_ptr[gene], t_hi = gene_ptr[gene + 1];
+  const uint8_t *gd = good + (int64_t)gene * n_groups;
+  if (threadIdx.x == 0) {
+    int ng = 0;
+    for (int j = 0; j < n_groups; j++)
+      if (gd[j]) glist[ng++] = j;
+    n_good_s = ng;
+  }
+  for (int j = threadIdx.x; j < n_groups; j += K9_THREADS) ncs[j] = Nc[j];
+  __syncthreads();
+  const int n = n_good_s;
+  const int nb = n_valid ? n_valid[gene] - 1 : num_boot;
+  const bool live = t_hi > t_lo && n > 0 && nb >= 1;
+  const int64_t row_base = (int64_t)gene * n_groups;
+  const int16_t *rg = rep ? rep + (int64_t)gene * n_groups * num_boot : nullptr;
+  const int32_t *bg = bcol ? bcol + (int64_t)gene * n_groups * num_boot : nullptr;
+  const int32_t *cm = col_map ? col_map + (int64_t)gene * (num_boot + 1) : nullptr;
+  const uint64_t gk = gene_key ? (uint64_t)gene_key[gene] : (uint64_t)gene;
+  const CrossTile tile{yt, ld, num_boot, tts, ncs, glist, n, nb, row_base, rg, bg, cm, gk, seed};
+  double *out = maxrow + (int64_t)gene * ld;
+  for (int64_t cb = c_lo; cb < c_hi; cb += K9_THREADS) {      // (uniform) K9_THREADS slots of the slab at a time
+    const int64_t c = cb + threadIdx.x;
+    const bool act = live && c < c_hi && c >= 1 && c < nb;   // a slot with replicates: the only ones coef_at is asked for
+    const bool walk = live && cb < nb && cb + K9_THREADS > 1;   // (uniform) some slot of this round is one
+    double mx = -INFINITY;
+    bool ok = act, any = false;
+    for (int64_t t0 = t_lo; walk && t0 < t_hi; t0 += XB_TT) {
+      const int nt = (int)(t_hi - t0 < XB_TT ? t_hi - t0 : XB_TT);
+      __syncthreads();                                       // the previous tile has been read
+      for (int j = threadIdx.x; j < n_groups; j += K9_THREADS)
+        for (int k = 0; k < XB_TT; k++) tts[(size_t)j * XB_TT + k] = k < nt ? tt[(t0 + k) * n_groups + j] : 0.0;
+      if (threadIdx.x < XB_TT) {
+        const int k = threadIdx.x;
+        double c0 = k < nt ? stats[(t0 + k) * 8] : NAN, sc = k < nt ? scale[t0 + k] : 0.0;
+        c0s[k] = c0;
+        scs[k] = (isfinite(sc) && sc > 0.0 && isfinite(c0)) ? sc : 0.0;
+      }
+      __syncthreads();
+      bool tile_any = false;
+      for (int k = 0; k < XB_TT; k++) tile_any = tile_any || scs[k] > 0.0;
+      if (!tile_any) continue;                               // (uniform: read from LDS)
+      any = true;
+      if (act) {
+        double v[XB_TT];
+        tile.coef_at((int)c, v);
+        for (int k = 0; k < XB_TT; k++) {
+          if (scs[k] > 0.0) {
+            ok = ok && v[k] == v[k];
+            mx = fmax(mx, fabs(v[k] - c0s[k]) * scs[k]);
+          }
+        }
+      }
+    }
+    if (c < c_hi) out[c] = (ok && any) ? mx : NAN;
+  }
+}
+
+// k_cross_family_count: one workgroup per gene, after k_cross_family_max.  adj[t] = (t0, n_adj) with t0_j = |coef0_j| * scale_j (NaN
+// where the member is not included) and n_adj_j = #{c : M[c] > t0_j} (NaN on either side is not counted); fam[gene] =
+// (n_valid_family = the non-NaN slots of the row, n_included).  The counts as in step 3 of family_maxt: waves over blocks of
+// FM_BLOCK members, lanes over slots, ballots, no reduction across waves.
+__global__ __launch_bounds__(K9_THREADS) void k_cross_family_count(int64_t ld, int32_t num_boot, int32_t n_groups,
+                                                                   const int32_t *__restrict__ gene_ptr, const uint8_t *__restrict__ good,
+                                                                   const int32_t *__restrict__ n_valid, const double *__restrict__ stats,
+                                                                   const double *__restrict__ scale, const double *__restrict__ maxrow,
+                                                                   double *__restrict__ adj, double *__restrict__ fam) {
+  __shared__ double red[K9_THREADS / 64];
+  const int gene = blockIdx.x;
+  const int64_t t_lo = gene_ptr[gene];
+  const int m = (int)(gene_ptr[gene + 1] - t_lo);
+  const int nb = n_valid ? n_valid[gene] - 1 : num_boot;
+  double n_good = 0.0;
+  for (int j = threadIdx.x; j < n_groups; j += K9_THREADS) n_good += good[(int64_t)gene * n_groups + j] ? 1.0 : 0.0;
+  n_good = wg_sum(n_good, red);
+  const bool live = m > 0 && n_good > 0.0 && nb >= 1;
+  double ninc = 0.0;
+  for (int j = threadIdx.x; j < m; j += K9_THREADS) {
+    double c0 = stats[(t_lo + j) * 8], sc = scale[t_lo + j];
+    bool inc = live && isfinite(sc) && sc > 0.0 && isfinite(c0);
+    adj[(t_lo + j) * 2] = inc ? fabs(c0) * sc : NAN;
+    if (inc) ninc += 1.0;
+  }
+  __threadfence_block();
+  ninc = wg_sum(ninc, red);                                  // (its barriers also publish the adj cells)
+  const double *r = maxrow + (int64_t)gene * ld;
+  double nval = 0.0;
+  for (int c = 1 + threadIdx.x; c <= num_boot; c += K9_THREADS) {
+    double x = r[c];
+    if (x == x) nval += 1.0;
+  }
+  nval = wg_sum(nval, red);
+  if (threadIdx.x == 0) { fam[(int64_t)gene * 2] = nval; fam[(int64_t)gene * 2 + 1] = ninc; }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int j0 = wave * FM_BLOCK; j0 < m; j0 += FM_BLOCK * (K9_THREADS / 64)) {
+    double t[FM_BLOCK];
+    uint32_t cnt[FM_BLOCK];
+#pragma unroll
+    for (int i = 0; i < FM_BLOCK; i++) {
+      t[i] = j0 + i < m ? adj[(t_lo + j0 + i) * 2] : NAN;
+      cnt[i] = 0;
+    }
+    for (int cb = 1; cb <= num_boot; cb += 64) {
+      int c = cb + lane;
+      double x = c <= num_boot ? r[c] : NAN;
+#pragma unroll
+      for (int i = 0; i < FM_BLOCK; i++) cnt[i] += (uint32_t)__popcll(__ballot(x > t[i]));      // (NaN on either side: not counted)
+    }
+    if (lane == 0) {
+#pragma unroll
+      for (int i = 0; i < FM_BLOCK; i++)
+        if (j0 + i < m) adj[(t_lo + j0 + i) * 2 + 1] = (double)cnt[i];
+    }
+  }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1272,6 +1437,32 @@ int mm_cross_resampled_block(const double *d_yt, int64_t ld, int32_t num_boot, i
   hipLaunchKernelGGL(k_cross_resampled_block, dim3((unsigned)(n_genes * tiles)), dim3(K9_THREADS), shm, (hipStream_t)stream, d_yt, ld,
                      num_boot, n_groups, tiles, d_gene_ptr, d_tt, d_good, d_Nc, d_rep, d_bcol, d_col_map, d_n_valid, d_gene_key, seed,
                      d_stats);
+  MM_LAUNCH_CHECK();
+  return MM_OK;
+}
+
+int mm_cross_resampled_family(const double *d_yt, int64_t ld, int32_t num_boot, int32_t n_groups, const int32_t *d_gene_ptr,
+                              int64_t n_genes, int32_t max_gene_tests, const double *d_tt, const uint8_t *d_good, const double *d_Nc,
+                              const int16_t *d_rep, const int32_t *d_bcol, const int32_t *d_col_map, const int32_t *d_n_valid,
+                              const int64_t *d_gene_key, uint64_t seed, int64_t n_tests, const double *d_stats, const double *d_scale,
+                              int32_t slab, double *d_maxrow, double *d_adj, double *d_fam, void *stream) {
+  int rc = cross_resampled_args(d_yt, ld, num_boot, n_groups, d_gene_ptr, d_tt, d_good, d_Nc, d_rep, d_bcol, d_col_map, d_n_valid, n_tests,
+                                d_stats);
+  if (rc != MM_OK) return rc;
+  MM_ARG(d_scale && d_maxrow && d_adj && d_fam);
+  MM_ARG(n_genes >= 0 && max_gene_tests >= 0 && (int64_t)max_gene_tests <= n_tests && slab >= 0);
+  if (n_genes == 0) return MM_OK;
+  if (slab == 0) slab = XF_SLAB;
+  int64_t slabs = ((int64_t)num_boot + slab) / slab;      // ceil((num_boot + 1) / slab)
+  MM_ARG(n_genes * slabs < 2147483647LL);
+  size_t shm = (size_t)n_groups * (XB_TT * 8 + 12) + 2 * XB_TT * 8 + 8;
+  MM_ARG(shm <= 64 * 1024);
+  hipLaunchKernelGGL(k_cross_family_max, dim3((unsigned)(n_genes * slabs)), dim3(K9_THREADS), shm, (hipStream_t)stream, d_yt, ld, num_boot,
+                     n_groups, (int32_t)slabs, slab, d_gene_ptr, d_tt, d_good, d_Nc, d_rep, d_bcol, d_col_map, d_n_valid, d_gene_key, seed,
+                     d_stats, d_scale, d_maxrow);
+  MM_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_cross_family_count, dim3((unsigned)n_genes), dim3(K9_THREADS), 0, (hipStream_t)stream, ld, num_boot, n_groups,
+                     d_gene_ptr, d_good, d_n_valid, d_stats, d_scale, d_maxrow, d_adj, d_fam);
   MM_LAUNCH_CHECK();
   return MM_OK;
 }

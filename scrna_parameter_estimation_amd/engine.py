@@ -1125,9 +1125,23 @@ class Bootstrap1D:
         ``contract_resampled`` gives for the same tests -- and ``rows(which, idx, to_host=True, out=None)``, the contract of
         ``contrast_design``'s closure: the coefficient rows of the tests ``idx`` on plane ``which``, from the per-test kernel on
         that subset with the same draws (mm_cross_resampled_keyed).  The closure holds the scratch."""
-        (st_m, st_v), rows = _cross_resampled_block([self.ym, self.yv], self.ld, self.B, self.ng, self.n_tested, gene_ptr, tt, good, gene_mask,
-                                                    M, Nc, rep, bcol, seed, col_map, n_valid, gene_key)
+        (st_m, st_v), rows, _ = _cross_resampled_block([self.ym, self.yv], self.ld, self.B, self.ng, self.n_tested, gene_ptr, tt, good,
+                                                       gene_mask, M, Nc, rep, bcol, seed, col_map, n_valid, gene_key)
         return st_m, st_v, rows
+
+    def cross_resampled_family(self, gene_ptr, tt, good, gene_mask, M, Nc, rep=None, bcol=None, seed=0, col_map=None, n_valid=None,
+                               gene_key=None):
+        """``cross_resampled_block`` with the single-step max-T over every gene's tests (mm_cross_resampled_family): the same call,
+        the same records and ``rows``, and a third closure ``family(scale, slab=None)`` on the uploaded tables and the one residual
+        scratch.  ``scale`` [n_tests][2] holds 1 / se of every test on the mean and the variability plane, 0 for a member without
+        a test (``family_scale(st_m, st_v)``).  It returns ``maxrow`` (a device tensor [n_genes][ld] per plane: the maximum row of
+        every gene, NaN in slot 0, the slots that are not family-valid and the slots from nb on), ``adj`` (host [n_tests][2][2]:
+        t0, n_adj) and ``fam`` (host [n_genes][2][2]: n_valid_family, n_included), the layout of ``family_maxt``; beyond ``maxrow``
+        it allocates nothing plane-sized, and the plane the scratch already holds is taken first.  ``slab``: the slots a
+        workgroup takes (default: the kernel's); no number depends on it."""
+        (st_m, st_v), rows, family = _cross_resampled_block([self.ym, self.yv], self.ld, self.B, self.ng, self.n_tested, gene_ptr, tt, good,
+                                                            gene_mask, M, Nc, rep, bcol, seed, col_map, n_valid, gene_key)
+        return st_m, st_v, rows, family
 
 
 def _rows_out(out, n, ld):
@@ -1406,7 +1420,8 @@ def _block_tables(B, ng, n_genes,gene_ptr, tt, good, gene_mask, M, Nc, rep, bcol
 
 
 def _cross_resampled_block(planes, ld, B, ng, n_genes, gene_ptr, tt, good, gene_mask, M, Nc, rep, bcol, seed, col_map, n_valid, gene_key):
-    """``Bootstrap1D.cross_resampled_block``: the records of every plane of ``planes`` and the ``rows`` closure."""
+    """``Bootstrap1D.cross_resampled_block`` / ``cross_resampled_family``: the records of every plane of ``planes``, the ``rows``
+    closure and the ``family`` closure."""
     torch = _torch()
     s = _stream()
     gene_ptr, tt, good, gene_mask, M, Nc, rep, bcol, n_valid, gene_key = _block_tables(B, ng, n_genes, gene_ptr, tt, good, gene_mask, M, Nc,
@@ -1430,13 +1445,14 @@ def _cross_resampled_block(planes, ld, B, ng, n_genes, gene_ptr, tt, good, gene_
             _lib.call("mm_residualize", P(planes[which]), P(yt), ld, ld, ng, n_genes, P(d_gm), P(d_M), _stream())
         held[0] = which
 
-    stats = []
+    stats, d_stats = [], []
     for which in range(len(planes)):
         residualise(which)
         st = empty((max(1, n_tests), 8), torch.float64)
         _lib.call("mm_cross_resampled_block", P(yt), ld, B, ng, P(d_ptr), n_genes, max_tests, P(d_tt), P(d_good), P(d_nc), P(d_rep), P(d_bcol),
                   P(d_cm), P(d_nv), P(d_key), seed, n_tests, P(st), s)
         stats.append(host(st)[:n_tests])
+        d_stats.append(st)                         # (the family pass reads coef0 from the records on the device)
 
     def rows(which, idx, to_host=True, out=None):
         idx = np.asarray(idx, dtype=np.int64)
@@ -1448,7 +1464,29 @@ def _cross_resampled_block(planes, ld, B, ng, n_genes, gene_ptr, tt, good, gene_
                   seed, len(idx), P(out), P(scrap), _stream())
         return host(out)[: len(idx)] if to_host else out[: len(idx)]
 
-    return stats, rows
+    def family(scale, slab=None):
+        scale = np.asarray(scale, dtype=np.float64)
+        if scale.shape != (n_tests, len(planes)):
+            raise ValueError(f"cross_resampled_family: scale must be [n_tests][{len(planes)}], one column per plane of records")
+        slab = 0 if slab is None else int(slab)
+        if not 0 <= slab < 2 ** 31:
+            raise ValueError("cross_resampled_family: slab must be a positive number of slots (None: the kernel's default)")
+        maxrow = [None] * len(planes)
+        adj, fam = np.zeros((n_tests, len(planes), 2)), np.zeros((n_genes, len(planes), 2))
+        order = sorted(range(len(planes)), key=lambda w: w != held[0])      # the plane the scratch holds first
+        for which in order:
+            residualise(which)
+            maxrow[which] = empty((max(1, n_genes), ld), torch.float64)
+            d_adj, d_fam = empty((max(1, n_tests), 2), torch.float64), empty((max(1, n_genes), 2), torch.float64)
+            d_sc = _up(np.ascontiguousarray(scale[:, which]))
+            _lib.call("mm_cross_resampled_family", P(yt), ld, B, ng, P(d_ptr), n_genes, max_tests, P(d_tt), P(d_good), P(d_nc), P(d_rep),
+                      P(d_bcol), P(d_cm), P(d_nv), P(d_key), seed, n_tests, P(d_stats[which]), P(d_sc), slab, P(maxrow[which]), P(d_adj),
+                      P(d_fam), _stream())
+            adj[:, which], fam[:, which] = host(d_adj)[:n_tests], host(d_fam)[:n_genes]
+            maxrow[which] = maxrow[which][:n_genes]
+        return maxrow, adj, fam
+
+    return stats, rows, family
 
 
 # =================================================================================================

@@ -25,7 +25,7 @@ import scipy.stats as stats
 from scipy.sparse import csr_matrix
 
 from .. import engine
-from . import _ht, _strict1d
+from . import _ht, _strict1d, util
 from . import asl as _asl
 from . import design as _design
 
@@ -818,7 +818,7 @@ def ht_1d_joint(adata, treatment, covariate=None, num_boot=10000, rng='replay', 
 
 
 def ht_1d_eqtl(adata, genotypes, gene_snp_pairs, covariate=None, num_boot=5000, num_cpus=1, rng='replay', fill_seed=0, max_rows=None,
-               approx=False, resampling='bootstrap', resample_rep=False, **not_offered):
+               approx=False, resampling='bootstrap', resample_rep=False, adjust=False, **not_offered):
     """cis-eQTL scan: every kept gene against its own list of SNPs, hundreds per gene (the reference's largest analysis,
     analysis/lupus/run_memento.py:29-52, :84-109: one group per donor, ``treatment_for_gene``, ``resample_rep=True``).
 
@@ -836,14 +836,29 @@ def ht_1d_eqtl(adata, genotypes, gene_snp_pairs, covariate=None, num_boot=5000, 
     demand in slices of a bounded scratch.  The device draws of ``resample_rep`` are keyed by the gene's position among the kept
     genes, so -- unlike ``ht_1d_moments`` there -- the result does not depend on ``max_rows``.
 
+    ``adjust=True`` adds a GENE-LEVEL correction over the gene's whole SNP list, the one FastQTL / TensorQTL make with
+    permutations: the single-step max-T of ``ht_1d_posthoc`` with the gene's tests as the family (centred null, so it needs
+    ``resampling='bootstrap'``: ValueError otherwise).  Replicate column c of all SNPs of a gene is one joint draw -- the plain
+    tests share the gene's replicate rows, the resampled tests share the draws, which are keyed by the gene -- so with
+    M[c] = max_j |coef_j[c] - coef_j[0]| / se_j over the included members (those with a test) on the columns valid for all of
+    them,  p_adj_j = (1 + #{c : M[c] > |coef_j[0]| / se_j}) / (1 + n_valid);  ``*_pval_adj`` is max(p_adj_j, the SNP's own p-value)
+    and NaN for a member without a test, ``n_family`` the number of included members (mean plane; ``var_n_family`` in ``uns``).
+    With ``resample_rep=False`` the family is all the gene's tests (``family_maxt`` on the weight-row designs); with
+    ``resample_rep=True`` it is the gene's RESAMPLED tests (mm_cross_resampled_family), and the few plain tests of such a call
+    (treatment all ones) are no joint draws with them: they get NaN adjusted values and do not count in ``n_family``.  A family
+    never spans gene chunks and ``max_rows`` changes no bit.  ``get_eqtl_gene_result`` turns the result into an eGene table.
+
     Not offered: ``strict``, ``ci``, ``max_boot``, ``treatment_for_gene`` (TypeError), and a gene-sharded run (NotImplementedError).
 
     Returns a DataFrame (gene, snp, de_coef, de_se, de_pval, dv_coef, dv_se, dv_pval), gene-major over the kept genes, each gene's
-    SNPs in its list order; the arrays go to ``uns['memento']['1d_ht_eqtl']``."""
+    SNPs in its list order; with ``adjust=True`` also de_pval_adj, dv_pval_adj and n_family, after these.  The arrays go to
+    ``uns['memento']['1d_ht_eqtl']`` (``mean_asl_adj``, ``var_asl_adj``, ``n_family``, ``var_n_family`` for the adjusted ones)."""
     if not_offered:
         raise TypeError(f"ht_1d_eqtl does not offer {sorted(not_offered)[0]!r}")
     _ht.check_args(rng, resampling=resampling)
-    resample_rep, approx = bool(resample_rep), bool(approx)
+    resample_rep, approx, adjust = bool(resample_rep), bool(approx), bool(adjust)
+    if adjust and resampling != 'bootstrap':
+        raise ValueError("ht_1d_eqtl(adjust=True) needs resampling='bootstrap': the max-T null is centred on the observed coefficient")
     m = adata.uns['memento']
     st = m['_hip']
     comm = getattr(st, 'comm', None)
@@ -864,6 +879,8 @@ def ht_1d_eqtl(adata, genotypes, gene_snp_pairs, covariate=None, num_boot=5000, 
     fill_pos = (np.asarray(st.shard, dtype=np.int64)[st.gene_idx] if getattr(st, 'shard', None) is not None
                 else np.asarray(st.gene_idx, dtype=np.int64))
     cols = {k: [] for k in ('mean_coef', 'mean_se', 'mean_asl', 'var_coef', 'var_se', 'var_asl')}
+    if adjust:
+        cols.update({k: [] for k in ('mean_asl_adj', 'mean_n_family', 'var_asl_adj', 'var_n_family')})
 
     def run_chunk(c):
         g0, g1, G, bs = c.g0, c.g1, c.G, c.bs
@@ -885,18 +902,31 @@ def ht_1d_eqtl(adata, genotypes, gene_snp_pairs, covariate=None, num_boot=5000, 
         local[rr_idx], local[pl_idx] = np.arange(len(rr_idx)), np.arange(len(pl_idx))
         stats = [np.full((n_tests, 8), np.nan), np.full((n_tests, 8), np.nan)]
         parts = []
+        # adjust: (t0, n_adj) per test and plane, (n_valid_family, n_included) per gene and plane; a test outside the family is (NaN, 0)
+        adj, fam = np.zeros((n_tests, 2, 2)), np.zeros((G, 2, 2))
+        adj[:, :, 0] = np.nan
         if len(pl_idx):                                           # plain tests: the weight rows as design contrasts, records only
-            st_m, st_v, rows_pl = bs.contrast_design(d.test_row[pl_idx], *_ht.weight_row_designs(d.test_row[pl_idx], d.Wmat[pl_idx], good))
+            tables = (d.test_row[pl_idx], *_ht.weight_row_designs(d.test_row[pl_idx], d.Wmat[pl_idx], good))
+            st_m, st_v, rows_pl = bs.contrast_design(*tables)
             stats[0][pl_idx], stats[1][pl_idx] = st_m, st_v
             parts.append((~is_rr, rows_pl))
+            if adjust and not resample_rep:                       # the family of a gene: all its tests, on the rows they share
+                scale = engine.family_scale(st_m, st_v)
+                _, adj, fam = bs.family_maxt(d.gene_ptr, *tables, scale)
+                st.last_eqtl = SimpleNamespace(gene_ptr=d.gene_ptr, tables=tables, scale=scale, adj=adj, fam=fam, rows=rows_pl, n_valid=None)
         if len(rr_idx):                                           # resampled tests: gene-major, keyed by the gene's position
             col_map, n_valid = _ht.surviving_cols(bs, good, num_boot)                                     # hypothesis_test.py:249-251
             rr_ptr = np.concatenate([[0], np.cumsum(np.bincount(d.test_row[rr_idx], minlength=G))])
-            st_m, st_v, rows_rr = bs.cross_resampled_block(rr_ptr, d.tt_mat[rr_idx], good, d.row_mask, d.Mstack, mv.Nc_list,
-                                                           seed=fill_seed + 17, col_map=col_map, n_valid=n_valid,
-                                                           gene_key=np.arange(g0, g1, dtype=np.int64))
+            block = bs.cross_resampled_family if adjust else bs.cross_resampled_block
+            st_m, st_v, rows_rr, *family = block(rr_ptr, d.tt_mat[rr_idx], good, d.row_mask, d.Mstack, mv.Nc_list, seed=fill_seed + 17,
+                                                 col_map=col_map, n_valid=n_valid, gene_key=np.arange(g0, g1, dtype=np.int64))
             stats[0][rr_idx], stats[1][rr_idx] = st_m, st_v
             parts.append((is_rr, rows_rr))
+            if adjust:                                            # the family of a gene: its resampled tests, which share the draws
+                scale = engine.family_scale(st_m, st_v)
+                _, adj_rr, fam = family[0](scale)
+                adj[rr_idx] = adj_rr
+                st.last_eqtl = SimpleNamespace(gene_ptr=rr_ptr, rr_idx=rr_idx, scale=scale, adj=adj_rr, fam=fam, rows=rows_rr, n_valid=n_valid)
         for which, tag in ((0, 'mean'), (1, 'var')):
             stt = stats[which]
             fetch = lambda idx, w=which: _ht.sliced_rows([(mem, local, functools.partial(r, w)) for mem, r in parts], idx, bs.ld)
@@ -906,20 +936,62 @@ def ht_1d_eqtl(adata, genotypes, gene_snp_pairs, covariate=None, num_boot=5000, 
             cols[tag + '_coef'].append(c0)
             cols[tag + '_se'].append(se)
             cols[tag + '_asl'].append(p)
+            if adjust:
+                p_adj, n_family, _ = _ht.adjusted_columns(p, adj[:, which], fam[:, which], np.diff(d.gene_ptr))
+                cols[tag + '_asl_adj'].append(p_adj)
+                cols[tag + '_n_family'].append(n_family)
 
     st.refill_stats = dict(chains=0, chains_refilled=0, genes=0, genes_refilled=0, gene_refilled=np.zeros(G_all, dtype=bool))
-    st.last_bootstrap = None                   # (see ht_1d_moments: free the previous call's replicate rows first)
+    st.last_bootstrap = st.last_eqtl = None    # (see ht_1d_moments: free the previous call's replicate rows first)
     if max_rows is None:
         max_rows = engine.auto_max_rows(num_boot + 1, arrays=2)
     for c in _ht.chunks_1d(st, mv, num_boot, max(1, int(max_rows) // max(1, ng))):
         run_chunk(c)
-    out = {k: (np.concatenate(v) if v else np.zeros(0)) for k, v in cols.items()}
+    out = {k: (np.concatenate(v) if v else np.zeros(0, dtype=np.int64 if k.endswith('_n_family') else np.float64)) for k, v in cols.items()}
+    if adjust:
+        out['n_family'] = out.pop('mean_n_family')
     n_snps = np.array([len(k) for k in gene_cols], dtype=np.int64)
     flat = np.array([j for k in gene_cols for j in k], dtype=np.int64)
     df = pd.DataFrame({'gene': np.repeat(np.asarray(names[:G_all], dtype=object), n_snps), 'snp': snp_names[flat]})
     m['1d_ht_eqtl'] = dict(out, gene=df['gene'].values, snp=df['snp'].values)
     df['de_coef'], df['de_se'], df['de_pval'] = out['mean_coef'], out['mean_se'], out['mean_asl']
     df['dv_coef'], df['dv_se'], df['dv_pval'] = out['var_coef'], out['var_se'], out['var_asl']
+    if adjust:
+        df['de_pval_adj'], df['dv_pval_adj'], df['n_family'] = out['mean_asl_adj'], out['var_asl_adj'], out['n_family']
+    return df
+
+
+def get_eqtl_gene_result(adata):
+    """The eGene table of the last ``ht_1d_eqtl(adjust=True)`` call (host only): one row per kept gene that has a SNP list, in the
+    order of the tests.  ``gene``, ``n_snps`` (the list's length), ``n_family`` (included members, mean plane); per plane
+    (``de`` / ``dv``) the LEAD SNP -- the included member with the largest |coef| / se, the first of equals --, its
+    ``*_coef``, ``*_se``, ``*_pval``, the gene-level ``*_gene_pval`` = the smallest ``*_pval_adj`` of the gene (the lead SNP's, unless
+    the tail fit of another member's own p-value lifted it), and ``*_gene_qval`` = Benjamini-Hochberg (``util._fdrcorrect``) over
+    the genes.  A gene without an included member on a plane has None / NaN there and q = 1.  ValueError if the stored result
+    has no adjusted arrays."""
+    ht = adata.uns['memento'].get('1d_ht_eqtl')
+    if ht is None or 'mean_asl_adj' not in ht:
+        raise ValueError("get_eqtl_gene_result needs the result of ht_1d_eqtl(adjust=True)")
+    gene = np.asarray(ht['gene'], dtype=object)
+    first = np.flatnonzero(np.r_[True, gene[1:] != gene[:-1]]) if len(gene) else np.zeros(0, dtype=np.int64)
+    ptr = np.r_[first, len(gene)]
+    df = pd.DataFrame({'gene': gene[first], 'n_snps': np.diff(ptr), 'n_family': np.asarray(ht['n_family'])[first]})
+    for name, tag in (('de', 'mean'), ('dv', 'var')):
+        coef, se, p, p_adj = (np.asarray(ht[tag + k], dtype=np.float64) for k in ('_coef', '_se', '_asl', '_asl_adj'))
+        with np.errstate(invalid='ignore', divide='ignore'):
+            t0 = np.where(np.isnan(p_adj), np.nan, np.abs(coef) * (1.0 / se))
+        lead = np.full(len(first), -1, dtype=np.int64)
+        gene_p = np.full(len(first), np.nan)
+        for k, (lo, hi) in enumerate(zip(ptr[:-1], ptr[1:])):
+            if not np.isnan(t0[lo:hi]).all():
+                lead[k] = lo + np.nanargmax(t0[lo:hi])
+                gene_p[k] = np.nanmin(p_adj[lo:hi])
+        has = lead >= 0
+        df[name + '_lead_snp'] = [ht['snp'][j] if ok else None for j, ok in zip(lead, has)]
+        for col, a in (('_coef', coef), ('_se', se), ('_pval', p)):
+            df[name + col] = np.where(has, a[np.maximum(lead, 0)] if len(a) else np.nan, np.nan)
+        df[name + '_gene_pval'] = gene_p
+        df[name + '_gene_qval'] = util._fdrcorrect(gene_p)
     return df
 
 

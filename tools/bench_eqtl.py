@@ -2,8 +2,11 @@
 donor shape (one group per donor, a list of cis SNPs per gene): wall time of every repetition after the warm-up, median and
 spread, and the peak device memory of each call above what was allocated before it.  One JSON line per call and one with the
 ratio.  The two calls are fed the same inputs and the same ``np.random`` seed; in a one-chunk run their coefficients are compared.
+``--adjust`` also times ``ht_1d_eqtl(adjust=True)`` (the gene-level max-T).  The calls ALTERNATE within every repetition, so that a
+drift of the device hits them alike.
 
     python tools/bench_eqtl.py --groups 120 --genes 256 --snps 256 --num-boot 3000 --reps 5 --warmup 1
+    python tools/bench_eqtl.py --groups 120 --genes 300 --snps 256 --num-boot 3000 --adjust --skip-parent
 """
 
 import argparse
@@ -33,6 +36,7 @@ def main():
     ap.add_argument("--parent-max-rows", type=int, default=None, help="max_rows of the ht_1d_moments call (default: its own choice)")
     ap.add_argument("--max-rows", type=int, default=None, help="max_rows of the ht_1d_eqtl call")
     ap.add_argument("--skip-parent", action="store_true")
+    ap.add_argument("--adjust", action="store_true", help="also time ht_1d_eqtl(adjust=True)")
     args = ap.parse_args()
 
     import torch
@@ -58,9 +62,9 @@ def main():
                  plane_bytes=len(names) * len(gdf) * ld * 8, rows_bytes=n_tests * ld * 8, device=torch.cuda.get_device_name(0))
     print(json.dumps(dict(shape=shape)), flush=True)
 
-    def eqtl():
+    def eqtl(**kw):
         return memento.ht_1d_eqtl(adata, geno, pairs, covariate=cov, num_boot=args.num_boot, rng=args.rng, fill_seed=3, approx=True,
-                                  resample_rep=True, max_rows=args.max_rows)
+                                  resample_rep=True, max_rows=args.max_rows, **kw)
 
     def parent():
         memento.ht_1d_moments(adata, covariate=cov, treatment=geno, treatment_for_gene=pairs, num_boot=args.num_boot, verbose=0,
@@ -69,10 +73,16 @@ def main():
         return memento.get_1d_ht_result(adata)
 
     results, frames = {}, {}
-    for name, fn in (("ht_1d_eqtl", eqtl),) + (() if args.skip_parent else (("ht_1d_moments", parent),)):
-        times, peak = [], 0
-        for rep in range(args.warmup + args.reps):
-            st.last_bootstrap = None
+    calls = [("ht_1d_eqtl", eqtl)]
+    if args.adjust:
+        calls.append(("ht_1d_eqtl_adjust", lambda: eqtl(adjust=True)))
+    if not args.skip_parent:
+        calls.append(("ht_1d_moments", parent))
+    times, peak, chunk = {n: [] for n, _ in calls}, {n: 0 for n, _ in calls}, {}
+    for rep in range(args.warmup + args.reps):
+        for name, fn in calls:
+            st.last_bootstrap = st.last_eqtl = None
+            frames.pop(name, None)
             torch.cuda.synchronize()
             torch.cuda.reset_peak_memory_stats()
             before = torch.cuda.memory_allocated()
@@ -81,16 +91,23 @@ def main():
             frames[name] = fn()
             torch.cuda.synchronize()
             dt = time.perf_counter() - t0
+            chunk[name] = int(st.last_chunk[1] - st.last_chunk[0])
             if rep >= args.warmup:
-                times.append(dt)
-                peak = max(peak, torch.cuda.max_memory_allocated() - before)
-        t = np.array(times)
-        results[name] = dict(call=name, seconds=[round(x, 4) for x in times], median_s=round(float(np.median(t)), 4),
-                             min_s=round(float(t.min()), 4), max_s=round(float(t.max()), 4), peak_device_bytes=int(peak),
-                             chunk_genes=int(st.last_chunk[1] - st.last_chunk[0]),
-                             max_rows=args.max_rows if name == "ht_1d_eqtl" else args.parent_max_rows)
+                times[name].append(dt)
+                peak[name] = max(peak[name], torch.cuda.max_memory_allocated() - before)
+    for name, _ in calls:
+        t = np.array(times[name])
+        results[name] = dict(call=name, seconds=[round(x, 4) for x in times[name]], median_s=round(float(np.median(t)), 4),
+                             min_s=round(float(t.min()), 4), max_s=round(float(t.max()), 4), peak_device_bytes=int(peak[name]),
+                             chunk_genes=chunk[name], max_rows=args.parent_max_rows if name == "ht_1d_moments" else args.max_rows)
         print(json.dumps(results[name]), flush=True)
-    if len(results) == 2:
+    if args.adjust:
+        a, b = frames["ht_1d_eqtl"], frames["ht_1d_eqtl_adjust"]
+        print(json.dumps(dict(adjust_over_plain_median=round(results["ht_1d_eqtl_adjust"]["median_s"] / results["ht_1d_eqtl"]["median_s"], 3),
+                              shared_columns_equal=bool(a.equals(b[list(a.columns)])),
+                              genes_with_adjusted_p=int(np.isfinite(memento.get_eqtl_gene_result(adata)["de_gene_pval"]).sum())
+                              if calls[-1][0] != "ht_1d_moments" else None)), flush=True)
+    if not args.skip_parent:
         a, b = frames["ht_1d_eqtl"], frames["ht_1d_moments"]
         one_chunk = all(r["chunk_genes"] == len(names) for r in results.values())
         same = bool(one_chunk and np.array_equal(a["de_coef"].values, b["de_coef"].values, equal_nan=True)
