@@ -419,6 +419,33 @@ int mm_cross_resampled_block(const double *d_yt, int64_t ld, int32_t num_boot, i
                              int64_t n_genes, int32_t max_gene_tests, const double *d_tt, const uint8_t *d_good, const double *d_Nc,
                              const int16_t *d_rep, const int32_t *d_bcol, const int32_t *d_col_map, const int32_t *d_n_valid,
                              const int64_t *d_gene_key, uint64_t seed, int64_t n_tests, double *d_stats, void *stream);
+/* A COVARIATE PER TEST for the gene-major tests (ht_1d_eqtl(interaction=): the genotype main effect beside the tested
+ * genotype x context).  d_zt [n_tests][n_groups] holds z = M g, the covariate residualised on the shared design like the response;
+ * residualising on [shared | g] is then the rank-one step
+ *   y_t[j][c] = y[j][c] - z[j] * beta[c],   beta[c] = sum_j Nc_j z_j y[j][c] / sum_j Nc_j z_j^2   (good groups, ascending; a zero
+ * denominator -- z == 0: the host found g inside the shared span -- gives beta = 0).  The tiles are those of
+ * mm_cross_resampled_block, numbered gene-major: tile = gene * ceil(max_gene_tests / 8) + (tile of 8 tests within the gene), and
+ * the entry points take a RANGE [tile_lo, tile_hi) of them so that the caller bounds the scratch d_beta
+ * [tile_hi - tile_lo][ld][8] doubles (test-minor: a draw reads one 64-byte line); a tile past its gene's last test leaves its
+ * block unwritten.  mm_cross_cov_beta writes beta for the columns 0..num_boot of the range (columns across threads, the weights in
+ * LDS).  mm_cross_resampled_block_cov launches it and then, on the same stream, the record kernel, which is
+ * mm_cross_resampled_block with test k of a tile reading y - z_k * beta_k: d_stats gets the records of the tests of the range's
+ * tiles and no other record is touched.  LDS: 140 bytes per group (n_groups <= 468).  d_zt == 0 gives the records of
+ * mm_cross_resampled_block bit for bit.  mm_residualize_rank1 materialises y_t for a LIST of tests (test l of gene d_test_gene[l],
+ * covariate row l of d_zt [n_list][n_groups]) into d_out [n_list][n_groups][ld] (columns 0..num_boot; NaN on the groups that are
+ * not good) with the same weights, beta and subtraction (the library is built with -ffp-contract=off):
+ * mm_cross_resampled_keyed on d_out, test l on row block l with the tables of its gene, gives the coefficient rows of the record
+ * kernel bit for bit.  The tables are trusted: validate them on the host (engine.cross_resampled_block(zt=...)). */
+int mm_cross_cov_beta(const double *d_yt, int64_t ld, int32_t num_boot, int32_t n_groups, const int32_t *d_gene_ptr, int64_t n_genes,
+                      int32_t max_gene_tests, const double *d_zt, const uint8_t *d_good, const double *d_Nc, int64_t n_tests,
+                      int64_t tile_lo, int64_t tile_hi, double *d_beta, void *stream);
+int mm_cross_resampled_block_cov(const double *d_yt, int64_t ld, int32_t num_boot, int32_t n_groups, const int32_t *d_gene_ptr,
+                                 int64_t n_genes, int32_t max_gene_tests, const double *d_tt, const double *d_zt, const uint8_t *d_good,
+                                 const double *d_Nc, const int16_t *d_rep, const int32_t *d_bcol, const int32_t *d_col_map,
+                                 const int32_t *d_n_valid, const int64_t *d_gene_key, uint64_t seed, int64_t n_tests, int64_t tile_lo,
+                                 int64_t tile_hi, double *d_beta, double *d_stats, void *stream);
+int mm_residualize_rank1(const double *d_yt, int64_t ld, int32_t num_boot, int32_t n_groups, const int32_t *d_test_gene,
+                         const double *d_zt, const uint8_t *d_good, const double *d_Nc, int64_t n_list, double *d_out, void *stream);
 /* mm_cross_resampled_family: single-step max-T over the resampled tests of every gene, on ONE response plane -- the family of gene
  * slot g is its tests [d_gene_ptr[g], d_gene_ptr[g + 1]), whose replicate slot c is one joint draw because the draws are keyed by
  * the gene.  The tables are those of mm_cross_resampled_block (max_gene_tests is checked and otherwise unused); d_stats [n_tests][8]

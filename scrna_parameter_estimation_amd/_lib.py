@@ -97,6 +97,12 @@ _SIGS = {
                                   c_void_p, c_void_p, c_uint64, c_int64, c_void_p, c_void_p, c_void_p], ctypes.c_int),
     "mm_cross_resampled_block": ([c_void_p, c_int64, c_int32, c_int32, c_void_p, c_int64, c_int32] + [c_void_p] * 8 +
                                  [c_uint64, c_int64, c_void_p, c_void_p], ctypes.c_int),
+    "mm_cross_cov_beta": ([c_void_p, c_int64, c_int32, c_int32, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_int64,
+                           c_int64, c_void_p, c_void_p], ctypes.c_int),
+    "mm_cross_resampled_block_cov": ([c_void_p, c_int64, c_int32, c_int32, c_void_p, c_int64, c_int32] + [c_void_p] * 9 +
+                                     [c_uint64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p], ctypes.c_int),
+    "mm_residualize_rank1": ([c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p],
+                             ctypes.c_int),
     "mm_cross_resampled_family": ([c_void_p, c_int64, c_int32, c_int32, c_void_p, c_int64, c_int32] + [c_void_p] * 8 +
                                   [c_uint64, c_int64, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p], ctypes.c_int),
     "mm_extract_cols": ([c_void_p] * 6 + [c_int32, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p], ctypes.c_int),

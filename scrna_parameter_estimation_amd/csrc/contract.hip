@@ -431,10 +431,56 @@ __device__ __forceinline__ void fill_records_each(F coef_at, int n_cols, double 
   }
 }
 
+// ------------------------------------------------------------------------------------------------
+// A covariate PER TEST (ht_1d_eqtl(interaction=): the genotype main effect g_s beside the tested g_s * ctx).  With M the shared
+// residual maker and z = M g_s, residualising on [shared | g_s] is M followed by a rank-one step (Frisch-Waugh):
+//   y_t[j][c] = (M y)[j][c] - z[j] * beta[c],   beta[c] = sum_j Nc_j z_j (M y)[j][c] / sum_j Nc_j z_j^2   over the good groups.
+// The three routines below are the only place where the weights, beta and y_t are formed: k_cross_cov_beta (beta of a tile into a
+// scratch), k_cross_resampled_block_cov (reads that scratch) and k_residualize_rank1 (materialises y_t) share them, so under
+// -ffp-contract=off the response a test sees is the same number on every route.
+// cov_weights: IN PLACE, zs[j * NT + k] (z of test k at group j) becomes Nc_j z_j / sum Nc z^2; the sum runs over the good groups
+// in ascending order, a zero sum gives zero weights (beta = 0: the host passes z = 0 for a covariate inside the shared span).
+// Thread k < NT does test k; the caller puts a barrier on either side.
+template <int NT>
+__device__ __forceinline__ void cov_weights(double *zs, const double *__restrict__ Nc, const int32_t *glist, int n) {
+  if (threadIdx.x < NT) {
+    const int k = threadIdx.x;
+    double den = 0.0;
+    for (int q = 0; q < n; q++) {
+      int j = glist[q];
+      double z = zs[(size_t)j * NT + k];
+      den += Nc[j] * z * z;
+    }
+    for (int q = 0; q < n; q++) {
+      int j = glist[q];
+      double z = zs[(size_t)j * NT + k];
+      zs[(size_t)j * NT + k] = den > 0.0 ? Nc[j] * z / den : 0.0;
+    }
+  }
+}
+// cov_beta: beta of NT tests at replicate column c from the weights wz [ng][NT]: good groups in ascending order, one read of the
+// residualised plane per group (columns across threads: coalesced).
+template <int NT>
+__device__ __forceinline__ void cov_beta(const double *__restrict__ yt, int64_t ld, int64_t row_base, const int32_t *glist, int n,
+                                         const double *wz, int c, double (&b)[NT]) {
+  for (int k = 0; k < NT; k++) b[k] = 0.0;
+  for (int q = 0; q < n; q++) {
+    int j = glist[q];
+    double y = yt[(row_base + j) * ld + c];
+    const double *w = wz + (size_t)j * NT;
+    for (int k = 0; k < NT; k++) b[k] += w[k] * y;
+  }
+}
+__device__ __forceinline__ double cov_residual(double y, double z, double beta) { return y - z * beta; }
+
 // The coefficients of ONE TILE of XB_TT tests of a gene at replicate column c, shared by the record kernel
 // (k_cross_resampled_block) and the family kernel (k_cross_family_max): for every (test, column) the operations of k_cross_resampled
 // in its order.  tts [ng][XB_TT] test-minor, ncs [ng] and glist [n] are in LDS; rg / bg / cm (or NULL) are the gene's own tables.
-struct CrossTile {
+// COV (k_cross_resampled_block_cov): every test has a covariate of its own, taken out of the shared response by a rank-one step:
+// test k reads y - zts[j][k] * beta[bb][k] where the others read y (zts [ng][XB_TT] in LDS, beta [ld][XB_TT] of this tile from
+// k_cross_cov_beta), so the response sums swy and mB are per test.
+template <bool COV>
+struct CrossTileT {
   const double *__restrict__ yt;
   int64_t ld;
   int32_t num_boot;
@@ -445,9 +491,11 @@ struct CrossTile {
   const int16_t *__restrict__ rg;
   const int32_t *__restrict__ bg, *__restrict__ cm;
   uint64_t gk, seed;
-  // row i of column c: the drawn group (index into yt / ncs / tts) and the response there
-  __device__ __forceinline__ void draw(int i, int c, int &j, double &y) const {
-    int r, bb;
+  const double *zts = nullptr;
+  const double *__restrict__ beta = nullptr;
+  // row i of column c: the drawn group (index into yt / ncs / tts), the response there and the replicate column it came from
+  __device__ __forceinline__ void draw(int i, int c, int &j, double &y, int &bb) const {
+    int r;
     if (c == 0) { r = i; bb = 0; }
     else if (rg) { r = rg[(int64_t)i * num_boot + c]; bb = bg[(int64_t)i * num_boot + c]; }
     else {
@@ -460,30 +508,41 @@ struct CrossTile {
     y = yt[(row_base + j) * ld + bb];
   }
   __device__ __forceinline__ void coef_at(int c, double (&v)[XB_TT]) const {
-    double sw = 0.0, swy = 0.0, swa[XB_TT], amax[XB_TT];
+    constexpr int NY = COV ? XB_TT : 1;      // response sums: one per test under COV, else one for the tile
+    double sw = 0.0, swy[NY], swa[XB_TT], amax[XB_TT];
+    for (int k = 0; k < NY; k++) swy[k] = 0.0;
     for (int k = 0; k < XB_TT; k++) swa[k] = amax[k] = 0.0;
     for (int i = 0; i < n; i++) {
-      int j;
+      int j, bb;
       double y;
-      draw(i, c, j, y);
+      draw(i, c, j, y, bb);
       double w = ncs[j];
       const double *a = tts + (size_t)j * XB_TT;
-      sw += w; swy += w * y;
+      sw += w;
+      if (COV) {
+        const double *z = zts + (size_t)j * XB_TT, *b = beta + (size_t)bb * XB_TT;
+        for (int k = 0; k < NY; k++) swy[k] += w * cov_residual(y, z[k], b[k]);
+      } else {
+        swy[0] += w * y;
+      }
       for (int k = 0; k < XB_TT; k++) {
         swa[k] += w * a[k];
         amax[k] = fmax(amax[k], fabs(a[k]));
       }
     }
-    double mB = swy / sw, ss[XB_TT], num[XB_TT];
+    double ss[XB_TT], num[XB_TT];
+    for (int k = 0; k < NY; k++) swy[k] = swy[k] / sw;                                     // swy is mB from here on
     for (int k = 0; k < XB_TT; k++) { swa[k] = swa[k] / sw; ss[k] = num[k] = 0.0; }      // swa is mA from here on
     for (int i = 0; i < n; i++) {
-      int j;
+      int j, bb;
       double y;
-      draw(i, c, j, y);
-      double w = ncs[j], dy = y - mB;
+      draw(i, c, j, y, bb);
+      double w = ncs[j], dy = y - swy[0];
       const double *a = tts + (size_t)j * XB_TT;
+      const double *z = COV ? zts + (size_t)j * XB_TT : nullptr, *b = COV ? beta + (size_t)bb * XB_TT : nullptr;
       for (int k = 0; k < XB_TT; k++) {
         double da = a[k] - swa[k];
+        if (COV) dy = cov_residual(y, z[k], b[k]) - swy[k < NY ? k : 0];
         ss[k] += da * da * w;
         num[k] += (da * w) * dy;
       }
@@ -495,6 +554,7 @@ struct CrossTile {
     }
   }
 };
+using CrossTile = CrossTileT<false>;
 
 __global__ __launch_bounds__(K9_THREADS, 2) void k_cross_resampled_block(
     const double *__restrict__ yt, int64_t ld, int32_t num_boot, int32_t n_groups, int32_t tiles_per_gene,
@@ -542,6 +602,135 @@ __global__ __launch_bounds__(K9_THREADS, 2) void k_cross_resampled_block(
   const CrossTile tile{yt, ld, num_boot, tts, ncs, glist, n, nb, row_base, rg, bg, cm, gk, seed};
   auto coef_at = [&](int c, double(&v)[XB_TT]) { tile.coef_at(c, v); };
   fill_records_each<XB_TT>(coef_at, nb, st, nt, red);
+}
+
+// beta of the tiles tile_lo + blockIdx.x / col_tiles: beta[(blockIdx.x / col_tiles)][c][k] for the columns c <= num_boot, 256 a
+// workgroup.  A tile past its gene's last test writes nothing (nobody reads its block).
+__global__ __launch_bounds__(K9_THREADS) void k_cross_cov_beta(
+    const double *__restrict__ yt, int64_t ld, int32_t num_boot, int32_t n_groups, int32_t tiles_per_gene, int32_t tile_lo,
+    int32_t col_tiles, const int32_t *__restrict__ gene_ptr, const double *__restrict__ zt /* [n_tests][ng] */,
+    const uint8_t *__restrict__ good, const double *__restrict__ Nc, double *__restrict__ beta /* [tiles][ld][XB_TT] */) {
+  extern __shared__ double sm[];
+  double *wz = sm;                                         // [ng][XB_TT], test-minor: z, then the weights
+  int32_t *glist = (int32_t *)(sm + (size_t)XB_TT * n_groups);
+  __shared__ int n_good_s;
+  const unsigned slot = blockIdx.x / (unsigned)col_tiles, tile = (unsigned)tile_lo + slot;
+  const int c = (int)(blockIdx.x % (unsigned)col_tiles) * K9_THREADS + (int)threadIdx.x;
+  const int gene = (int)(tile / (unsigned)tiles_per_gene);
+  const int64_t t0 = (int64_t)gene_ptr[gene] + (int64_t)(tile % (unsigned)tiles_per_gene) * XB_TT;
+  const int64_t t1 = gene_ptr[gene + 1];
+  if (t0 >= t1) return;
+  const int nt = (int)(t1 - t0 < XB_TT ? t1 - t0 : XB_TT);
+  const uint8_t *gd = good + (int64_t)gene * n_groups;
+  if (threadIdx.x == 0) {
+    int ng = 0;
+    for (int j = 0; j < n_groups; j++)
+      if (gd[j]) glist[ng++] = j;
+    n_good_s = ng;
+  }
+  for (int j = threadIdx.x; j < n_groups; j += K9_THREADS)
+    for (int k = 0; k < XB_TT; k++) wz[(size_t)j * XB_TT + k] = k < nt ? zt[(t0 + k) * n_groups + j] : 0.0;
+  __syncthreads();
+  const int n = n_good_s;
+  cov_weights<XB_TT>(wz, Nc, glist, n);
+  __syncthreads();
+  if (c > num_boot) return;
+  double b[XB_TT];
+  cov_beta<XB_TT>(yt, ld, (int64_t)gene * n_groups, glist, n, wz, c, b);
+  double *out = beta + ((size_t)slot * ld + c) * XB_TT;
+  for (int k = 0; k < XB_TT; k++) out[k] = b[k];
+}
+
+// k_cross_resampled_block with a covariate per test (zt [n_tests][ng] beside tt): the tiles tile_lo + blockIdx.x, whose beta blocks
+// ([ld][XB_TT] each) a launch of k_cross_cov_beta over the same range wrote before this one on the same stream.  The set-up is
+// k_cross_resampled_block's, kept apart from it so that that kernel's code does not move; the tile's zt rows sit in LDS beside tts.
+__global__ __launch_bounds__(K9_THREADS, 2) void k_cross_resampled_block_cov(
+    const double *__restrict__ yt, int64_t ld, int32_t num_boot, int32_t n_groups, int32_t tiles_per_gene, int32_t tile_lo,
+    const int32_t *__restrict__ gene_ptr, const double *__restrict__ tt, const double *__restrict__ zt,
+    const uint8_t *__restrict__ good, const double *__restrict__ Nc, const int16_t *__restrict__ rep, const int32_t *__restrict__ bcol,
+    const int32_t *__restrict__ col_map, const int32_t *__restrict__ n_valid, const int64_t *__restrict__ gene_key, uint64_t seed,
+    const double *__restrict__ beta, double *__restrict__ stats) {
+  extern __shared__ double sm[];
+  double *tts = sm;                                        // [ng][XB_TT], test-minor
+  double *zts = sm + (size_t)XB_TT * n_groups;             // [ng][XB_TT], test-minor
+  double *ncs = zts + (size_t)XB_TT * n_groups;            // [ng]
+  int32_t *glist = (int32_t *)(ncs + n_groups);            // [ng] indices of good groups
+  __shared__ double red[K9_THREADS / 64];
+  __shared__ int n_good_s;
+  const unsigned tile = (unsigned)tile_lo + blockIdx.x;
+  const int gene = (int)(tile / (unsigned)tiles_per_gene);
+  const int64_t t0 = (int64_t)gene_ptr[gene] + (int64_t)(tile % (unsigned)tiles_per_gene) * XB_TT;
+  const int64_t t1 = gene_ptr[gene + 1];
+  if (t0 >= t1) return;
+  const int nt = (int)(t1 - t0 < XB_TT ? t1 - t0 : XB_TT);
+  const uint8_t *gd = good + (int64_t)gene * n_groups;
+  if (threadIdx.x == 0) {
+    int ng = 0;
+    for (int j = 0; j < n_groups; j++)
+      if (gd[j]) glist[ng++] = j;
+    n_good_s = ng;
+  }
+  for (int j = threadIdx.x; j < n_groups; j += K9_THREADS) {
+    for (int k = 0; k < XB_TT; k++) {
+      tts[(size_t)j * XB_TT + k] = k < nt ? tt[(t0 + k) * n_groups + j] : 0.0;
+      zts[(size_t)j * XB_TT + k] = k < nt ? zt[(t0 + k) * n_groups + j] : 0.0;
+    }
+    ncs[j] = Nc[j];
+  }
+  __syncthreads();
+  const int n = n_good_s;
+  double *st[XB_TT];
+  for (int k = 0; k < XB_TT; k++) st[k] = stats + (t0 + (k < nt ? k : 0)) * 8;
+  const int64_t row_base = (int64_t)gene * n_groups;
+  const int nb = n_valid ? n_valid[gene] - 1 : num_boot;
+  if (n == 0 || nb < 1) {
+    for (int k = 0; k < nt; k++) write_nan_record(st[k]);
+    return;
+  }
+  const int16_t *rg = rep ? rep + (int64_t)gene * n_groups * num_boot : nullptr;
+  const int32_t *bg = bcol ? bcol + (int64_t)gene * n_groups * num_boot : nullptr;
+  const int32_t *cm = col_map ? col_map + (int64_t)gene * (num_boot + 1) : nullptr;
+  const uint64_t gk = gene_key ? (uint64_t)gene_key[gene] : (uint64_t)gene;
+  const CrossTileT<true> tile_c{yt, ld, num_boot, tts, ncs, glist, n, nb, row_base, rg, bg, cm, gk, seed, zts,
+                                beta + (size_t)blockIdx.x * ld * XB_TT};
+  auto coef_at = [&](int c, double(&v)[XB_TT]) { tile_c.coef_at(c, v); };
+  fill_records_each<XB_TT>(coef_at, nb, st, nt, red);
+}
+
+// y_t of a short LIST of tests, materialised: out[l][j][c] = yt[gene_l][j][c] - z_l[j] * beta_l[c] on the good groups of
+// gene_l = test_gene[l] and the columns c <= num_boot (NaN on the other groups), with the weights, beta and the subtraction of
+// the routines above -- mm_cross_resampled_keyed on ``out`` with test l on row block l then gives, bit for bit, the coefficients
+// that k_cross_resampled_block_cov forms for that test.  One workgroup per (l, 256 columns).
+__global__ __launch_bounds__(K9_THREADS) void k_residualize_rank1(
+    const double *__restrict__ yt, int64_t ld, int32_t num_boot, int32_t n_groups, int32_t col_tiles,
+    const int32_t *__restrict__ test_gene /* [n_list] */, const double *__restrict__ zt /* [n_list][ng] */,
+    const uint8_t *__restrict__ good, const double *__restrict__ Nc, double *__restrict__ out /* [n_list][ng][ld] */) {
+  extern __shared__ double sm[];
+  double *zs = sm;                                         // [ng] z
+  double *wz = sm + n_groups;                              // [ng] the weights
+  int32_t *glist = (int32_t *)(wz + n_groups);
+  __shared__ int n_good_s;
+  const int64_t l = blockIdx.x / (unsigned)col_tiles;
+  const int c = (int)(blockIdx.x % (unsigned)col_tiles) * K9_THREADS + (int)threadIdx.x;
+  const int gene = test_gene[l];
+  const uint8_t *gd = good + (int64_t)gene * n_groups;
+  if (threadIdx.x == 0) {
+    int ng = 0;
+    for (int j = 0; j < n_groups; j++)
+      if (gd[j]) glist[ng++] = j;
+    n_good_s = ng;
+  }
+  for (int j = threadIdx.x; j < n_groups; j += K9_THREADS) zs[j] = wz[j] = zt[l * n_groups + j];
+  __syncthreads();
+  const int n = n_good_s;
+  cov_weights<1>(wz, Nc, glist, n);
+  __syncthreads();
+  if (c > num_boot) return;
+  const int64_t row_base = (int64_t)gene * n_groups;
+  double b[1];
+  cov_beta<1>(yt, ld, row_base, glist, n, wz, c, b);
+  for (int j = 0; j < n_groups; j++)
+    out[(l * n_groups + j) * ld + c] = gd[j] ? cov_residual(yt[(row_base + j) * ld + c], zs[j], b[0]) : NAN;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1437,6 +1626,74 @@ int mm_cross_resampled_block(const double *d_yt, int64_t ld, int32_t num_boot, i
   hipLaunchKernelGGL(k_cross_resampled_block, dim3((unsigned)(n_genes * tiles)), dim3(K9_THREADS), shm, (hipStream_t)stream, d_yt, ld,
                      num_boot, n_groups, tiles, d_gene_ptr, d_tt, d_good, d_Nc, d_rep, d_bcol, d_col_map, d_n_valid, d_gene_key, seed,
                      d_stats);
+  MM_LAUNCH_CHECK();
+  return MM_OK;
+}
+
+// the tile range of the per-test-covariate entry points: [tile_lo, tile_hi) among the n_genes * ceil(max_gene_tests / XB_TT) tiles
+static int cross_cov_tiles(int64_t n_genes, int32_t max_gene_tests, int64_t n_tests, int64_t tile_lo, int64_t tile_hi, int32_t *tiles) {
+  MM_ARG(n_genes >= 0 && max_gene_tests >= 0 && (int64_t)max_gene_tests <= n_tests);
+  *tiles = (max_gene_tests + XB_TT - 1) / XB_TT;
+  MM_ARG(n_genes * *tiles < 2147483647LL && tile_lo >= 0 && tile_lo <= tile_hi && tile_hi <= n_genes * *tiles);
+  return MM_OK;
+}
+
+int mm_cross_cov_beta(const double *d_yt, int64_t ld, int32_t num_boot, int32_t n_groups, const int32_t *d_gene_ptr, int64_t n_genes,
+                      int32_t max_gene_tests, const double *d_zt, const uint8_t *d_good, const double *d_Nc, int64_t n_tests,
+                      int64_t tile_lo, int64_t tile_hi, double *d_beta, void *stream) {
+  MM_ARG(d_yt && d_gene_ptr && d_zt && d_good && d_Nc && d_beta);
+  MM_ARG(n_tests >= 0 && n_tests < 2147483647LL && n_groups > 0 && n_groups <= 32767 && num_boot > 1 && ld >= (int64_t)num_boot + 1);
+  int32_t tiles;
+  int rc = cross_cov_tiles(n_genes, max_gene_tests, n_tests, tile_lo, tile_hi, &tiles);
+  if (rc != MM_OK) return rc;
+  if (tile_hi == tile_lo) return MM_OK;
+  int32_t col_tiles = (num_boot + K9_THREADS) / K9_THREADS;      // ceil((num_boot + 1) / K9_THREADS)
+  MM_ARG((tile_hi - tile_lo) * col_tiles < 2147483647LL);
+  size_t shm = (size_t)n_groups * (XB_TT * 8 + 4) + 8;
+  MM_ARG(shm <= 64 * 1024);
+  hipLaunchKernelGGL(k_cross_cov_beta, dim3((unsigned)((tile_hi - tile_lo) * col_tiles)), dim3(K9_THREADS), shm, (hipStream_t)stream, d_yt,
+                     ld, num_boot, n_groups, tiles, (int32_t)tile_lo, col_tiles, d_gene_ptr, d_zt, d_good, d_Nc, d_beta);
+  MM_LAUNCH_CHECK();
+  return MM_OK;
+}
+
+int mm_cross_resampled_block_cov(const double *d_yt, int64_t ld, int32_t num_boot, int32_t n_groups, const int32_t *d_gene_ptr,
+                                 int64_t n_genes, int32_t max_gene_tests, const double *d_tt, const double *d_zt, const uint8_t *d_good,
+                                 const double *d_Nc, const int16_t *d_rep, const int32_t *d_bcol, const int32_t *d_col_map,
+                                 const int32_t *d_n_valid, const int64_t *d_gene_key, uint64_t seed, int64_t n_tests, int64_t tile_lo,
+                                 int64_t tile_hi, double *d_beta, double *d_stats, void *stream) {
+  int rc = cross_resampled_args(d_yt, ld, num_boot, n_groups, d_gene_ptr, d_tt, d_good, d_Nc, d_rep, d_bcol, d_col_map, d_n_valid, n_tests,
+                                d_stats);
+  if (rc != MM_OK) return rc;
+  MM_ARG(d_zt && d_beta);
+  int32_t tiles;
+  rc = cross_cov_tiles(n_genes, max_gene_tests, n_tests, tile_lo, tile_hi, &tiles);
+  if (rc != MM_OK) return rc;
+  if (tile_hi == tile_lo) return MM_OK;
+  size_t shm = (size_t)n_groups * (2 * XB_TT * 8 + 12) + 8;
+  MM_ARG(shm <= 64 * 1024);
+  // beta first, by a launch of its own: the record kernel reads it through a const __restrict__ pointer
+  rc = mm_cross_cov_beta(d_yt, ld, num_boot, n_groups, d_gene_ptr, n_genes, max_gene_tests, d_zt, d_good, d_Nc, n_tests, tile_lo, tile_hi,
+                         d_beta, stream);
+  if (rc != MM_OK) return rc;
+  hipLaunchKernelGGL(k_cross_resampled_block_cov, dim3((unsigned)(tile_hi - tile_lo)), dim3(K9_THREADS), shm, (hipStream_t)stream, d_yt, ld,
+                     num_boot, n_groups, tiles, (int32_t)tile_lo, d_gene_ptr, d_tt, d_zt, d_good, d_Nc, d_rep, d_bcol, d_col_map, d_n_valid,
+                     d_gene_key, seed, d_beta, d_stats);
+  MM_LAUNCH_CHECK();
+  return MM_OK;
+}
+
+int mm_residualize_rank1(const double *d_yt, int64_t ld, int32_t num_boot, int32_t n_groups, const int32_t *d_test_gene,
+                         const double *d_zt, const uint8_t *d_good, const double *d_Nc, int64_t n_list, double *d_out, void *stream) {
+  MM_ARG(d_yt && d_test_gene && d_zt && d_good && d_Nc && d_out && d_out != d_yt);
+  MM_ARG(n_list >= 0 && n_groups > 0 && n_groups <= 32767 && num_boot > 1 && ld >= (int64_t)num_boot + 1);
+  if (n_list == 0) return MM_OK;
+  int32_t col_tiles = (num_boot + K9_THREADS) / K9_THREADS;
+  MM_ARG(n_list * col_tiles < 2147483647LL);
+  size_t shm = (size_t)n_groups * 20 + 8;
+  MM_ARG(shm <= 64 * 1024);
+  hipLaunchKernelGGL(k_residualize_rank1, dim3((unsigned)(n_list * col_tiles)), dim3(K9_THREADS), shm, (hipStream_t)stream, d_yt, ld, num_boot,
+                     n_groups, col_tiles, d_test_gene, d_zt, d_good, d_Nc, d_out);
   MM_LAUNCH_CHECK();
   return MM_OK;
 }

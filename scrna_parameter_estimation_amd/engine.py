@@ -1117,20 +1117,27 @@ class Bootstrap1D:
                                    M, Nc, rep, bcol, seed, col_map, n_valid)
 
     def cross_resampled_block(self, gene_ptr, tt, good, gene_mask, M, Nc, rep=None, bcol=None, seed=0, col_map=None, n_valid=None,
-                              gene_key=None):
+                              gene_key=None, zt=None, beta_scratch_bytes=None):
         """resample_rep=True for tests that arrive gene-major (mm_cross_resampled_block): the tests of gene slot g are the rows
         ``gene_ptr[g]:gene_ptr[g + 1]`` of ``tt`` [n_tests][n_groups]; everything else as ``contract_resampled``, and ``gene_key``
         [n_genes] keys the device draws of a gene (None: its slot).  Each plane is residualised into ONE plane-sized scratch in
         turn; no coefficient row is stored.  Returns (stats_mean, stats_var) host arrays [n_tests][8] -- the records
         ``contract_resampled`` gives for the same tests -- and ``rows(which, idx, to_host=True, out=None)``, the contract of
         ``contrast_design``'s closure: the coefficient rows of the tests ``idx`` on plane ``which``, from the per-test kernel on
-        that subset with the same draws (mm_cross_resampled_keyed).  The closure holds the scratch."""
+        that subset with the same draws (mm_cross_resampled_keyed).  The closure holds the scratch.
+
+        ``zt`` [n_tests][n_groups] (finite; checked here, the kernel trusts it): a covariate PER TEST, residualised by ``M`` like the
+        response -- test t then reads ``y - zt[t] * beta`` with beta the weighted slope of the residualised response on ``zt[t]``
+        (mm_cross_resampled_block_cov; a zero row leaves the response as it is).  The tiles go through a beta scratch of at most
+        ``beta_scratch_bytes`` (default ``CROSS_COV_SCRATCH_BYTES``; never less than one tile: 64 x ld bytes) a batch at a time,
+        and no number depends on the batches; ``rows`` materialises the response of the listed tests (mm_residualize_rank1) into a
+        scratch of the same bound and runs the per-test kernel on the copies: the block kernel's coefficients bit for bit."""
         (st_m, st_v), rows, _ = _cross_resampled_block([self.ym, self.yv], self.ld, self.B, self.ng, self.n_tested, gene_ptr, tt, good,
-                                                       gene_mask, M, Nc, rep, bcol, seed, col_map, n_valid, gene_key)
+                                                       gene_mask, M, Nc, rep, bcol, seed, col_map, n_valid, gene_key, zt, beta_scratch_bytes)
         return st_m, st_v, rows
 
     def cross_resampled_family(self, gene_ptr, tt, good, gene_mask, M, Nc, rep=None, bcol=None, seed=0, col_map=None, n_valid=None,
-                               gene_key=None):
+                               gene_key=None, zt=None):
         """``cross_resampled_block`` with the single-step max-T over every gene's tests (mm_cross_resampled_family): the same call,
         the same records and ``rows``, and a third closure ``family(scale, slab=None)`` on the uploaded tables and the one residual
         scratch.  ``scale`` [n_tests][2] holds 1 / se of every test on the mean and the variability plane, 0 for a member without
@@ -1138,7 +1145,10 @@ class Bootstrap1D:
         every gene, NaN in slot 0, the slots that are not family-valid and the slots from nb on), ``adj`` (host [n_tests][2][2]:
         t0, n_adj) and ``fam`` (host [n_genes][2][2]: n_valid_family, n_included), the layout of ``family_maxt``; beyond ``maxrow``
         it allocates nothing plane-sized, and the plane the scratch already holds is taken first.  ``slab``: the slots a
-        workgroup takes (default: the kernel's); no number depends on it."""
+        workgroup takes (default: the kernel's); no number depends on it.  A covariate per test (``zt``) is not offered: the
+        family kernel walks all tiles of a gene per slot and would need the beta rows of the whole gene at once."""
+        if zt is not None:
+            raise NotImplementedError("cross_resampled_family with a covariate per test (zt)")
         (st_m, st_v), rows, family = _cross_resampled_block([self.ym, self.yv], self.ld, self.B, self.ng, self.n_tested, gene_ptr, tt, good,
                                                             gene_mask, M, Nc, rep, bcol, seed, col_map, n_valid, gene_key)
         return st_m, st_v, rows, family
@@ -1374,14 +1384,16 @@ def _contract_resampled(src, ld, B, ng, n_genes, test_gene, tt, good, gene_mask,
 
 CROSS_BLOCK_TT = 8            # tests of one gene that a workgroup of mm_cross_resampled_block takes together (contract.hip: XB_TT)
 CROSS_BLOCK_MAX_GROUPS = 860  # 76 bytes of LDS per group, 64 KB a workgroup
+CROSS_COV_MAX_GROUPS = 468    # mm_cross_resampled_block_cov: 140 bytes of LDS per group (the tile's zt rows beside tt), 64 KB a workgroup
+CROSS_COV_SCRATCH_BYTES = 256 << 20   # the beta scratch of a batch of tiles, and the materialised responses of ``rows``
 
 
-def _block_tables(B, ng, n_genes,gene_ptr, tt, good, gene_mask, M, Nc, rep, bcol, n_valid, gene_key):
+def _block_tables(B, ng, n_genes,gene_ptr, tt, good, gene_mask, M, Nc, rep, bcol, n_valid, gene_key, zt=None):
     """The tables of mm_cross_resampled_block, coerced and checked on the host (the kernel trusts them): ``gene_ptr`` a CSR pointer
     over the rows of ``tt`` [n_tests][ng], one entry per gene slot; ``good`` [n_genes][ng]; ``gene_mask`` [n_genes] into ``M``
     [n_masks][ng][ng]; ``n_valid`` [n_genes] in 0..B + 1; ``rep`` / ``bcol`` [n_genes][ng][B] with, in the rows i < n of a gene with n
     good groups and the columns 1..nb - 1 the kernel reads, 0 <= rep < n and 1 <= bcol <= nb (nb = n_valid - 1, or B);
-    ``gene_key`` [n_genes] >= 0."""
+    ``gene_key`` [n_genes] >= 0; ``zt`` (or None) [n_tests][ng], finite."""
     gene_ptr = np.asarray(gene_ptr, dtype=np.int64).reshape(-1)
     tt = np.ascontiguousarray(tt, dtype=np.float64)
     good = np.ascontiguousarray(np.asarray(good, dtype=bool), dtype=np.uint8)
@@ -1416,16 +1428,23 @@ def _block_tables(B, ng, n_genes,gene_ptr, tt, good, gene_mask, M, Nc, rep, bcol
         gene_key = np.asarray(gene_key, dtype=np.int64)
         if gene_key.shape != (n_genes,) or (n_genes and gene_key.min() < 0):
             raise ValueError(f"{what}: gene_key must hold one non-negative key per gene")
-    return gene_ptr.astype(np.int32), tt, good, gene_mask, M, Nc, rep, bcol, n_valid, gene_key
+    if zt is not None:
+        zt = np.ascontiguousarray(zt, dtype=np.float64)
+        if ng > CROSS_COV_MAX_GROUPS:
+            raise NotImplementedError(f"{what} with a covariate per test and more than {CROSS_COV_MAX_GROUPS} groups")
+        if zt.shape != tt.shape or not np.isfinite(zt).all():
+            raise ValueError(f"{what}: zt must be finite and [n_tests][n_groups], one row per row of tt")
+    return gene_ptr.astype(np.int32), tt, good, gene_mask, M, Nc, rep, bcol, n_valid, gene_key, zt
 
 
-def _cross_resampled_block(planes, ld, B, ng, n_genes, gene_ptr, tt, good, gene_mask, M, Nc, rep, bcol, seed, col_map, n_valid, gene_key):
+def _cross_resampled_block(planes, ld, B, ng, n_genes, gene_ptr, tt, good, gene_mask, M, Nc, rep, bcol, seed, col_map, n_valid, gene_key,
+                           zt=None, beta_scratch_bytes=None):
     """``Bootstrap1D.cross_resampled_block`` / ``cross_resampled_family``: the records of every plane of ``planes``, the ``rows``
     closure and the ``family`` closure."""
     torch = _torch()
     s = _stream()
-    gene_ptr, tt, good, gene_mask, M, Nc, rep, bcol, n_valid, gene_key = _block_tables(B, ng, n_genes, gene_ptr, tt, good, gene_mask, M, Nc,
-                                                                                      rep, bcol, n_valid, gene_key)
+    gene_ptr, tt, good, gene_mask, M, Nc, rep, bcol, n_valid, gene_key, zt = _block_tables(B, ng, n_genes, gene_ptr, tt, good, gene_mask, M,
+                                                                                          Nc, rep, bcol, n_valid, gene_key, zt)
     n_tests = len(tt)
     if n_valid is not None and (col_map is None or col_map.dtype != torch.int32 or col_map.numel() < n_genes * (B + 1)):
         raise ValueError("cross_resampled_block: col_map must be the int32 device tensor [n_genes][num_boot + 1] of valid_cols")
@@ -1439,6 +1458,11 @@ def _cross_resampled_block(planes, ld, B, ng, n_genes, gene_ptr, tt, good, gene_
     d_nv = dev(n_valid) if n_valid is not None else None
     d_cm = col_map if n_valid is not None else None
     d_key = _up(gene_key) if gene_key is not None else None
+    if zt is not None:
+        budget = CROSS_COV_SCRATCH_BYTES if beta_scratch_bytes is None else int(beta_scratch_bytes)
+        n_tiles = n_genes * ((max_tests + CROSS_BLOCK_TT - 1) // CROSS_BLOCK_TT)
+        batch = int(min(max(1, n_tiles), max(1, budget // (ld * CROSS_BLOCK_TT * 8))))
+        d_zt, beta = _up(zt.reshape(-1)), empty((batch * ld * CROSS_BLOCK_TT,), torch.float64)
 
     def residualise(which):
         if held[0] != which and n_genes:
@@ -1449,8 +1473,13 @@ def _cross_resampled_block(planes, ld, B, ng, n_genes, gene_ptr, tt, good, gene_
     for which in range(len(planes)):
         residualise(which)
         st = empty((max(1, n_tests), 8), torch.float64)
-        _lib.call("mm_cross_resampled_block", P(yt), ld, B, ng, P(d_ptr), n_genes, max_tests, P(d_tt), P(d_good), P(d_nc), P(d_rep), P(d_bcol),
-                  P(d_cm), P(d_nv), P(d_key), seed, n_tests, P(st), s)
+        if zt is None:
+            _lib.call("mm_cross_resampled_block", P(yt), ld, B, ng, P(d_ptr), n_genes, max_tests, P(d_tt), P(d_good), P(d_nc), P(d_rep),
+                      P(d_bcol), P(d_cm), P(d_nv), P(d_key), seed, n_tests, P(st), s)
+        else:                                      # a batch of tiles at a time: beta of the batch, then its records (same stream)
+            for lo in range(0, n_tiles if n_tests else 0, batch):
+                _lib.call("mm_cross_resampled_block_cov", P(yt), ld, B, ng, P(d_ptr), n_genes, max_tests, P(d_tt), P(d_zt), P(d_good), P(d_nc),
+                          P(d_rep), P(d_bcol), P(d_cm), P(d_nv), P(d_key), seed, n_tests, lo, min(lo + batch, n_tiles), P(beta), P(st), s)
         stats.append(host(st)[:n_tests])
         d_stats.append(st)                         # (the family pass reads coef0 from the records on the device)
 
@@ -1458,11 +1487,34 @@ def _cross_resampled_block(planes, ld, B, ng, n_genes, gene_ptr, tt, good, gene_
         idx = np.asarray(idx, dtype=np.int64)
         out = _rows_out(out, len(idx), ld)
         residualise(int(which))
-        a, b = _up(test_gene[idx]), _up(tt[idx].reshape(-1))
         scrap = empty((max(1, len(idx)), 8), torch.float64)
-        _lib.call("mm_cross_resampled_keyed", P(yt), ld, B, ng, P(a), P(b), P(d_good), P(d_nc), P(d_rep), P(d_bcol), P(d_cm), P(d_nv), P(d_key),
-                  seed, len(idx), P(out), P(scrap), _stream())
+        if zt is None:
+            a, b = _up(test_gene[idx]), _up(tt[idx].reshape(-1))
+            _lib.call("mm_cross_resampled_keyed", P(yt), ld, B, ng, P(a), P(b), P(d_good), P(d_nc), P(d_rep), P(d_bcol), P(d_cm), P(d_nv),
+                      P(d_key), seed, len(idx), P(out), P(scrap), _stream())
+        else:
+            rows_cov(idx, out, scrap)
         return host(out)[: len(idx)] if to_host else out[: len(idx)]
+
+    def rows_cov(idx, out, scrap):
+        """The rows of the tests ``idx`` under a covariate per test: their responses are materialised a slice at a time, test l of a
+        slice on row block l, and the per-test kernel runs on the copies with the tables (mask, draws, surviving columns, key) of the
+        test's gene gathered to row block l."""
+        per = int(min(max(1, len(idx)), max(1, budget // (ng * ld * 8))))
+        copies = empty((per * ng, ld), torch.float64)
+        keys = gene_key if gene_key is not None else np.arange(n_genes, dtype=np.int64)
+        for lo in range(0, len(idx), per):
+            sl = idx[lo:lo + per]
+            g = test_gene[sl]
+            d_g, d_z, d_t, d_gd, d_k = dev(g.astype(np.int32)), dev(zt[sl].reshape(-1)), dev(tt[sl].reshape(-1)), dev(good[g].reshape(-1)), dev(keys[g])
+            _lib.call("mm_residualize_rank1", P(yt), ld, B, ng, P(d_g), P(d_z), P(d_good), P(d_nc), len(sl), P(copies), _stream())
+            own = dev(np.arange(len(sl), dtype=np.int32))
+            g_rep, g_bcol = (dev(rep[g]), dev(bcol[g])) if rep is not None else (None, None)
+            g_cm = d_cm.view(-1)[: n_genes * (B + 1)].view(n_genes, B + 1)[d_g.long()].contiguous() if d_cm is not None else None
+            g_nv = dev(n_valid[g]) if n_valid is not None else None
+            o, sc = out[lo:lo + len(sl)], scrap[lo:lo + len(sl)]
+            _lib.call("mm_cross_resampled_keyed", P(copies), ld, B, ng, P(own), P(d_t), P(d_gd), P(d_nc), P(g_rep), P(g_bcol), P(g_cm), P(g_nv),
+                      P(d_k), seed, len(sl), P(o), P(sc), _stream())
 
     def family(scale, slab=None):
         scale = np.asarray(scale, dtype=np.float64)

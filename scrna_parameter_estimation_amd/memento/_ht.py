@@ -440,6 +440,80 @@ def eqtl_tables(good, cols, cov, trt, Nc, resampled=False):
     return d
 
 
+def interaction_context(interaction, ng):
+    """The context vector of ``ht_1d_eqtl(interaction=...)``: one finite value per group from an array, a Series or a one-column
+    frame; ValueError otherwise (more than one column, another length, a non-finite value)."""
+    ctx = np.asarray(getattr(interaction, 'values', interaction), dtype=np.float64)
+    if ctx.ndim == 2 and ctx.shape[1] == 1:
+        ctx = ctx[:, 0]
+    if ctx.ndim != 1:
+        raise ValueError("interaction must be ONE value per group (an array, a Series or a one-column frame), not several columns")
+    if len(ctx) != ng or not np.isfinite(ctx).all():
+        raise ValueError(f"interaction must be one finite value per group ({ng})")
+    return ctx
+
+
+def eqtl_interaction_tables(good, cols, cov, ctx, trt, Nc):
+    """``eqtl_tables`` for the genotype-by-context tests of ``ht_1d_eqtl(interaction=ctx)``: test (row ``k``, SNP ``s`` of ``cols[k]``)
+    is of ``a = g_s * ctx`` after the shared covariates ``[cov | ctx]`` and the covariate of its own ``g_s``.  With M the residual
+    maker of ``[1 | cov | ctx]`` on the row's good groups (``design.residual_parts``, once per distinct mask), z = M g_s and
+    a~ = M a, the per-test covariate comes out by a rank-one step (Frisch-Waugh), for all SNPs of a row at once:
+      ``zt_mat`` [test][group]  z, or exactly zero where its wbar-weighted sum of squares is <= ``design.SS_DEGENERATE`` (g_s inside
+                                the shared span: the test proceeds on the shared covariates alone);
+      ``tt_mat`` [test][group]  tt = a~ - z (z' W a~) / (z' W z), the fully residualised treatment;
+      ``Wmat``   [test][group]  Nc_j tt_j / sum Nc tt^2 on the good groups -- the weight row of ``design.weight_rows`` on
+                                ``[cov | ctx | g_s]``: tt is W-orthogonal to that whole design, so its hat-matrix term drops out;
+      ``has_test`` [test]       false (no test: zero rows in ``tt_mat`` and ``Wmat``) where the wbar-weighted sum of squares of tt
+                                is <= ``SS_DEGENERATE`` (carriers in one context only, a monomorphic SNP, a constant context), where
+                                the treatment is all ones on the good groups, and for a row without a good group;
+    ``gene_ptr``, ``test_row``, ``Mstack`` / ``row_mask`` as in ``eqtl_tables`` (one maker per mask)."""
+    good = np.asarray(good, dtype=bool)
+    n_rows, ng = good.shape
+    Nc = np.asarray(Nc, dtype=np.float64)
+    ctx = np.asarray(ctx, dtype=np.float64).reshape(ng)
+    covx = np.column_stack([np.asarray(cov, dtype=np.float64).reshape(ng, -1), ctx])
+    cache, m_index = {}, {}
+    counts, parts, Ms = [], [], []
+    row_mask = np.zeros(n_rows, dtype=np.int32)
+    for k in range(n_rows):
+        mask, ck = good[k].tobytes(), tuple(cols[k])
+        counts.append(len(ck))
+        if mask not in m_index:
+            m_index[mask] = len(Ms)
+            Ms.append(_design.residual_parts(covx, np.zeros((ng, 1)), Nc, good[k])[0])
+        row_mask[k] = m_index[mask]
+        if not ck:
+            continue
+        key = (mask, ck)
+        if key not in cache:
+            S, idx = len(ck), np.flatnonzero(good[k])
+            g = _take(trt, ck)
+            a = g * ctx[:, None]
+            zt, tt, W, has = np.zeros((S, ng)), np.zeros((S, ng)), np.zeros((S, ng)), np.zeros(S, dtype=bool)
+            if len(idx):
+                res = _design.residual_parts(covx, np.column_stack([g, a]), Nc, good[k])[1]
+                z, at = res[:S, idx], res[S:, idx]
+                w = Nc[idx]
+                wbar = w / w.sum()
+                z = np.where(((z * z) @ wbar > _design.SS_DEGENERATE)[:, None], z, 0.0)
+                zz = (z * z) @ w
+                with np.errstate(divide="ignore", invalid="ignore"):
+                    slope = np.where(zz > 0, ((z * at) @ w) / zz, 0.0)
+                t = at - z * slope[:, None]
+                has = ((t * t) @ wbar > _design.SS_DEGENERATE) & ~(a[idx] == 1).all(axis=0)
+                t = np.where(has[:, None], t, 0.0)
+                with np.errstate(divide="ignore", invalid="ignore"):
+                    Wg = np.where(has[:, None], t * w[None, :] / ((t * t) @ w)[:, None], 0.0)
+                zt[:, idx], tt[:, idx], W[:, idx] = z, t, Wg
+            cache[key] = (zt, tt, W, has)
+        parts.append(cache[key])
+    gene_ptr = np.concatenate([[0], np.cumsum(counts, dtype=np.int64)]).astype(np.int64)
+    cat = lambda i, empty: np.concatenate([p[i] for p in parts], axis=0) if parts else empty
+    return SimpleNamespace(gene_ptr=gene_ptr, test_row=np.repeat(np.arange(n_rows, dtype=np.int64), counts),
+                           zt_mat=cat(0, np.zeros((0, ng))), tt_mat=cat(1, np.zeros((0, ng))), Wmat=cat(2, np.zeros((0, ng))),
+                           has_test=cat(3, np.zeros(0, dtype=bool)), Mstack=np.stack(Ms) if Ms else np.zeros((0, ng, ng)), row_mask=row_mask)
+
+
 def weight_row_designs(test_row, Wmat, good):
     """The weight rows of plain tests as the CSR designs of ``contrast_design``: design t lists the good groups of row block
     ``test_row[t]`` in ascending order (zero weights included: they take part in the validity of a column) with the weights

@@ -818,7 +818,7 @@ def ht_1d_joint(adata, treatment, covariate=None, num_boot=10000, rng='replay', 
 
 
 def ht_1d_eqtl(adata, genotypes, gene_snp_pairs, covariate=None, num_boot=5000, num_cpus=1, rng='replay', fill_seed=0, max_rows=None,
-               approx=False, resampling='bootstrap', resample_rep=False, adjust=False, **not_offered):
+               approx=False, resampling='bootstrap', resample_rep=False, adjust=False, interaction=None, **not_offered):
     """cis-eQTL scan: every kept gene against its own list of SNPs, hundreds per gene (the reference's largest analysis,
     analysis/lupus/run_memento.py:29-52, :84-109: one group per donor, ``treatment_for_gene``, ``resample_rep=True``).
 
@@ -848,7 +848,20 @@ def ht_1d_eqtl(adata, genotypes, gene_snp_pairs, covariate=None, num_boot=5000, 
     (treatment all ones) are no joint draws with them: they get NaN adjusted values and do not count in ``n_family``.  A family
     never spans gene chunks and ``max_rows`` changes no bit.  ``get_eqtl_gene_result`` turns the result into an eGene table.
 
-    Not offered: ``strict``, ``ci``, ``max_boot``, ``treatment_for_gene`` (TypeError), and a gene-sharded run (NotImplementedError).
+    ``interaction``: one finite value per group (array, Series or one-column frame, in the group order; more than one column or a
+    wrong length: ValueError) -- a context ``ctx`` such as stimulated / control, cell type or dose.  Every (gene, SNP) test is then of
+    the GENOTYPE-BY-CONTEXT term of  y ~ 1 + covariate + ctx + g_s + g_s * ctx  (a response eQTL): ``ctx`` joins the shared covariates
+    (the hat matrix is a pseudo-inverse, so passing it in ``covariate`` as well changes nothing), the genotype main effect g_s is a
+    covariate of the test's own, taken out by a rank-one step on the device (mm_cross_resampled_block_cov), and the coefficient
+    columns hold the interaction coefficient.  A pair gets NO TEST (NaN coef / se / p-value, outside any family) where the fully
+    residualised treatment has a weighted sum of squares <= ``design.SS_DEGENERATE`` on the gene's good groups (carriers in one
+    context only, a monomorphic SNP, a constant context) or the treatment is all ones; a genotype inside the span of the shared
+    covariates counts as no covariate.  The rows, their order and every other argument are those of the plain call, and
+    ``adjust=True`` with ``resample_rep=False`` takes the gene's interaction tests as the family.  ``None``: the plain call.
+
+    Not offered: ``strict``, ``ci``, ``max_boot``, ``treatment_for_gene`` (TypeError), a gene-sharded run (NotImplementedError), and
+    ``adjust=True`` together with ``resample_rep=True`` and ``interaction`` (NotImplementedError: the family kernel would need the
+    rank-one coefficients of a whole gene at once).
 
     Returns a DataFrame (gene, snp, de_coef, de_se, de_pval, dv_coef, dv_se, dv_pval), gene-major over the kept genes, each gene's
     SNPs in its list order; with ``adjust=True`` also de_pval_adj, dv_pval_adj and n_family, after these.  The arrays go to
@@ -859,7 +872,11 @@ def ht_1d_eqtl(adata, genotypes, gene_snp_pairs, covariate=None, num_boot=5000, 
     resample_rep, approx, adjust = bool(resample_rep), bool(approx), bool(adjust)
     if adjust and resampling != 'bootstrap':
         raise ValueError("ht_1d_eqtl(adjust=True) needs resampling='bootstrap': the max-T null is centred on the observed coefficient")
+    if interaction is not None and adjust and resample_rep:
+        raise NotImplementedError("ht_1d_eqtl(interaction=..., adjust=True, resample_rep=True): the resampled family needs the "
+                                  "per-test covariate's coefficients of a whole gene at once")
     m = adata.uns['memento']
+    ctx = None if interaction is None else _ht.interaction_context(interaction, len(m['groups']))
     st = m['_hip']
     comm = getattr(st, 'comm', None)
     if comm is not None and comm.world > 1:
@@ -893,9 +910,16 @@ def ht_1d_eqtl(adata, genotypes, gene_snp_pairs, covariate=None, num_boot=5000, 
         rs['genes'] += G
         rs['genes_refilled'] += int(refilled.sum())
         rs['gene_refilled'][g0:g1] = refilled
-        d = _ht.eqtl_tables(good, gene_cols[g0:g1], cov, trt_all, mv.Nc_list, resampled=resample_rep)
+        if ctx is None:
+            d = _ht.eqtl_tables(good, gene_cols[g0:g1], cov, trt_all, mv.Nc_list, resampled=resample_rep)
+            zt_mat = None
+        else:                                                     # no test: a zero weight row (a record that is no family member)
+            d = _ht.eqtl_interaction_tables(good, gene_cols[g0:g1], cov, ctx, trt_all, mv.Nc_list)
+            d.rr_test, zt_mat = d.has_test, d.zt_mat
         n_tests = len(d.test_row)
         no_group = ~good[d.test_row].any(axis=1)
+        if ctx is not None:
+            no_group = no_group | ~d.has_test
         is_rr = d.rr_test if resample_rep else np.zeros(n_tests, dtype=bool)
         rr_idx, pl_idx = np.flatnonzero(is_rr), np.flatnonzero(~is_rr)
         local = np.zeros(n_tests, dtype=np.int64)                 # a test's number inside its part
@@ -912,14 +936,16 @@ def ht_1d_eqtl(adata, genotypes, gene_snp_pairs, covariate=None, num_boot=5000, 
             parts.append((~is_rr, rows_pl))
             if adjust and not resample_rep:                       # the family of a gene: all its tests, on the rows they share
                 scale = engine.family_scale(st_m, st_v)
+                scale[no_group[pl_idx]] = 0.0
                 _, adj, fam = bs.family_maxt(d.gene_ptr, *tables, scale)
                 st.last_eqtl = SimpleNamespace(gene_ptr=d.gene_ptr, tables=tables, scale=scale, adj=adj, fam=fam, rows=rows_pl, n_valid=None)
         if len(rr_idx):                                           # resampled tests: gene-major, keyed by the gene's position
             col_map, n_valid = _ht.surviving_cols(bs, good, num_boot)                                     # hypothesis_test.py:249-251
             rr_ptr = np.concatenate([[0], np.cumsum(np.bincount(d.test_row[rr_idx], minlength=G))])
             block = bs.cross_resampled_family if adjust else bs.cross_resampled_block
+            per_test = {} if zt_mat is None else dict(zt=zt_mat[rr_idx])
             st_m, st_v, rows_rr, *family = block(rr_ptr, d.tt_mat[rr_idx], good, d.row_mask, d.Mstack, mv.Nc_list, seed=fill_seed + 17,
-                                                 col_map=col_map, n_valid=n_valid, gene_key=np.arange(g0, g1, dtype=np.int64))
+                                                 col_map=col_map, n_valid=n_valid, gene_key=np.arange(g0, g1, dtype=np.int64), **per_test)
             stats[0][rr_idx], stats[1][rr_idx] = st_m, st_v
             parts.append((is_rr, rows_rr))
             if adjust:                                            # the family of a gene: its resampled tests, which share the draws
@@ -954,6 +980,8 @@ def ht_1d_eqtl(adata, genotypes, gene_snp_pairs, covariate=None, num_boot=5000, 
     flat = np.array([j for k in gene_cols for j in k], dtype=np.int64)
     df = pd.DataFrame({'gene': np.repeat(np.asarray(names[:G_all], dtype=object), n_snps), 'snp': snp_names[flat]})
     m['1d_ht_eqtl'] = dict(out, gene=df['gene'].values, snp=df['snp'].values)
+    if ctx is not None:
+        m['1d_ht_eqtl'].update(interaction=True, context=ctx)
     df['de_coef'], df['de_se'], df['de_pval'] = out['mean_coef'], out['mean_se'], out['mean_asl']
     df['dv_coef'], df['dv_se'], df['dv_pval'] = out['var_coef'], out['var_se'], out['var_asl']
     if adjust:
